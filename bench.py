@@ -2,13 +2,18 @@
 """bench.py -- clips/s of the hot path (log-mel -> Cnn8Rnn -> w2v-mean text encoder -> frame
 similarity -> FrameBceLoss), forward + backward + gradient all-reduce + clip + Adam, on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 Workload = BASELINE.json configs[1]: biencoder Cnn8Rnn + EmbeddingAgg(512, mean) + match.DotProduct, fp32,
 batch 64 per GPU, 10 s @ 32 kHz synthetic clips, dropout on, train-mode BatchNorm (weak scaling: per-GPU batch
 fixed).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times K steps, writes the last timed step's outputs (--dump-outputs) and prints the line with
+what the timed region itself recorded.  --full adds every leg that needs runs of its own: the isolated-kernel pass of an
+overlapped step, the direct-kernel and other-arithmetic legs, the MFMA ceiling probes, the other workloads, the collectives
+timed alone (N > 1) and the CPU oracle baseline.
 """
 import argparse
 import glob
@@ -199,6 +204,32 @@ def mem_record(device):
             "device_mallocs": int(st.get("num_device_alloc", 0)), "alloc_retries": int(st.get("num_alloc_retries", 0))}
 
 
+def dump_outputs(out_dir, runner, loss, max_params=10_000_000, max_grad=1 << 22, max_buffers=1 << 20):
+    """--dump-outputs DIR: what StrongRunner.train_step computed in the last timed step, as float32 .npy files (<= 60 MB in all):
+    loss.npy (the returned loss, shape (1,)), params.npy (the flat parameter buffer after clip + Adam), grad.npy (the flat gradient
+    the step's Adam consumed) and buffers.npy (the floating-point module buffers -- BatchNorm running statistics -- concatenated in
+    named_buffers() order).  An array longer than its cap is replaced by a fixed sample: the sorted first `cap` indices of
+    torch.randperm(numel) under a CPU generator seeded with 0, the same on every run of the same model."""
+    import numpy as np
+
+    def sample(t, cap):
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            t = t[idx.to(t.device)]
+        return t.float().cpu().numpy()
+
+    bufs = [b.detach().reshape(-1).float() for _, b in runner.model.named_buffers() if b.is_floating_point()]
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "params": sample(runner.flat.flat, max_params),
+              "grad": sample(runner.flat.grad, max_grad),
+              "buffers": sample(torch.cat(bufs), max_buffers) if bufs else np.zeros(0, np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def run_steps(runner, batch, k, sync, spread=None):
     """k training steps; returns (wall seconds incl. the closing sync, host seconds spent INSIDE train_step = the time one core
     needs to enqueue a step: ctypes launches + autograd bookkeeping, no synchronisation), and the last loss.
@@ -364,6 +395,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="clips per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg that needs runs of its own (isolated-kernel pass, direct "
+                         "kernels, other arithmetics, MFMA ceiling probes, other workloads, collectives alone, CPU baseline); "
+                         "the --no-* options below trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameters, gradient, BatchNorm buffers) to DIR/<name>.npy "
+                         "as float32 (a fixed seeded sample where an array is large; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cross-encoder", action="store_true",
                     help="time BASELINE configs[3] instead: the same biencoder with CrossAttentionGating(512) and the "
@@ -401,6 +439,8 @@ def main():
                     help="arithmetic of the 3x3 conv forward/dgrad kernels of the TIMED run: fp32 = exact fp32 MFMA "
                          "(the contract's number); x3 = opt-in 3 x bf16 split on the bf16 MFMA (conv_x3.hip)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         sys.exit(self_launch(args))
 
@@ -507,6 +547,9 @@ def main():
     mem_main = mem_record(device)
     log(f"timed {args.steps} steps in {dt:.3f} s (host enqueue {host_s / args.steps * 1e3:.2f} ms/step)")
     prof, ops.PROFILE = ops.PROFILE, None
+    if args.dump_outputs and rank == 0:          # before any further leg moves the runner's state on
+        shapes = dump_outputs(args.dump_outputs, runner, loss)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
     comm_timing = None
     if runner.buckets is not None:
         runner.buckets.record = False
@@ -521,12 +564,15 @@ def main():
     # ---- roofline of the dominant kernel family (halo-tile conv: forward+dgrad launches), HIP events recorded on
     # the launch stream over the timed region.  The timed region runs the weight-gradient convs on a second stream
     # (they overlap the dgrad/BatchNorm chain), which stretches every overlapped kernel's own start-to-end time;
-    # a second, untimed pass of the same K steps with that overlap switched off gives the isolated kernel rate.
+    # a second, untimed pass of the same K steps with that overlap switched off gives the isolated kernel rate (--full only: without
+    # it an overlapped run reports no roofline).
     fam = families(prof)
     overlap = ops.side_stream_enabled()         # auto: off for the fp32-accurate arithmetics, on in the bf16 mode (settings.py)
     side_setting = ops.WGRAD_SIDE_STREAM
     fam_iso = fam
-    if overlap:
+    if overlap and not args.full:
+        fam_iso = None
+    elif overlap:
         ops.WGRAD_SIDE_STREAM = False
         ops.PROFILE = {}
         for _ in range(args.steps):
@@ -537,7 +583,7 @@ def main():
     # ---- the same K steps with the direct halo-tile kernels everywhere (TAG_CONV_WINOGRAD=0): what the Winograd form of the deep
     # layers is worth on this box, in the driver-timed record
     alt_algo = None
-    if args.conv_math == "fp32" and ops.CONV_WINOGRAD and not args.no_alt:
+    if args.full and args.conv_math == "fp32" and ops.CONV_WINOGRAD and not args.no_alt:
         ops.CONV_WINOGRAD = False
         runner.train_step(dict(batch))
         sync()
@@ -551,7 +597,7 @@ def main():
                                "value": round(clips / dtd, 2), "unit": "clips/s", "ms_per_step": round(dtd / args.steps * 1e3, 3)}}
     # ---- the same K steps with the opt-in conv arithmetic (reported beside the contract's number, never as `value`)
     alt = None
-    if args.conv_math == "fp32" and not args.no_alt:
+    if args.full and args.conv_math == "fp32" and not args.no_alt:
         alt = {}
         desc = {"x3": "fp32 operands split exactly into 3 bf16 terms, 6 partial products on v_mfma_f32_32x32x16_bf16, f32 "
                       "accumulate (forward, dgrad and wgrad convs; same parity tolerances as fp32; opt-in TAG_CONV_MATH=x3)",
@@ -606,18 +652,19 @@ def main():
         ops.CONV_MATH = "fp32"
         ops.ACT_DTYPE = "fp32"
     loss_value = round(runner.loss_value(loss), 6)
-    roof = roofline_of(fam, fam_iso, args.steps, "bf16" if args.dtype == "bf16" else "fp32", args.conv_math, args.batch, overlap)
-    if roof is not None and rank == 0 and not args.no_probe:
+    roof = None if fam_iso is None else roofline_of(fam, fam_iso, args.steps, "bf16" if args.dtype == "bf16" else "fp32",
+                                                    args.conv_math, args.batch, overlap)
+    if roof is not None and rank == 0 and args.full and not args.no_probe:
         kind = "bf16" if args.conv_math in ("bf16", "x3", "x9") else "f32"
         roof["measured_ceiling"] = {"random_operands": mfma_probe(f"{kind}_random", 50.0, local),
                                     "constant_operands": mfma_probe(f"{kind}_constant", 50.0, local)}
     others = None
     main_wl = not (args.crnn or args.cross_attention or args.cross_encoder)
-    if world == 1 and main_wl and args.conv_math == "fp32" and not args.no_others:
+    if args.full and world == 1 and main_wl and args.conv_math == "fp32" and not args.no_others:
         del runner, model
         torch.cuda.empty_cache()
         others = other_workloads(args, device, log)
-    comm_only_res = comm_only() if world > 1 else None        # every rank takes part; a few ms
+    comm_only_res = comm_only() if world > 1 and args.full else None        # every rank takes part; a few ms
     if rank == 0:
         out = {"metric": "clips/sec (10 s@32 kHz, 1-phrase) fwd+bwd", "value": round(value, 2), "unit": "clips/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -677,7 +724,7 @@ def main():
                            "bucket_ms_in_step": comm_timing["bucket_ms"] if comm_timing else None,
                            "exposed_ms_per_step": comm_timing["exposed_ms_per_step"] if comm_timing else None,
                            "comm_only": comm_only_res}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing the CPU oracle (bounded sample)")
             out["cpu_baseline"] = cpu_baseline()
         # compact digest of every timed leg as the LAST key: a reader who only keeps the tail of this line still sees them

@@ -340,6 +340,8 @@ def case_frontend():
     out = {}
     for kind in ("cnn8rnn", "crnn"):
         out[f"sine_{kind}"] = O.logmel(x, kind).numpy()
+        # fp64: free of the fp32 FFT's rounding at the leakage floor, so the same on every host's FFT / BLAS code path
+        out[f"sine_{kind}_f64"] = O.logmel(x.double(), kind).numpy()
         out[f"noise_{kind}"] = O.logmel(noise, kind).numpy()
         out[f"noise_power_{kind}"] = O.mel_spectrogram(noise, kind).numpy()
         w, fb = O.frontend_tables(kind)

@@ -43,11 +43,37 @@ floor = (o64["token_emb"] - token_emb.double()).abs().max().item()
 print(f"transformers {transformers.__version__}: oracle vs ClapTextModel max abs err {err:.2e}; "
       f"fp32-vs-fp64 floor on token_emb {floor:.2e} (|max| {token_emb.abs().max().item():.2f})")
 assert err < 5e-6
+# the same modules in fp64: reference outputs free of fp32 GEMM rounding, which differs between hosts' BLAS code paths.  The
+# eager attention takes its softmax with dtype=torch.float32 (an upcast meant for half precision); for this run that upcast is
+# to fp64, so that no stage rounds to fp32
+text64, proj64 = text.double(), proj.double()
+_softmax = torch.nn.functional.softmax
+
+
+def _softmax_f64(x, dim=None, _stacklevel=3, dtype=None):
+    return _softmax(x, dim=dim, dtype=torch.float64 if x.dtype == torch.float64 else dtype)
+
+
+torch.nn.functional.softmax = _softmax_f64
+try:
+    with torch.no_grad():
+        out64 = text64(input_ids=ids, attention_mask=mask)
+        f64 = {"last_hidden_state_f64": out64.last_hidden_state, "pooler_output_f64": out64.pooler_output,
+               "token_emb_f64": proj64(out64.last_hidden_state),
+               "seq_emb_f64": torch.nn.functional.normalize(proj64(out64.pooler_output), dim=-1)}
+finally:
+    torch.nn.functional.softmax = _softmax
+o64 = C.laion_clap_encoder_forward(st64, ids, mask, cfg.num_attention_heads, cfg.layer_norm_eps)
+h64, pooled64 = C.text_model_forward(st64, ids, mask, cfg.num_attention_heads, cfg.layer_norm_eps, prefix="model.")
+err64 = max((h64 - f64["last_hidden_state_f64"]).abs().max().item(), (pooled64 - f64["pooler_output_f64"]).abs().max().item(),
+            (o64["token_emb"] - f64["token_emb_f64"]).abs().max().item(), (o64["seq_emb"] - f64["seq_emb_f64"]).abs().max().item())
+print(f"fp64: oracle vs ClapTextModel max abs err {err64:.2e}")
+assert err64 < 1e-10
 valid = mask.bool()
 np.savez_compressed(os.path.join(ROOT, "tests", "golden", "clap_text_tiny.npz"),
                     input_ids=ids.numpy(), attention_mask=mask.numpy(), n_heads=cfg.num_attention_heads,
                     eps=cfg.layer_norm_eps, last_hidden_state=out.last_hidden_state.numpy(),
                     pooler_output=out.pooler_output.numpy(), token_emb=token_emb.numpy(), seq_emb=seq_emb.numpy(),
-                    transformers_version=transformers.__version__,
+                    transformers_version=transformers.__version__, **{k: v.numpy() for k, v in f64.items()},
                     **{"w/" + k: v.numpy() for k, v in st.items()})
 print("wrote clap_text_tiny.npz", os.path.getsize(os.path.join(ROOT, "tests", "golden", "clap_text_tiny.npz")), "bytes")

@@ -34,7 +34,7 @@ def test_bench_launches_its_own_ranks(extra):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "8", "--no-cpu-baseline", "--no-alt"] + extra, env=env, capture_output=True, text=True,
+                        "--batch", "8", "--full", "--no-cpu-baseline", "--no-alt"] + extra, env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -63,7 +63,7 @@ def test_bench_eight_ranks_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--batch", "4", "--no-cpu-baseline", "--no-alt", "--dtype", "bf16"], env=env, capture_output=True,
+                        "--batch", "4", "--full", "--no-cpu-baseline", "--no-alt", "--dtype", "bf16"], env=env, capture_output=True,
                        text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -7,7 +7,7 @@ R=${1:-r05}
 OUT=gpurun_out/prof_$R
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-alt --no-others --no-probe"
+BENCH="python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-alt --no-others --no-probe"
 for mode in fp32 bf16; do
   extra=""; [ $mode = bf16 ] && extra="--dtype bf16"
   # steps in the traced process: 2 warm-up + 5 timed (+ 5 of bench.py's isolated pass where the wgrad side stream is on = bf16 mode)
