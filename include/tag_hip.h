@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-#define TAG_ABI_VERSION 3   /* bump whenever an entry point is added or changes its arguments / data layout (lib.py checks it FIRST) */
+#define TAG_ABI_VERSION 3   /* bump whenever an EXISTING entry point changes its arguments / data layout (lib.py checks it FIRST);
+                               entry points that are only added do not bump it: a library without them fails lib.load() on its
+                               build id and on the symbol lookup */
 #define TAG_EINVAL (-1) /* bad argument (shape not supported, null pointer, ...) */
 #define TAG_ELAUNCH (-2)
 
@@ -102,6 +104,24 @@ int tag_affine_forward(const float* x, long rows, int C, const float* scale, con
 /* dgamma[c] = sum dy*xhat, dbeta[c] = sum dy  for a plain affine BN (bn0): xhat=(x-mean)*invstd */
 int tag_bn_param_grad(const float* x, const float* dy, long rows, int C, const float* mean,
                       const float* invstd, float* dgamma, float* dbeta, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training-time augmentation of the bn0 output (csrc/augment.hip): SpecAugment = torchlibrosa's
+ * SpecAugmentation / DropStripes (augmentation.py; time dropper first, then frequency), applied at
+ * models/audio_encoder.py:126-131,192-195, and mixup = utils/train_util.py:73-88 do_mixup, applied at
+ * models/audio_encoder.py:197-200.
+ *   lm (B, F, NM) log-mel in dB (frames x mel bins); scale / shift (NM): the bn0 affine, applied as
+ *   fmaf(lm, scale[m], shift[m]) exactly as the Cin = 1 convolutions apply it on load (both null: plain copy);
+ *   stripes (B, n_time + n_freq, 2) int32 [bgn, width]: rows 0..n_time-1 zero frames [bgn, bgn+width), the rest zero
+ *   mel bins (null when n_time = n_freq = 0; the values are compared, never used as addresses);
+ *   lam (B) fp32 or null: x0[k] = x[2k]*lam[2k] + x[2k+1]*lam[2k+1] (two products, one add), B even.
+ *   x0 (B' = B, or B/2 with lam, F, NM).  NM % 4 == 0, n_time, n_freq <= 8.
+ * backward: dbn0 (B, F, NM) = mask[b] * lam[b] * dx0[b/2]  (dx0[b] without lam); masked elements exactly 0.
+ */
+int tag_augment_forward(const float* lm, const float* scale, const float* shift, const int* stripes, int n_time,
+                        int n_freq, const float* lam, float* x0, int B, int F, int NM, void* stream);
+int tag_augment_backward(const float* dx0, const int* stripes, int n_time, int n_freq, const float* lam, float* dbn0,
+                         int B, int F, int NM, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A1: 3x3 convolution, stride 1, pad 1, no bias (models/panns.py:25-33,49-50), channels-last,

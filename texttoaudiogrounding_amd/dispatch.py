@@ -546,6 +546,47 @@ def bn_param_grad(x2d, dy2d, st: BNStat, dg_out=None, db_out=None):
     return dg, db
 
 
+def _stripe_counts(stripes, n_time, B):
+    if stripes is None:
+        return 0, 0
+    if (not stripes.is_cuda or not stripes.is_contiguous() or stripes.dtype != torch.int32 or stripes.dim() != 3
+            or stripes.shape[0] != B or stripes.shape[2] != 2):
+        raise RuntimeError(f"augment: stripes must be a contiguous device int32 (B={B}, n_time + n_freq, 2) table, got "
+                           f"{stripes.dtype} {tuple(stripes.shape)} on {stripes.device}")
+    if not 0 <= n_time <= stripes.shape[1]:
+        raise RuntimeError(f"augment: n_time {n_time} outside the table's {stripes.shape[1]} rows")
+    return n_time, stripes.shape[1] - n_time
+
+
+def augment_forward(lm, scale=None, shift=None, stripes=None, n_time=0, lam=None):
+    """SpecAugment + mixup of the bn0 output (csrc/augment.hip): lm (B,F,NM) -> x0 (B or B/2, F, NM), the bn0 affine (scale,
+    shift) applied as the Cin = 1 convolutions apply it, then the stripes' zeros (stripes: int32 (B, n_time + n_freq, 2)
+    [bgn, width], the first n_time rows along frames), then do_mixup with lam (B,) when given."""
+    lm = _chk(lm, "lm")
+    B, Fr, NM = lm.shape
+    nt, nf = _stripe_counts(stripes, n_time, B)
+    lam = None if lam is None else _chk(lam, "mixup_lambda")
+    if lam is not None and (lam.numel() != B or B % 2):
+        raise RuntimeError(f"augment: mixup needs an even batch and fp32 lambda of length B={B}, got {tuple(lam.shape)}")
+    x0 = _empty(B // 2 if lam is not None else B, Fr, NM, like=lm)
+    call("tag_augment_forward", ptr(lm), ptr(scale), ptr(shift), ptr(stripes), nt, nf, ptr(lam), ptr(x0), B, Fr, NM)
+    return x0
+
+
+def augment_backward(dx0, B, stripes=None, n_time=0, lam=None):
+    """Gradient of augment_forward with respect to its masked input: dbn0 (B,F,NM) = mask[b] * lam[b] * dx0[b/2] (dx0[b]
+    without lam)."""
+    dx0 = _chk(dx0, "grad")
+    _, Fr, NM = dx0.shape
+    nt, nf = _stripe_counts(stripes, n_time, B)
+    lam = None if lam is None else _chk(lam, "mixup_lambda")
+    if dx0.shape[0] != (B // 2 if lam is not None else B):
+        raise RuntimeError(f"augment_backward: dx0 has {dx0.shape[0]} clips for B={B}")
+    dbn0 = _empty(B, Fr, NM, like=dx0)
+    call("tag_augment_backward", ptr(dx0), ptr(stripes), nt, nf, ptr(lam), ptr(dbn0), B, Fr, NM)
+    return dbn0
+
+
 def dropout_mask(seed, shape, p, device, pooled=False):
     """The keep mask (0/1 bytes) a kernel draws for `seed`; pooled=True: the generator of the pooled activations' dropout
     (one hash per 4 elements; bnact_pool / bnrelu_pool_backward), else the per-element one (mean_w, dropout, attention)."""
@@ -605,6 +646,7 @@ def align_dot(audio, text, l2norm=False, scaled=False):
     """align.DotProduct forward (models/align.py:14-31): (B,T,D),(B,N,D) -> (B,B,T,N); F.normalize of both operands first
     when l2norm (row kernels), then the MFMA GEMM with the [/sqrt D ->] sigmoid -> clamp -> (B,B,T,N) scatter epilogue."""
     audio, text = _chk(audio, "audio"), _chk(text, "text")
+    _check_pair_batch("align_dot", audio, text)         # models/align.py:20-21 asserts a_bs == t_bs, a_dim == t_dim
     B, T, D = audio.shape
     N = text.shape[1]
     if l2norm:
@@ -886,9 +928,20 @@ def embed_mean_backward_into(dtab, dseq, dtok, text, text_len):
     return dtab
 
 
+def _check_pair_batch(what, a, t):
+    """Heads that pair audio clip b with text row b: the batches must agree (the reference's broadcast / assert fails otherwise;
+    mixup halves the audio batch of a BiEncoder).  Raised before any launch: the kernels take B from the audio side."""
+    if a.dim() != 3 or t.dim() < 2 or t.shape[0] != a.shape[0] or t.shape[-1] != a.shape[2]:
+        raise RuntimeError(f"{what}: audio {tuple(a.shape)} and text {tuple(t.shape)} must agree in batch and embedding size "
+                           f"(audio clip b is scored against text row b; mixup halves the audio batch)")
+
+
 def match_forward(audio, text, kind, l2norm, scale):
     """match.DotProduct (kind 0) / match.ExpNegL2 (kind 1), text_level='seq' (models/match.py:16-33,43-60): (B,T,D),(B,D) -> (B,T)."""
     a, t = _chk(audio, "audio_emb"), _chk(text, "text_emb")
+    _check_pair_batch("frame_match", a, t)
+    if t.dim() != 2:
+        raise RuntimeError(f"frame_match: text_emb must be (B, D), got {tuple(t.shape)}")
     B, T, D = a.shape
     sim = _empty(B, T, like=a)
     call("tag_match_forward", ptr(a), ptr(t), ptr(sim), int(kind), int(l2norm), int(scale), B, T, D)
@@ -897,6 +950,9 @@ def match_forward(audio, text, kind, l2norm, scale):
 
 def match_backward(audio, text, sim, dsim, kind, l2norm, scale):
     a, t = _chk(audio, "audio_emb"), _chk(text, "text_emb")
+    _check_pair_batch("frame_match_backward", a, t)
+    if t.dim() != 2:
+        raise RuntimeError(f"frame_match_backward: text_emb must be (B, D), got {tuple(t.shape)}")
     B, T, D = a.shape
     da, dt = torch.empty_like(a), torch.empty_like(t)
     call("tag_match_backward", ptr(a), ptr(t), ptr(sim), ptr(_chk(dsim, "grad")), ptr(da), ptr(dt), int(kind), int(l2norm),
@@ -930,6 +986,7 @@ def align_dot_backward(audio, text, out, dout, l2norm, scaled):
     """Gradient of align.DotProduct (models/align.py:14-31): d score from (out, dout), then two MFMA GEMMs against the
     (re-normalised when l2norm) operands and the backward of F.normalize."""
     a, t = _chk(audio, "audio"), _chk(text, "text")
+    _check_pair_batch("align_dot_backward", a, t)
     B, T, D = a.shape
     N = t.shape[1]
     an, tn = (_l2norm_rows(a, B * T, D), _l2norm_rows(t, B * N, D)) if l2norm else (a, t)

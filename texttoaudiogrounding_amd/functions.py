@@ -12,7 +12,8 @@ from . import settings as cfg
 from .lib import call, ptr, query
 from .engine import (F32, TagFunction, _chk, _deliver, _empty, _flush, _ready, _side_stream, _sinks, _ws, new_seed,
                      side_stream_enabled)
-from .dispatch import (BF16, BNStat, C1_BWD_FUSED_SHAPE, _sfx, _wino_u, act_bf16, bn_act_backward, bn_param_grad,
+from .dispatch import (BF16, BNStat, C1_BWD_FUSED_SHAPE, _sfx, _wino_u, act_bf16, augment_backward, augment_forward,
+                       bn_act_backward, bn_param_grad,
                        bn_stats, bnact_pool, bnrelu_pool_backward, check_pass_size, colsum, conv3x3,
                        conv3x3_bnrelu_pool_eval, conv3x3_c1, conv3x3_c1_backward, conv3x3_c1_dgrad, conv3x3_c1_stats,
                        conv3x3_c1_wgrad, conv3x3_dgrad_bnrelu_backward, conv3x3_dgrad_poolsums, conv3x3_stats,
@@ -97,7 +98,12 @@ class _SideWgrad:
 
 class Cnn8RnnFunction(TagFunction):
     """params order: bn0.w, bn0.b, 4 x (conv1.w, bn1.w, bn1.b, conv2.w, bn2.w, bn2.b), fc1.w, fc1.b,
-    rnn (w_ih, w_hh, b_ih, b_hh) x (fwd, reverse)."""
+    rnn (w_ih, w_hh, b_ih, b_hh) x (fwd, reverse).
+
+    ``ctx.augment`` (set by tag::cnn8rnn_encoder, absent otherwise): (stripes, n_time, lam) -- SpecAugment's stripe table and /
+    or mixup's lambda applied to the bn0 output (models/audio_encoder.py:192-200).  Then bn0 is applied by augment_forward into
+    x0 (B or B/2 clips) instead of inside the Cin = 1 convolution, and every later stage takes its batch from the tensor it reads;
+    bn0's statistics stay over all B clips."""
 
     @staticmethod
     def forward(ctx, waveform, mod, *params):
@@ -113,18 +119,24 @@ class Cnn8RnnFunction(TagFunction):
         drop = mod.dropout_p if training else (0.0, 0.0)
         seeds = [new_seed() for _ in range(5)] if training and (drop[0] > 0 or drop[1] > 0) else [0] * 5
         need_grad = any(ctx.needs_input_grad[2:])
+        aug = getattr(ctx, "augment", None)
 
         lm = logmel(wave, mod.n_fft, mod.win_length, mod.hop_length, mod.window, mod.mel_fb)   # (B,F,64)
         B, Fr, NM = lm.shape
         st0 = bn_stats(lm.view(B * Fr, NM), bn0_w, bn0_b, mod.bn0.running_mean, mod.bn0.running_var, bn_train,
                        mod.bn0.eps, mod.bn0.momentum)
+        x0 = augment_forward(lm, st0.scale, st0.shift, *aug) if aug is not None else None     # (B',F,64), bn0 applied
         x = None
         acts = []
         for i, (c1w, g1, b1, c2w, g2, b2) in enumerate(blocks):
             blk = getattr(mod, f"conv_block{i + 1}")
             if i == 0:
-                y1, part1 = conv3x3_c1_stats(lm, c1w, st0.scale, st0.shift, want_stats=bn_train,
-                                             out_dtype=BF16 if act_bf16() else F32)
+                if x0 is None:
+                    y1, part1 = conv3x3_c1_stats(lm, c1w, st0.scale, st0.shift, want_stats=bn_train,
+                                                 out_dtype=BF16 if act_bf16() else F32)
+                else:
+                    y1, part1 = conv3x3_c1_stats(x0, c1w, None, None, want_stats=bn_train,
+                                                 out_dtype=BF16 if act_bf16() else F32)
                 wf1 = wd1 = None
             else:
                 wf1, wd1 = pack_conv_weight(c1w, want_dgrad=need_grad, W=x.shape[2])
@@ -155,7 +167,7 @@ class Cnn8RnnFunction(TagFunction):
         fc = gemm(xm, fc_w, M, fc_w.shape[0], C, transB=True, bias=fc_b, act=1)
         y, gsave = gru_bidir_forward(fc, rnn, Bx, Tp, need_grad)
         if need_grad:
-            ctx.saved = dict(lm=lm, st0=st0, acts=acts, x_last=x, xm=xm, fc=fc, gsave=gsave, p=p, drop=drop,
+            ctx.saved = dict(lm=lm, st0=st0, aug=aug, x0=x0, acts=acts, x_last=x, xm=xm, fc=fc, gsave=gsave, p=p, drop=drop,
                              seeds=seeds, sinks=_sinks(params), params=params if cfg.DIRECT_GRADS else None)
         mod._last_dropout = dict(p=drop, seeds=seeds)
         return y
@@ -239,8 +251,15 @@ class Cnn8RnnFunction(TagFunction):
                     dx = conv3x3(dy1, wd1, x_in.shape[3])
                 sw.release()
             else:
-                dw0, dbn0 = conv3x3_c1_backward(lm, dy1, c1w, st0.scale, st0.shift, out=sk[2],   # dbn0: (B,F,64) grad wrt bn0 output
-                                                bn_bwd=None if applied else (y1, s1, g1, dg1, db1))
+                x0, aug = sv["x0"], sv["aug"]
+                if x0 is None:
+                    dw0, dbn0 = conv3x3_c1_backward(lm, dy1, c1w, st0.scale, st0.shift, out=sk[2],   # dbn0: (B,F,64) grad wrt bn0 output
+                                                    bn_bwd=None if applied else (y1, s1, g1, dg1, db1))
+                else:
+                    dw0, dx0 = conv3x3_c1_backward(x0, dy1, c1w, None, None, out=sk[2],
+                                                   bn_bwd=None if applied else (y1, s1, g1, dg1, db1))
+                    dbn0 = augment_backward(dx0, lm.shape[0], *aug)
+                    del dx0
                 _deliver(grads, sk, 2, dw0)
                 Bq, Fr, NM = lm.shape
                 dg0, db0 = bn_param_grad(lm.view(Bq * Fr, NM), dbn0.view(Bq * Fr, NM), st0, dg_out=sk[0], db_out=sk[1])
@@ -254,6 +273,25 @@ class Cnn8RnnFunction(TagFunction):
                 _flush()
         sw.join()
         return (None, None, *grads)
+
+
+class SpecAugmentFunction(TagFunction):
+    """models.augmentation.SpecAugmentation.forward on a (B, C, T, F) tensor: the stripes of clip b zero frames / mel bins of every
+    channel of that clip (torchlibrosa augmentation.py DropStripes); the gradient is the incoming one with the same zeros."""
+
+    @staticmethod
+    def forward(ctx, x, stripes, n_time):
+        x = _chk(x, "input")
+        B, C, T, Fq = x.shape
+        st = stripes.repeat_interleave(C, 0) if C > 1 else stripes          # one table row block per (clip, channel) image
+        ctx.stripes, ctx.n_time = st, n_time
+        return augment_forward(x.view(B * C, T, Fq), None, None, st, n_time).view(B, C, T, Fq)
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, C, T, Fq = dy.shape
+        dx = augment_backward(_chk(dy, "grad").view(B * C, T, Fq), B * C, ctx.stripes, ctx.n_time)
+        return dx.view(B, C, T, Fq), None, None
 
 
 # ------------------------------------------------------------------------------------------------

@@ -37,6 +37,8 @@ _SIGS = {
     "tag_bn_eval_affine": (c_int, [P, P, P, P, c_float, c_int, P, P, P]),
     "tag_affine_forward": (c_int, [P, c_long, c_int, P, P, P, P]),
     "tag_bn_param_grad": (c_int, [P, P, c_long, c_int, P, P, P, P, P, P]),
+    "tag_augment_forward": (c_int, [P, P, P, P, c_int, c_int, P, P, c_int, c_int, c_int, P]),
+    "tag_augment_backward": (c_int, [P, P, c_int, c_int, P, P, c_int, c_int, c_int, P]),
     "tag_pack_conv_weight": (c_int, [P, P, P, c_int, c_int, P]),
     "tag_conv3x3_stats_rows": (c_int, [c_int, c_int, c_int, c_int]),
     "tag_conv3x3_x3_stats_rows": (c_int, [c_int, c_int, c_int, c_int]),

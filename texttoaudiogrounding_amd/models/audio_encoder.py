@@ -15,6 +15,8 @@ import torch.nn as nn
 
 from .. import ops
 from .. import torch_ops  # noqa: F401  (registers torch.ops.tag.*)
+from ..utils.train_util import do_mixup
+from .augmentation import SpecAugmentation
 from .panns import ConvBlock, init_bn, init_layer
 
 
@@ -140,6 +142,7 @@ class Cnn8Rnn(nn.Module):
         self.melspec_extractor = _MelFrontendBuffers(
             torch.hann_window(self.win_length),
             slaney_mel_filterbank(self.n_fft // 2 + 1, 50.0, float(f_max), 64, sample_rate))
+        self.spec_augmenter = SpecAugmentation(time_drop_width=64, time_stripes_num=2, freq_drop_width=8, freq_stripes_num=2)
         self.bn0 = nn.BatchNorm2d(64)
         self.conv_block1 = ConvBlock(1, 64)
         self.conv_block2 = ConvBlock(64, 128)
@@ -196,18 +199,42 @@ class Cnn8Rnn(nn.Module):
                    getattr(self.rnn, f"bias_ih_l0{sfx}"), getattr(self.rnn, f"bias_hh_l0{sfx}")]
         return ps
 
+    def _augment_args(self, waveform, specaug, mixup_lambda):
+        """The trailing tag::cnn8rnn_encoder arguments of a train-mode call: () without augmentation, else (stripes, lambda)
+        on the device.  Everything is checked here, before any launch; the stripes are drawn BEFORE the operator draws its
+        dropout seeds, as the reference's SpecAugment runs before its dropout (models/audio_encoder.py:192-215)."""
+        self._last_specaug = None
+        if not self.training or (not specaug and mixup_lambda is None):
+            return ()
+        B = waveform.shape[0]
+        lam = None
+        if mixup_lambda is not None:
+            lam = torch.as_tensor(mixup_lambda, dtype=torch.float)
+            if B % 2 or lam.dim() != 1 or lam.numel() != B:
+                raise ValueError(f"Cnn8Rnn: mixup pairs clips (2k, 2k+1) and needs an even batch with one lambda per clip; "
+                                 f"got {B} clips and lambda of shape {tuple(lam.shape)}")
+        stripes = None
+        if specaug:
+            frames = waveform.shape[1] // self.hop_length + 1
+            stripes = self.spec_augmenter.draw(B, frames, self.bn0.num_features)
+            self._last_specaug = stripes
+            stripes = torch_ops.stage_to_device(stripes, waveform.device, torch.int32)
+        if lam is not None:
+            lam = torch_ops.stage_to_device(lam, waveform.device, torch.float32)
+        return stripes, lam
+
     def forward(self, input_dict: Dict):
         waveform = input_dict["waveform"]
-        if self.training and input_dict["specaug"]:
-            raise NotImplementedError("SpecAugment is off on the strongly-supervised path (run_strong.py:101-103)")
-        if self.training and input_dict.get("mixup_lambda", None) is not None:
-            raise NotImplementedError("mixup is not used on the strongly-supervised path")
+        mixup_lambda = input_dict.get("mixup_lambda", None)
+        augment = self._augment_args(waveform, input_dict["specaug"], mixup_lambda)
         if self.training and not self.freeze_bn:
             ops.bump_bn_counters(self, [self.bn0, *(getattr(self, f"conv_block{i}").bn1 for i in range(1, 5)),
                                         *(getattr(self, f"conv_block{i}").bn2 for i in range(1, 5))])
-        x = torch_ops.run_encoder(torch.ops.tag.cnn8rnn_encoder, self, waveform, self._flat_params())
+        x = torch_ops.run_encoder(torch.ops.tag.cnn8rnn_encoder, self, waveform, self._flat_params(), *augment)
         length = torch.div(torch.as_tensor(input_dict["waveform_len"]), self.hop_length, rounding_mode="floor") + 1
         length = torch.div(length, self.downsample_ratio, rounding_mode="floor")
+        if self.training and mixup_lambda is not None:
+            length = do_mixup(length, mixup_lambda)
         return {"embedding": x, "length": length}
 
 

@@ -382,16 +382,17 @@ def encoder_token(mod) -> int:
 
 
 class _EncCtx:
-    """What ops.Cnn8RnnFunction.forward / .backward expect of their ctx."""
+    """What ops.Cnn8RnnFunction.forward / .backward expect of their ctx (``augment``: see ops.Cnn8RnnFunction)."""
 
-    def __init__(self, needs):
+    def __init__(self, needs, augment=None):
         self.needs_input_grad = needs
         self.saved = None
+        self.augment = augment
 
 
-def _enc_forward(engine, waveform, params, module_token, need_grad):
+def _enc_forward(engine, waveform, params, module_token, need_grad, augment=None):
     mod = _ENC_MODULES[module_token]
-    ctx = _EncCtx((False, False) + tuple(bool(need_grad and p.requires_grad) for p in params))
+    ctx = _EncCtx((False, False) + tuple(bool(need_grad and p.requires_grad) for p in params), augment)
     y = engine.forward(ctx, waveform, mod, *params)
     _ENC_HANDOVER[0] = (engine, ctx) if need_grad else None
     return y
@@ -400,6 +401,12 @@ def _enc_forward(engine, waveform, params, module_token, need_grad):
 def _enc_setup(ctx, inputs, output):
     ctx.enc, _ENC_HANDOVER[0] = _ENC_HANDOVER[0], None
     ctx.enc_consumed = False
+    # backward returns one entry per argument of the CALL: the dispatcher drops trailing optional arguments left at their
+    # default (None), while ``inputs`` here has them filled in
+    n = len(inputs)
+    while n > 4 and inputs[n - 1] is None:
+        n -= 1
+    ctx.n_args = n
 
 
 def _enc_backward(ctx, dy):
@@ -414,7 +421,7 @@ def _enc_backward(ctx, dy):
     ctx.enc = None
     ctx.enc_consumed = True
     grads = engine.backward(ectx, dy.contiguous())            # (None, None, *parameter gradients)
-    return None, list(grads[2:]), None, None
+    return (None, list(grads[2:])) + (None,) * (ctx.n_args - 2)
 
 
 def _enc_fake_frames(mod, waveform):
@@ -422,18 +429,29 @@ def _enc_fake_frames(mod, waveform):
 
 
 @custom_op("tag::cnn8rnn_encoder", mutates_args=())
-def cnn8rnn_encoder(waveform: Tensor, params: List[Tensor], module_token: int, need_grad: bool) -> Tensor:
+def cnn8rnn_encoder(waveform: Tensor, params: List[Tensor], module_token: int, need_grad: bool,
+                    specaug_stripes: Optional[Tensor] = None, mixup_lambda: Optional[Tensor] = None) -> Tensor:
     """Cnn8Rnn.forward of models/audio_encoder.py:88-227: waveform (B,S) -> embedding (B, T', 512).  params in
     Cnn8Rnn._flat_params() order.  In train mode the BatchNorm running statistics of the MODULE named by the token are updated
     as nn.BatchNorm2d updates its buffers: module state, not operator arguments (torch.library refuses an autograd formula on an
-    operator that declares mutated arguments)."""
-    return _enc_forward(ops.Cnn8RnnFunction, waveform, params, module_token, need_grad)
+    operator that declares mutated arguments).
+
+    specaug_stripes: device int32 (B, n_time + n_freq, 2) [bgn, width] of SpecAugmentation.draw (the first n_time =
+    module.spec_augmenter.time_dropper.stripes_num rows along frames); mixup_lambda: device fp32 (B,), B even -> embedding of
+    B/2 clips (models/audio_encoder.py:192-200).  Both are applied as given: the module decides when (train mode)."""
+    augment = None
+    if specaug_stripes is not None or mixup_lambda is not None:
+        mod = _ENC_MODULES[module_token]
+        n_time = mod.spec_augmenter.time_dropper.stripes_num if specaug_stripes is not None else 0
+        augment = (specaug_stripes, n_time, mixup_lambda)
+    return _enc_forward(ops.Cnn8RnnFunction, waveform, params, module_token, need_grad, augment)
 
 
 @cnn8rnn_encoder.register_fake
-def _(waveform, params, module_token, need_grad):
+def _(waveform, params, module_token, need_grad, specaug_stripes=None, mixup_lambda=None):
     mod = _ENC_MODULES[module_token]
-    return waveform.new_empty(waveform.shape[0], _enc_fake_frames(mod, waveform), mod.embed_dim)
+    B = waveform.shape[0] // 2 if mixup_lambda is not None else waveform.shape[0]
+    return waveform.new_empty(B, _enc_fake_frames(mod, waveform), mod.embed_dim)
 
 
 register_autograd("tag::cnn8rnn_encoder", _enc_backward, setup_context=_enc_setup)
@@ -454,13 +472,25 @@ def _(waveform, params, module_token, need_grad):
 register_autograd("tag::crnn_encoder", _enc_backward, setup_context=_enc_setup)
 
 
-def run_encoder(op, mod, waveform, params):
+def stage_to_device(t, device, dtype):
+    """A small host table (stripes, mixup lambda) -> ``device`` through pinned memory, non-blocking (a pageable host->device
+    copy waits for the stream to drain: the host would stall mid-step, runner.py stages the lengths the same way)."""
+    t = torch.as_tensor(t).to(dtype)
+    if t.device == torch.device(device):
+        return t.contiguous()
+    if t.is_cuda:
+        return t.to(device).contiguous()
+    return t.contiguous().pin_memory().to(device, non_blocking=True)
+
+
+def run_encoder(op, mod, waveform, params, *augment):
     """Front door of the two encoder modules: calls ``op`` with the caller's grad mode made visible to the engine (inside an
-    operator grad mode is always off) and the module's token."""
+    operator grad mode is always off) and the module's token.  ``augment``: the trailing optional operator arguments
+    (tag::cnn8rnn_encoder: specaug_stripes, mixup_lambda)."""
     need = torch.is_grad_enabled() and any(p.requires_grad for p in params)
     prev, engine._RECORDING = engine._RECORDING, torch.is_grad_enabled()
     try:
-        return op(waveform, list(params), encoder_token(mod), need)
+        return op(waveform, list(params), encoder_token(mod), need, *augment)
     finally:
         engine._RECORDING = prev
         # setup_context has taken the saved state by now; if it was skipped (the dispatcher decided that no input needs a
