@@ -681,6 +681,45 @@ int tag_mean_w_forward_bf16(const void* x, long rows, int W, int C, float drop_p
 int tag_mean_w_backward_bf16(const float* dout, long rows, int W, int C, float drop_p, uint64_t seed, void* dx,
                              void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Early-fusion CrossCnn8_Rnn (models/audio_text_model.py:571-840): the text enters every conv layer as a per-(clip, channel)
+ * bias between BatchNorm and ReLU, relu(bn(y) + bias[b, c]), and again at fc1 and after the GRU.  fp32, channels-last.
+ * A reducing entry writes clip (B, 2, C) doubles, [b][sum a | sum b] of its two quantities over clip b, folded in a fixed order
+ * from fp64 partial rows that never straddle two clips; the channel totals are folded from those (no atomics).
+ * ws: tag_clip_reduce_ws_bytes(B, C) bytes.
+ *   tag_bias_bnrelu_forward       out = relu(y*scale + shift + bias[b]) over (B, HW, C)
+ *   tag_bias_bnrelu_pool_forward  tag_bnact_pool_forward (act 1; pool 0 avg+max | 2 avg | 3 max) with the bias
+ *   tag_bias_bnrelu_pool_backward its backward: clip = [sum dz | sum dz*xhat], dbeta / dgamma their totals, dy
+ *   tag_bias_bnrelu_backward      backward of tag_bias_bnrelu_forward; dt (B, C) or null = this site's clip sum dz + prev's
+ *                                 slot 0 (prev: the clip sums of the block's other site, or null)
+ *   tag_rowgroup_bias_relu        out = relu(x + bias[row / T]) over (B*T, N) (fc1 + fc1_text(e)); in place allowed
+ *   tag_rowgroup_colsum           dgroup (B, N) = column sums of each group of T rows, dtotal (N) = their total
+ *   tag_frame_head_forward        sig = sigmoid((y + rb[row / T]) . w + b0), prob = clamp(sig, 1e-7, 1) per row
+ *   tag_frame_head_backward       dlogit = dprob*(1-sig)*sig where 1e-7 <= sig <= 1, else 0; dy = dlogit*w,
+ *                                 dw = sum dlogit*(y + rb), dsum[n] = sum dlogit (= d b0), drb[b] = (sum_t dlogit)*w
+ */
+size_t tag_clip_reduce_ws_bytes(int B, int C);
+int tag_bias_bnrelu_forward(const float* y, const float* scale, const float* shift, const float* bias, float* out, int B,
+                            long HW, int C, void* stream);
+int tag_bias_bnrelu_pool_forward(const float* y, const float* scale, const float* shift, const float* bias, float* out,
+                                 int B, int H, int W, int C, int ph, int pw, int pool, float drop_p, uint64_t seed,
+                                 void* stream);
+int tag_bias_bnrelu_pool_backward(const float* y, const float* scale, const float* shift, const float* mean,
+                                  const float* invstd, const float* gamma, const float* bias, const float* dout, float* dy,
+                                  float* dgamma, float* dbeta, double* clip, int B, int H, int W, int C, int ph, int pw,
+                                  int pool, float drop_p, uint64_t seed, int bn_train, void* ws, void* stream);
+int tag_bias_bnrelu_backward(const float* y, const float* scale, const float* shift, const float* mean,
+                             const float* invstd, const float* gamma, const float* bias, const float* da, float* dy,
+                             float* dgamma, float* dbeta, double* clip, const double* prev, float* dt, int B, long HW,
+                             int C, int bn_train, void* ws, void* stream);
+int tag_rowgroup_bias_relu(const float* x, const float* bias, float* out, int B, int T, int N, void* stream);
+int tag_rowgroup_colsum(const float* x, int B, int T, int N, float* dgroup, float* dtotal, double* clip, void* ws,
+                        void* stream);
+int tag_frame_head_forward(const float* y, const float* rb, const float* w, const float* b0, float* sig, float* prob, int B,
+                           int T, int N, void* stream);
+int tag_frame_head_backward(const float* y, const float* rb, const float* w, const float* sig, const float* dprob, float* dy,
+                            float* dw, float* dsum, float* drb, double* clip, int B, int T, int N, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,8 +24,10 @@ __device__ __forceinline__ float leaky01(float v) { return v > 0.0f ? v : 0.1f *
 // generic two-quantity per-channel reduction over (rows, C), C % 4 == 0, (C/4) | 256
 // Functor: void operator()(long row, int c, float4& a, float4& b)   (c multiple of 4)
 // partials: [nblk][2][C] doubles
+// CLIP: one clip per blockIdx.y, ``rows`` = rows of ONE clip, partials [clip][nblk][2][C] (no partial row straddles two clips;
+// per-clip sums of the per-clip bias passes).  Fn::clip(b, c) loads the clip's per-channel constants.
 // ------------------------------------------------------------------------------------------
-template <class Fn>
+template <class Fn, bool CLIP = false>
 __global__ __launch_bounds__(256) void reduce2_kernel(Fn fn, long rows, int C, double* __restrict__ partials) {
     extern __shared__ double sred[];   // [256][8]
     const int tpr = C >> 2;                 // threads per row
@@ -34,9 +36,11 @@ __global__ __launch_bounds__(256) void reduce2_kernel(Fn fn, long rows, int C, d
     const int rsub = threadIdx.x / tpr;
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     fn.prep(c);                             // per-channel constants -> registers (a thread keeps its channel quad)
+    if constexpr (CLIP) fn.clip(blockIdx.y, c);
+    const long r0 = CLIP ? (long)blockIdx.y * rows : 0;
     for (long r = (long)blockIdx.x * rpi + rsub; r < rows; r += (long)gridDim.x * rpi) {
         float4 a, b;
-        fn(r, c, a, b);
+        fn(r0 + r, c, a, b);
         s1[0] += a.x; s1[1] += a.y; s1[2] += a.z; s1[3] += a.w;
         s2[0] += b.x; s2[1] += b.y; s2[2] += b.z; s2[3] += b.w;
     }
@@ -50,7 +54,8 @@ __global__ __launch_bounds__(256) void reduce2_kernel(Fn fn, long rows, int C, d
 #pragma unroll
             for (int j = 0; j < 4; ++j) { s1[j] += o[j]; s2[j] += o[4 + j]; }
         }
-        double* p = partials + (size_t)blockIdx.x * 2 * C;
+        const size_t blk = CLIP ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
+        double* p = partials + blk * 2 * C;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { p[c + j] = s1[j]; p[C + c + j] = s2[j]; }
     }
@@ -244,6 +249,23 @@ __global__ __launch_bounds__(FOLD_T) void bn_grad_finalize_kernel(const double* 
     dgamma[c] = (float)s2;
 }
 
+// per-clip sums of a clip-partitioned reduction (partials [B][nblk][2][C], blockIdx.y = clip): clip[b][2][C] = the fixed-order
+// fold of clip b's partial rows; bn_grad_finalize_kernel over clip[] (nblk = B) then gives the per-channel totals, so a
+// per-clip sum and its channel total come from ONE fold.  dt (B, C), optional: slot 0 + prev's slot 0 (prev: the clip sums of
+// the block's other bias site, or null), or with wcol: slot 1 * wcol[c] (the frame head's (sum_t dlogit) * w).
+__global__ __launch_bounds__(FOLD_T) void clip_fold_kernel(const double* __restrict__ partials, int nblk, int C,
+                                                           double* __restrict__ clip, const double* __restrict__ prev,
+                                                           const float* __restrict__ wcol, float* __restrict__ dt) {
+    const int b = blockIdx.y;
+    const int c = blockIdx.x * 16 + (threadIdx.x & 15), part = threadIdx.x >> 4;
+    double s1, s2;
+    fold_partials(partials + (size_t)b * nblk * 2 * C, nblk, C, c, part, s1, s2);
+    if (part != 0 || c >= C) return;
+    clip[(size_t)b * 2 * C + c] = s1;
+    clip[(size_t)b * 2 * C + C + c] = s2;
+    if (dt) dt[(size_t)b * C + c] = wcol ? (float)s2 * wcol[c] : (float)(prev ? s1 + prev[(size_t)b * 2 * C + c] : s1);
+}
+
 // dgamma / dbeta from the fp32 partial rows the dgrad conv epilogue writes (conv3x3_halo_kernel<.., EPI = 1>): row p =
 // [sum g | sum g*xhat] over one 64-pixel wave tile.  Stage 1: (16 channels) x (row chunk) blocks fold their rows in fp64;
 // stage 2: one block per 16 channels folds the chunks.  Fixed order throughout.
@@ -278,16 +300,25 @@ __global__ void bn_eval_affine_kernel(const float* gamma, const float* beta, con
     shift[c] = b - rm[c] * g * is;
 }
 
+// BIAS: y = relu(x*scale[c] + shift[c] + bias[clip, c]), one clip per blockIdx.y, n4 = float4s of ONE clip
+// (the CrossCnn8_Rnn conv block: ReLU(bn1(conv1(x)) + fc_text(e)), models/audio_text_model.py:621)
+template <bool BIAS = false>
 __global__ __launch_bounds__(256) void affine_kernel(const float* __restrict__ x, long n4, int C,
                                                      const float* __restrict__ scale,
-                                                     const float* __restrict__ shift, float* __restrict__ y) {
+                                                     const float* __restrict__ shift, float* __restrict__ y,
+                                                     const float* __restrict__ bias = nullptr) {
+    const long i0 = BIAS ? (long)blockIdx.y * n4 : 0;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const int c = (int)((i * 4) % C);
-        float4 v = reinterpret_cast<const float4*>(x)[i];
+        float4 v = reinterpret_cast<const float4*>(x)[i0 + i];
         const float4 s = *reinterpret_cast<const float4*>(scale + c);
         const float4 t = *reinterpret_cast<const float4*>(shift + c);
         v.x = fmaf(v.x, s.x, t.x); v.y = fmaf(v.y, s.y, t.y); v.z = fmaf(v.z, s.z, t.z); v.w = fmaf(v.w, s.w, t.w);
-        reinterpret_cast<float4*>(y)[i] = v;
+        if constexpr (BIAS) {
+            const float4 e = *reinterpret_cast<const float4*>(bias + (size_t)blockIdx.y * C + c);
+            v.x = fmaxf(v.x + e.x, 0.0f); v.y = fmaxf(v.y + e.y, 0.0f); v.z = fmaxf(v.z + e.z, 0.0f); v.w = fmaxf(v.w + e.w, 0.0f);
+        }
+        reinterpret_cast<float4*>(y)[i0 + i] = v;
     }
 }
 
@@ -342,12 +373,15 @@ struct SlotIx {
         return o;
     }
 };
-template <int PH, int PW, class TS = float, int NC = 4>
+// BIAS: relu(bn(y) + bias[clip, c]) (act 1; the CrossCnn8_Rnn conv block, models/audio_text_model.py:622): the same windows,
+// first-maximum rule and dropout counters as without it
+template <int PH, int PW, class TS = float, int NC = 4, bool BIAS = false>
 __global__ __launch_bounds__(256) void bnact_pool_fwd_kernel(const TS* __restrict__ y,
                                                              const float* __restrict__ scale,
                                                              const float* __restrict__ shift,
                                                              TS* __restrict__ out, int B, int H, int W, int C,
-                                                             int act, int pool, float drop_p, uint64_t seed) {
+                                                             int act, int pool, float drop_p, uint64_t seed,
+                                                             const float* __restrict__ bias) {
     typedef typename ActN<TS, NC>::raw_t raw_t;
     const int Ho = H / PH, Wo = W / PW, CN = C / NC, rpi = 256 / CN;
     const int c = (threadIdx.x % CN) * NC, rsub = threadIdx.x / CN;
@@ -365,11 +399,11 @@ __global__ __launch_bounds__(256) void bnact_pool_fwd_kernel(const TS* __restric
 #pragma unroll
             for (int dw = 0; dw < PW; ++dw) raw[dh][dw] = ActN<TS, NC>::ldraw(p + (size_t)(dh * W + dw) * C);
     };
-    auto finish = [&](long r, const raw_t (&raw)[PH][PW]) {
+    auto finish = [&](long r, const SlotIx& ix, const raw_t (&raw)[PH][PW]) {
         const size_t e0 = (size_t)(unsigned)r * C + c;   // flat index of the thread's first output element
-        float sum[NC], mx[NC];
+        float sum[NC], mx[NC], bb[NC];
 #pragma unroll
-        for (int j = 0; j < NC; ++j) { sum[j] = 0.0f; mx[j] = 0.0f; }
+        for (int j = 0; j < NC; ++j) { sum[j] = 0.0f; mx[j] = 0.0f; bb[j] = BIAS ? bias[(size_t)ix.b * C + c + j] : 0.0f; }
 #pragma unroll
         for (int dh = 0; dh < PH; ++dh)
 #pragma unroll
@@ -379,6 +413,7 @@ __global__ __launch_bounds__(256) void bnact_pool_fwd_kernel(const TS* __restric
 #pragma unroll
                 for (int j = 0; j < NC; ++j) {
                     float a = fmaf(v[j], s[j], t[j]);
+                    if constexpr (BIAS) a += bb[j];
                     a = (act == 1) ? fmaxf(a, 0.0f) : leaky01(a);
                     if (pool != 1) {
                         sum[j] += a;
@@ -417,13 +452,13 @@ __global__ __launch_bounds__(256) void bnact_pool_fwd_kernel(const TS* __restric
             const long r2 = r + stride, r3 = r2 + stride;
             ib = ia.plus(dstep, Ho, Wo);
             if (r2 < slots) load(ib, rb);
-            finish(r, ra);
+            finish(r, ia, ra);
             ia = ib.plus(dstep, Ho, Wo);
             if (r3 < slots) load(ia, ra);
-            if (r2 < slots) finish(r2, rb);
+            if (r2 < slots) finish(r2, ib, rb);
         }
     } else {
-        for (; r < slots; r += stride) { load(ia, ra); finish(r, ra); ia = ia.plus(dstep, Ho, Wo); }
+        for (; r < slots; r += stride) { load(ia, ra); finish(r, ia, ra); ia = ia.plus(dstep, Ho, Wo); }
     }
 }
 
@@ -432,12 +467,14 @@ __global__ __launch_bounds__(256) void bnact_pool_fwd_kernel(const TS* __restric
 // including the partial slots of the floor-dropped last row/column (dz = 0 there).
 // MODE 0: accumulate (sum dz, sum dz*xhat); MODE 1: write dy.
 // ------------------------------------------------------------------------------------------
-template <int PH, int PW, class TS = float, int NC = 4>
+// BIAS: the pool input is relu(bn(y) + bias[clip, c]); the reduction then runs clip by clip (pool_bwd_reduce_kernel)
+template <int PH, int PW, class TS = float, int NC = 4, bool BIAS = false>
 struct PoolBwdCtx {
     const TS* y; const float* scale; const float* shift; const float* mean; const float* invstd;
     const TS* dout; int B, H, W, C; float drop_p; uint64_t seed;
     float wavg, wmax;                      // pool_type: 'avg+max' (1/(PH*PW), 1) | 'avg' (1/(PH*PW), 0) | 'max' (0, 1)
     float sv[NC], tv[NC], mv[NC], iv[NC];  // per-channel constants of this thread's NC channels
+    const float* bias;                     // (B, C), BIAS only
     __device__ void prep(int c) {
 #pragma unroll
         for (int j = 0; j < NC; ++j) { sv[j] = scale[c + j]; tv[j] = shift[c + j]; mv[j] = mean[c + j]; iv[j] = invstd[c + j]; }
@@ -482,6 +519,7 @@ struct PoolBwdCtx {
 #pragma unroll
                 for (int j = 0; j < NC; ++j) {
                     a[dh][dw][j] = fmaf(vv[j], sv[j], tv[j]);
+                    if constexpr (BIAS) a[dh][dw][j] += bias[(size_t)b * C + c + j];
                     xh[dh][dw][j] = (vv[j] - mv[j]) * iv[j];
                     dz[dh][dw][j] = 0.0f;
                 }
@@ -526,18 +564,21 @@ struct PoolBwdCtx {
     }
 };
 
-template <int PH, int PW, class TS = float, int NC = 4>
-__global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(PoolBwdCtx<PH, PW, TS, NC> ctx, double* __restrict__ partials) {
+// BIAS: one clip per blockIdx.y, partials [clip][nblk][2][C] (a partial row never straddles two clips)
+template <int PH, int PW, class TS = float, int NC = 4, bool BIAS = false>
+__global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(PoolBwdCtx<PH, PW, TS, NC, BIAS> ctx,
+                                                              double* __restrict__ partials) {
     extern __shared__ double sred[];
     const int C = ctx.C, tpr = C / NC, rpi = 256 / tpr;
     const int c = (threadIdx.x % tpr) * NC, rsub = threadIdx.x / tpr;
     const int Ho = ctx.H / PH, Wo = ctx.W / PW;   // only full slots carry gradient
-    const long slots = (long)ctx.B * Ho * Wo;
+    const long slots = BIAS ? (long)Ho * Wo : (long)ctx.B * Ho * Wo;
+    const long base = BIAS ? (long)blockIdx.y * Ho * Wo : 0;
     double s1[NC], s2[NC];
 #pragma unroll
     for (int j = 0; j < NC; ++j) { s1[j] = 0.0; s2[j] = 0.0; }
     ctx.prep(c);
-    typedef typename PoolBwdCtx<PH, PW, TS, NC>::Raw Raw;
+    typedef typename PoolBwdCtx<PH, PW, TS, NC, BIAS>::Raw Raw;
     const long stride = (long)gridDim.x * rpi;
     auto load = [&](const SlotIx& ix, Raw& raw) { ctx.load(ix.b, ix.hs, ix.ws, c, raw); };
     auto finish = [&](const SlotIx& ix, const Raw& raw) {
@@ -560,7 +601,7 @@ __global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(PoolBwdCtx<PH, PW,
         Raw ra, rb;
         long r = (long)blockIdx.x * rpi + rsub;
         SlotIx ia, ib, ic, dstep;
-        ia.set(r < slots ? r : 0, Ho, Wo);
+        ia.set(base + (r < slots ? r : 0), Ho, Wo);
         dstep.set(stride, Ho, Wo);
         if constexpr (pool_pipelined<TS>()) {
             if (r < slots) load(ia, ra);
@@ -588,14 +629,15 @@ __global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(PoolBwdCtx<PH, PW,
 #pragma unroll
             for (int j = 0; j < NC; ++j) { s1[j] += o[j]; s2[j] += o[NC + j]; }
         }
-        double* p = partials + (size_t)blockIdx.x * 2 * C;
+        const size_t blk = BIAS ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
+        double* p = partials + blk * 2 * C;
 #pragma unroll
         for (int j = 0; j < NC; ++j) { p[c + j] = s1[j]; p[C + c + j] = s2[j]; }
     }
 }
 
-template <int PH, int PW, class TS = float, int NC = 4>
-__global__ __launch_bounds__(256) void pool_bwd_apply_kernel(PoolBwdCtx<PH, PW, TS, NC> ctx, const float* __restrict__ gamma,
+template <int PH, int PW, class TS = float, int NC = 4, bool BIAS = false>
+__global__ __launch_bounds__(256) void pool_bwd_apply_kernel(PoolBwdCtx<PH, PW, TS, NC, BIAS> ctx, const float* __restrict__ gamma,
                                                              const float* __restrict__ dgamma,
                                                              const float* __restrict__ dbeta, int bn_train,
                                                              TS* __restrict__ dy) {
@@ -612,7 +654,7 @@ __global__ __launch_bounds__(256) void pool_bwd_apply_kernel(PoolBwdCtx<PH, PW, 
         k1[j] = bn_train ? dbeta[c + j] * invN : 0.0f;
         k2[j] = bn_train ? dgamma[c + j] * invN : 0.0f;
     }
-    typedef typename PoolBwdCtx<PH, PW, TS, NC>::Raw Raw;
+    typedef typename PoolBwdCtx<PH, PW, TS, NC, BIAS>::Raw Raw;
     const long stride = (long)gridDim.x * rpi;
     auto load = [&](const SlotIx& ix, Raw& raw) { ctx.load(ix.b, ix.hs, ix.ws, c, raw); };
     auto finish = [&](const SlotIx& ix, const Raw& raw) {
@@ -664,15 +706,65 @@ struct BnReluBwdFnT {
 
 typedef BnReluBwdFnT<float> BnReluBwdFn;
 
-template <class TS>
-__global__ __launch_bounds__(256) void bnrelu_bwd_apply_kernel(BnReluBwdFnT<TS> fn, const float* __restrict__ gamma,
+// relu(bn(y) + bias[clip, c]) backward (the CrossCnn8_Rnn conv block's first site, models/audio_text_model.py:621), reduced
+// and applied clip by clip (reduce2_kernel / bnrelu_bwd_apply_kernel with CLIP): clip() loads the clip's bias quad
+struct BiasBnReluBwdFn : BnReluBwdFnT<float> {
+    const float* bias;
+    float4 e;
+    __device__ void clip(int b, int c) { e = *reinterpret_cast<const float4*>(bias + (size_t)b * C + c); }
+    __device__ void operator()(long r, int c, float4& a, float4& b) const {
+        const float4 v = *reinterpret_cast<const float4*>(y + (size_t)r * C + c);
+        const float4 g = *reinterpret_cast<const float4*>(da + (size_t)r * C + c);
+        a.x = fmaf(v.x, s.x, t.x) + e.x > 0.0f ? g.x : 0.0f;
+        a.y = fmaf(v.y, s.y, t.y) + e.y > 0.0f ? g.y : 0.0f;
+        a.z = fmaf(v.z, s.z, t.z) + e.z > 0.0f ? g.z : 0.0f;
+        a.w = fmaf(v.w, s.w, t.w) + e.w > 0.0f ? g.w : 0.0f;
+        b = make_float4(a.x * (v.x - m.x) * is.x, a.y * (v.y - m.y) * is.y, a.z * (v.z - m.z) * is.z,
+                        a.w * (v.w - m.w) * is.w);
+    }
+};
+
+// per-clip column sums of x (B*T, C) in both slots (d fc1_text(e) and d fc1.bias of CrossCnn8_Rnn)
+struct ColSumFn {
+    const float* x; int C;
+    __device__ void prep(int) {}
+    __device__ void clip(int, int) {}
+    __device__ void operator()(long r, int c, float4& a, float4& b) const {
+        a = *reinterpret_cast<const float4*>(x + (size_t)r * C + c);
+        b = a;
+    }
+};
+
+// backward of prob = clamp(sigmoid((y + rb[clip]) . w + b0), 1e-7, 1) (models/audio_text_model.py:816-818), row r of (B*T, C):
+// dlogit = dprob * s * (1 - s) where 1e-7 <= s <= 1 (torch's clamp gradient), else 0; writes dy = dlogit * w; slot 0 =
+// dlogit * (y + rb) (-> dw), slot 1 = dlogit in every channel (-> db0 and, times w, drb)
+struct FrameHeadBwdFn {
+    const float* y; const float* rb; const float* w; const float* sig; const float* dprob; float* dy; int C;
+    float4 wv, e;
+    __device__ void prep(int c) { wv = *reinterpret_cast<const float4*>(w + c); }
+    __device__ void clip(int b, int c) { e = *reinterpret_cast<const float4*>(rb + (size_t)b * C + c); }
+    __device__ void operator()(long r, int c, float4& a, float4& b) const {
+        const float s = sig[r];
+        const float dl = (s >= 1e-7f && s <= 1.0f) ? dprob[r] * (1.0f - s) * s : 0.0f;
+        const float4 v = *reinterpret_cast<const float4*>(y + (size_t)r * C + c);
+        *reinterpret_cast<float4*>(dy + (size_t)r * C + c) = make_float4(dl * wv.x, dl * wv.y, dl * wv.z, dl * wv.w);
+        a = make_float4(dl * (v.x + e.x), dl * (v.y + e.y), dl * (v.z + e.z), dl * (v.w + e.w));
+        b = make_float4(dl, dl, dl, dl);
+    }
+};
+
+template <class TS, class Fn = BnReluBwdFnT<TS>, bool CLIP = false>
+__global__ __launch_bounds__(256) void bnrelu_bwd_apply_kernel(Fn fn, const float* __restrict__ gamma,
                                                                const float* __restrict__ dgamma,
                                                                const float* __restrict__ dbeta, int bn_train,
                                                                long rows, TS* __restrict__ dy) {
     const int C = fn.C, tpr = C >> 2, rpi = 256 / tpr;
     const int c = (threadIdx.x % tpr) << 2, rsub = threadIdx.x / tpr;
-    const float invN = 1.0f / (float)rows;
+    // CLIP: rows of ONE clip, one clip per blockIdx.y; the BatchNorm count is that of all clips
+    const float invN = 1.0f / (float)(CLIP ? rows * gridDim.y : rows);
+    const long r0 = CLIP ? (long)blockIdx.y * rows : 0;
     fn.prep(c);
+    if constexpr (CLIP) fn.clip(blockIdx.y, c);
     float k0[4], k1[4], k2[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -683,13 +775,13 @@ __global__ __launch_bounds__(256) void bnrelu_bwd_apply_kernel(BnReluBwdFnT<TS> 
     const float mv[4] = {fn.m.x, fn.m.y, fn.m.z, fn.m.w}, iv[4] = {fn.is.x, fn.is.y, fn.is.z, fn.is.w};
     for (long r = (long)blockIdx.x * rpi + rsub; r < rows; r += (long)gridDim.x * rpi) {
         float4 dz, dzx;
-        fn(r, c, dz, dzx);
-        const f32x4 v = Act<TS>::ld4(fn.y + (size_t)r * C + c);
+        fn(r0 + r, c, dz, dzx);
+        const f32x4 v = Act<TS>::ld4(fn.y + (size_t)(r0 + r) * C + c);
         const float vv[4] = {v.x, v.y, v.z, v.w}, dzv[4] = {dz.x, dz.y, dz.z, dz.w};
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = k0[j] * (dzv[j] - k1[j] - (vv[j] - mv[j]) * iv[j] * k2[j]);
-        Act<TS>::st4(dy + (size_t)r * C + c, (f32x4){o[0], o[1], o[2], o[3]});
+        Act<TS>::st4(dy + (size_t)(r0 + r) * C + c, (f32x4){o[0], o[1], o[2], o[3]});
     }
 }
 
@@ -858,6 +950,11 @@ int apply_blocks(long rows, int C, int nc = 4) {
     if (nb > 8192) nb = 8192;
     return (int)(nb < 1 ? 1 : nb);
 }
+// blocks per clip of a clip-partitioned reduction: at most 2048 partial rows over all clips (and red_blocks' cap per clip)
+int clip_red_blocks(long rows_per_clip, int C, int B) {
+    const int nb = red_blocks(rows_per_clip, C), cap = B >= 2048 ? 1 : 2048 / B;
+    return nb < cap ? nb : cap;
+}
 bool vec_ok(int C) { return C % 4 == 0 && C >= 4 && (C >> 2) <= 256 && 256 % (C >> 2) == 0; }
 // channels per thread of the pool passes: 8 for bf16 tensors when the channel count allows (16-byte accesses), else 4
 template <class TS>
@@ -944,7 +1041,8 @@ extern "C" int tag_affine_forward(const float* x, long rows, int C, const float*
                                   void* stream) {
     TAG_CHECK_ARG(x && y && scale && shift && C % 4 == 0);
     const long n4 = rows * C / 4;
-    hipLaunchKernelGGL(affine_kernel, dim3(ew_blocks(n4)), dim3(256), 0, as_stream(stream), x, n4, C, scale, shift, y);
+    hipLaunchKernelGGL(affine_kernel<false>, dim3(ew_blocks(n4)), dim3(256), 0, as_stream(stream), x, n4, C, scale, shift, y,
+                       nullptr);
     TAG_LAUNCH_CHECK();
     return 0;
 }
@@ -981,14 +1079,14 @@ static int bnact_pool_forward_impl(const TS* y, const float* scale, const float*
     if constexpr (pool_nc8_type<TS>()) {                                                                            \
         if (nc8) {                                                                                                  \
             hipLaunchKernelGGL((bnact_pool_fwd_kernel<PH, PW, TS, 8>), dim3(nb), dim3(256), 0, as_stream(stream), y, scale, \
-                               shift, out, B, H, W, C, act, pool, drop_p, seed);                                    \
+                               shift, out, B, H, W, C, act, pool, drop_p, seed, nullptr);                                    \
         } else {                                                                                                    \
             hipLaunchKernelGGL((bnact_pool_fwd_kernel<PH, PW, TS, 4>), dim3(nb), dim3(256), 0, as_stream(stream), y, scale, \
-                               shift, out, B, H, W, C, act, pool, drop_p, seed);                                    \
+                               shift, out, B, H, W, C, act, pool, drop_p, seed, nullptr);                                    \
         }                                                                                                           \
     } else {                                                                                                        \
         hipLaunchKernelGGL((bnact_pool_fwd_kernel<PH, PW, TS, 4>), dim3(nb), dim3(256), 0, as_stream(stream), y, scale, shift, \
-                           out, B, H, W, C, act, pool, drop_p, seed);                                               \
+                           out, B, H, W, C, act, pool, drop_p, seed, nullptr);                                               \
     }
     DISPATCH_POOL(2, 2, POOL_FWD_BODY)
     DISPATCH_POOL(1, 2, POOL_FWD_BODY)
@@ -1275,4 +1373,148 @@ extern "C" int tag_lppool_leaky_backward(const float* y, const float* dout, floa
     TAG_CHECK_ARG(launched);
     TAG_LAUNCH_CHECK();
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-clip bias passes of the early-fusion CrossCnn8_Rnn (models/audio_text_model.py:571-840): the text enters every conv
+// layer as a per-(clip, channel) bias between BatchNorm and ReLU, relu(bn(y) + bias[b, c]), and again at fc1 / after the GRU.
+// Variants of the passes above (BIAS / CLIP template parameters); fp32 only.  A per-clip sum and its channel total come from
+// one fixed-order fold of fp64 partials whose rows never straddle two clips (clip_fold_kernel, then bn_grad_finalize_kernel
+// over the clips); no atomics.  clip: (B, 2, C) doubles [b][sum a | sum b], an output of every reducing entry.
+// ------------------------------------------------------------------------------------------
+extern "C" size_t tag_clip_reduce_ws_bytes(int B, int C) {
+    const long rows = B >= 2048 ? (long)B : 2048;
+    return (size_t)(rows < (long)B * RED_MAX_BLOCKS ? rows : (long)B * RED_MAX_BLOCKS) * 2 * (size_t)C * sizeof(double);
+}
+
+static int clip_fold_and_total(const double* partials, int nblk, int B, int C, double* clip, const double* prev,
+                               const float* wcol, float* dt, float* dsum1, float* dsum2, hipStream_t st) {
+    hipLaunchKernelGGL(clip_fold_kernel, dim3(cdiv(C, 16), B), dim3(FOLD_T), 0, st, partials, nblk, C, clip, prev, wcol, dt);
+    TAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, st, clip, B, C, dsum2, dsum1);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+// out = relu(y * scale[c] + shift[c] + bias[b, c]) over (B, HW, C)
+extern "C" int tag_bias_bnrelu_forward(const float* y, const float* scale, const float* shift, const float* bias, float* out,
+                                       int B, long HW, int C, void* stream) {
+    TAG_CHECK_ARG(y && scale && shift && bias && out && B > 0 && HW > 0 && vec_ok(C));
+    const long n4 = HW * C / 4;
+    hipLaunchKernelGGL(affine_kernel<true>, dim3(ew_blocks(n4 * B) / B + 1, B), dim3(256), 0, as_stream(stream), y, n4, C, scale,
+                       shift, out, bias);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+// dropout(pool(relu(bn(y) + bias[b, c]))): tag_bnact_pool_forward (act 1) with the per-clip bias
+extern "C" int tag_bias_bnrelu_pool_forward(const float* y, const float* scale, const float* shift, const float* bias,
+                                            float* out, int B, int H, int W, int C, int ph, int pw, int pool, float drop_p,
+                                            uint64_t seed, void* stream) {
+    TAG_CHECK_ARG(y && scale && shift && bias && out && (pool == 0 || pool == 2 || pool == 3));
+    TAG_CHECK_ARG(H / ph > 0 && W / pw > 0 && vec_ok(C));
+    TAG_CHECK_ARG((long)B * H * W < (1L << 31));
+    bool launched = false;
+    const int nb = apply_blocks((long)B * (H / ph) * (W / pw), C);
+#define BIAS_POOL_FWD hipLaunchKernelGGL((bnact_pool_fwd_kernel<PH, PW, float, 4, true>), dim3(nb), dim3(256), 0, \
+                                         as_stream(stream), y, scale, shift, out, B, H, W, C, 1, pool, drop_p, seed, bias)
+    DISPATCH_POOL(2, 2, BIAS_POOL_FWD)
+    DISPATCH_POOL(1, 2, BIAS_POOL_FWD)
+    DISPATCH_POOL(1, 1, BIAS_POOL_FWD)
+    DISPATCH_POOL(2, 1, BIAS_POOL_FWD)
+#undef BIAS_POOL_FWD
+    TAG_CHECK_ARG(launched);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+// backward of tag_bias_bnrelu_pool_forward: dz = d(bn(y) + bias) per position; clip[b] = [sum dz | sum dz*xhat] over clip b,
+// dbeta / dgamma their totals; dy = gamma*invstd*(dz - sum dz/N - xhat * sum dz*xhat/N) (train BN) or gamma*invstd*dz
+extern "C" int tag_bias_bnrelu_pool_backward(const float* y, const float* scale, const float* shift, const float* mean,
+                                             const float* invstd, const float* gamma, const float* bias, const float* dout,
+                                             float* dy, float* dgamma, float* dbeta, double* clip, int B, int H, int W, int C,
+                                             int ph, int pw, int pool, float drop_p, uint64_t seed, int bn_train, void* ws,
+                                             void* stream) {
+    TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && bias && dout && dy && dgamma && dbeta && clip && ws);
+    TAG_CHECK_ARG(pool == 0 || pool == 2 || pool == 3);
+    TAG_CHECK_ARG(vec_ok(C) && H / ph > 0 && W / pw > 0);
+    TAG_CHECK_ARG((long)B * H * W < (1L << 31));
+    const float wavg = pool == 3 ? 0.0f : 1.0f / (float)(ph * pw), wmax = pool == 2 ? 0.0f : 1.0f;
+    double* partials = static_cast<double*>(ws);
+    const int nblk = clip_red_blocks((long)(H / ph) * (W / pw), C, B);
+    const int nb = apply_blocks((long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw), C);
+    hipStream_t st = as_stream(stream);
+    bool launched = false;
+#define BIAS_POOL_BWD                                                                                                \
+    {                                                                                                                \
+        PoolBwdCtx<PH, PW, float, 4, true> ctx{y, scale, shift, mean, invstd, dout, B, H, W, C, drop_p, seed, wavg, wmax}; \
+        ctx.bias = bias;                                                                                             \
+        hipLaunchKernelGGL((pool_bwd_reduce_kernel<PH, PW, float, 4, true>), dim3(nblk, B), dim3(256),               \
+                           256 * 2 * 4 * sizeof(double), st, ctx, partials);                                         \
+        TAG_LAUNCH_CHECK();                                                                                          \
+        if (int e = clip_fold_and_total(partials, nblk, B, C, clip, nullptr, nullptr, nullptr, dbeta, dgamma, st)) return e; \
+        hipLaunchKernelGGL((pool_bwd_apply_kernel<PH, PW, float, 4, true>), dim3(nb), dim3(256), 0, st, ctx, gamma, dgamma, \
+                           dbeta, bn_train, dy);                                                                     \
+    }
+    DISPATCH_POOL(2, 2, BIAS_POOL_BWD)
+    DISPATCH_POOL(1, 2, BIAS_POOL_BWD)
+    DISPATCH_POOL(1, 1, BIAS_POOL_BWD)
+    DISPATCH_POOL(2, 1, BIAS_POOL_BWD)
+#undef BIAS_POOL_BWD
+    TAG_CHECK_ARG(launched);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+// backward of tag_bias_bnrelu_forward given da = d out: same sums and apply as tag_bnrelu_backward, clip by clip; dt (B, C),
+// optional: this site's per-clip sum dz plus prev's (the clip sums of the block's other site), from the same fold
+extern "C" int tag_bias_bnrelu_backward(const float* y, const float* scale, const float* shift, const float* mean,
+                                        const float* invstd, const float* gamma, const float* bias, const float* da, float* dy,
+                                        float* dgamma, float* dbeta, double* clip, const double* prev, float* dt, int B,
+                                        long HW, int C, int bn_train, void* ws, void* stream) {
+    TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && bias && da && dy && dgamma && dbeta && clip && ws);
+    TAG_CHECK_ARG(vec_ok(C) && B > 0 && HW > 0 && (long)B * HW < (1L << 31));
+    double* partials = static_cast<double*>(ws);
+    hipStream_t st = as_stream(stream);
+    const int nblk = clip_red_blocks(HW, C, B);
+    BiasBnReluBwdFn fn{{y, scale, shift, mean, invstd, da, C}, bias};
+    hipLaunchKernelGGL((reduce2_kernel<BiasBnReluBwdFn, true>), dim3(nblk, B), dim3(256), 256 * 8 * sizeof(double), st, fn, HW,
+                       C, partials);
+    TAG_LAUNCH_CHECK();
+    if (int e = clip_fold_and_total(partials, nblk, B, C, clip, prev, nullptr, dt, dbeta, dgamma, st)) return e;
+    const int nb = apply_blocks((long)B * HW, C) / B + 1;
+    hipLaunchKernelGGL((bnrelu_bwd_apply_kernel<float, BiasBnReluBwdFn, true>), dim3(nb, B), dim3(256), 0, st, fn, gamma,
+                       dgamma, dbeta, bn_train, HW, dy);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+// per-group column sums of x (B*T, N): dgroup (B, N) = sum over the T rows of each group, dtotal (N) = their sum over groups
+extern "C" int tag_rowgroup_colsum(const float* x, int B, int T, int N, float* dgroup, float* dtotal, double* clip, void* ws,
+                                   void* stream) {
+    TAG_CHECK_ARG(x && dgroup && dtotal && clip && ws && B > 0 && T > 0 && vec_ok(N));
+    double* partials = static_cast<double*>(ws);
+    hipStream_t st = as_stream(stream);
+    const int nblk = clip_red_blocks(T, N, B);
+    hipLaunchKernelGGL((reduce2_kernel<ColSumFn, true>), dim3(nblk, B), dim3(256), 256 * 8 * sizeof(double), st, ColSumFn{x, N},
+                       (long)T, N, partials);
+    TAG_LAUNCH_CHECK();
+    // both slots hold the same sums: their totals land in dtotal twice, with the same value
+    return clip_fold_and_total(partials, nblk, B, N, clip, nullptr, nullptr, dgroup, dtotal, dtotal, st);
+}
+
+// backward of the frame head prob = clamp(sigmoid((y + rb[b]) . w + b0), 1e-7, 1) over (B*T, N) rows (FrameHeadBwdFn):
+// dy (B*T, N); dw (N); dsum (N): every entry = d b0; drb (B, N) = (sum_t dlogit) * w
+extern "C" int tag_frame_head_backward(const float* y, const float* rb, const float* w, const float* sig, const float* dprob,
+                                       float* dy, float* dw, float* dsum, float* drb, double* clip, int B, int T, int N,
+                                       void* ws, void* stream) {
+    TAG_CHECK_ARG(y && rb && w && sig && dprob && dy && dw && dsum && drb && clip && ws && B > 0 && T > 0 && vec_ok(N));
+    double* partials = static_cast<double*>(ws);
+    hipStream_t st = as_stream(stream);
+    const int nblk = clip_red_blocks(T, N, B);
+    FrameHeadBwdFn fn{y, rb, w, sig, dprob, dy, N};
+    hipLaunchKernelGGL((reduce2_kernel<FrameHeadBwdFn, true>), dim3(nblk, B), dim3(256), 256 * 8 * sizeof(double), st, fn,
+                       (long)T, N, partials);
+    TAG_LAUNCH_CHECK();
+    return clip_fold_and_total(partials, nblk, B, N, clip, nullptr, w, drb, dw, dsum, st);
 }

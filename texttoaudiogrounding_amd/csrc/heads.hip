@@ -791,6 +791,47 @@ __global__ __launch_bounds__(256) void group_expand_bwd_kernel(const float* __re
         dx[i] = s;
     }
 }
+// ---------------------------------------------------------------- CrossCnn8_Rnn heads (models/audio_text_model.py:809-818)
+// out = relu(x + bias[group, n]) over (B*T, N), a group = T consecutive rows (one clip), one group per blockIdx.y
+__global__ __launch_bounds__(256) void rowgroup_bias_relu_kernel(const float* __restrict__ x, const float* __restrict__ bias,
+                                                                 float* __restrict__ out, long n4, int N) {
+    const long i0 = (long)blockIdx.y * n4;
+    const float* e = bias + (size_t)blockIdx.y * N;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const int c = (int)((i * 4) % N);
+        float4 v = reinterpret_cast<const float4*>(x)[i0 + i];
+        const float4 b = *reinterpret_cast<const float4*>(e + c);
+        v.x = fmaxf(v.x + b.x, 0.0f); v.y = fmaxf(v.y + b.y, 0.0f); v.z = fmaxf(v.z + b.z, 0.0f); v.w = fmaxf(v.w + b.w, 0.0f);
+        reinterpret_cast<float4*>(out)[i0 + i] = v;
+    }
+}
+
+// prob = clamp(sigmoid((y + rb[clip]) . w + b0), 1e-7, 1) per row of (B*T, N), y + rb formed first as the reference does; one
+// wave per row.  sig: the unclamped sigmoid (its clamp mask is the backward's)
+__global__ __launch_bounds__(256) void frame_head_fwd_kernel(const float* __restrict__ y, const float* __restrict__ rb,
+                                                             const float* __restrict__ w, const float* __restrict__ b0,
+                                                             float* __restrict__ sig, float* __restrict__ prob, long rows,
+                                                             int T, int N) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= rows) return;
+    const float* yr = y + (size_t)r * N;
+    const float* e = rb + (size_t)((unsigned)r / (unsigned)T) * N;
+    float s = 0.0f;
+    for (int k = lane * 4; k < N; k += 256) {
+        const float4 v = *reinterpret_cast<const float4*>(yr + k);
+        const float4 b = *reinterpret_cast<const float4*>(e + k);
+        const float4 u = *reinterpret_cast<const float4*>(w + k);
+        s = fmaf(v.x + b.x, u.x, s); s = fmaf(v.y + b.y, u.y, s); s = fmaf(v.z + b.z, u.z, s); s = fmaf(v.w + b.w, u.w, s);
+    }
+    s = wave_sum(s);
+    if (lane == 0) {
+        const float g = 1.0f / (1.0f + expf(-(s + b0[0])));
+        sig[r] = g;
+        prob[r] = fminf(fmaxf(g, 1e-7f), 1.0f);
+    }
+}
+
 }  // namespace
 
 extern "C" int tag_embed_mean_forward(const int64_t* text, const int64_t* text_len, const float* table,
@@ -1050,6 +1091,26 @@ extern "C" int tag_maxmargin_backward(const float* x, int n, float margin, float
     TAG_CHECK_ARG(x && dloss && dx && n > 1);
     hipLaunchKernelGGL(maxmargin_bwd_kernel, dim3(cdiv(n, 4)), dim3(256), 0, as_stream(stream), x, n, margin, lamda1, fix_norm,
                        dloss, dx);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tag_rowgroup_bias_relu(const float* x, const float* bias, float* out, int B, int T, int N, void* stream) {
+    TAG_CHECK_ARG(x && bias && out && B > 0 && T > 0 && N % 4 == 0 && N > 0);
+    const long n4 = (long)T * N / 4;
+    long nb = (n4 + 255) / 256;
+    nb = nb > 64 ? 64 : nb;
+    hipLaunchKernelGGL(rowgroup_bias_relu_kernel, dim3((int)nb, B), dim3(256), 0, as_stream(stream), x, bias, out, n4, N);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tag_frame_head_forward(const float* y, const float* rb, const float* w, const float* b0, float* sig, float* prob,
+                                      int B, int T, int N, void* stream) {
+    TAG_CHECK_ARG(y && rb && w && b0 && sig && prob && B > 0 && T > 0 && N % 4 == 0 && N > 0 && (long)B * T < (1L << 31));
+    const long rows = (long)B * T;
+    hipLaunchKernelGGL(frame_head_fwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, as_stream(stream), y, rb, w, b0, sig, prob, rows,
+                       T, N);
     TAG_LAUNCH_CHECK();
     return 0;
 }

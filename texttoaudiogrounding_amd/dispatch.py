@@ -1003,6 +1003,102 @@ def align_dot_backward(audio, text, out, dout, l2norm, scaled):
 
 
 # ------------------------------------------------------------------------------------------------
+# per-clip bias passes and heads of the early-fusion CrossCnn8_Rnn (models/audio_text_model.py:571-840), fp32
+# ------------------------------------------------------------------------------------------------
+
+def _clip_ws(B, C, like):
+    return _ws(query("tag_clip_reduce_ws_bytes", B, C), like), torch.empty(B, 2, C, device=like.device, dtype=torch.float64)
+
+
+def bias_bnrelu_forward(y, st: BNStat, bias):
+    """relu(bn(y) + bias[b, c]) of a channels-last y (B,H,W,C); bias (B, C)."""
+    B, H, W, C = y.shape
+    out = torch.empty_like(y)
+    call("tag_bias_bnrelu_forward", ptr(y), ptr(st.scale), ptr(st.shift), ptr(bias), ptr(out), B, H * W, C)
+    return out
+
+
+def bias_bnrelu_pool(y, st: BNStat, bias, ph, pw, pool=0, drop_p=0.0, seed=0):
+    """dropout(pool(relu(bn(y) + bias[b, c]))): bnact_pool (act 1) with the per-clip bias."""
+    B, H, W, C = y.shape
+    out = _empty(B, H // ph, W // pw, C, like=y)
+    call("tag_bias_bnrelu_pool_forward", ptr(y), ptr(st.scale), ptr(st.shift), ptr(bias), ptr(out), B, H, W, C, ph, pw,
+         int(pool), float(drop_p), seed)
+    return out
+
+
+def bias_bnrelu_pool_backward(y, st: BNStat, gamma, bias, dout, ph, pw, pool=0, drop_p=0.0, seed=0, dg_out=None, db_out=None):
+    """-> (dy, dgamma, dbeta, clip): clip (B, 2, C) fp64 = [sum dz | sum dz*xhat] of each clip (dz: gradient at bn(y) + bias)."""
+    B, H, W, C = y.shape
+    dy = torch.empty_like(y)
+    dg = dg_out if dg_out is not None else _empty(C, like=y)
+    db = db_out if db_out is not None else _empty(C, like=y)
+    ws, clip = _clip_ws(B, C, y)
+    call("tag_bias_bnrelu_pool_backward", ptr(y), ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(st.invstd), ptr(gamma),
+         ptr(bias), ptr(dout), ptr(dy), ptr(dg), ptr(db), ptr(clip), B, H, W, C, ph, pw, int(pool), float(drop_p), seed,
+         int(st.train), ptr(ws))
+    return dy, dg, db, clip
+
+
+def bias_bnrelu_backward(y, st: BNStat, gamma, bias, da, prev=None, want_dt=True, dg_out=None, db_out=None):
+    """Backward of bias_bnrelu_forward given da.  -> (dy, dgamma, dbeta, dt): dt (B, C) = this site's per-clip sum of dz plus
+    prev's (the clip sums bias_bnrelu_pool_backward returned for the block's other site), or None."""
+    B, H, W, C = y.shape
+    dy = torch.empty_like(y)
+    dg = dg_out if dg_out is not None else _empty(C, like=y)
+    db = db_out if db_out is not None else _empty(C, like=y)
+    dt = _empty(B, C, like=y) if want_dt else None
+    ws, clip = _clip_ws(B, C, y)
+    call("tag_bias_bnrelu_backward", ptr(y), ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(st.invstd), ptr(gamma), ptr(bias),
+         ptr(da), ptr(dy), ptr(dg), ptr(db), ptr(clip), ptr(prev), ptr(dt), B, H * W, C, int(st.train), ptr(ws))
+    return dy, dg, db, dt
+
+
+def rowgroup_bias_relu(x, bias, T, out=None):
+    """relu(x + bias[row // T]) over x (B*T, N); bias (B, N).  out may be x."""
+    M, N = x.shape
+    out = out if out is not None else torch.empty_like(x)
+    call("tag_rowgroup_bias_relu", ptr(x), ptr(bias), ptr(out), M // T, T, N)
+    return out
+
+
+def rowgroup_colsum(x, T, dtotal=None):
+    """x (B*T, N) -> (per-group column sums (B, N), their total (N))."""
+    M, N = x.shape
+    B = M // T
+    dgroup = _empty(B, N, like=x)
+    dtotal = dtotal if dtotal is not None else _empty(N, like=x)
+    ws, clip = _clip_ws(B, N, x)
+    call("tag_rowgroup_colsum", ptr(x), B, T, N, ptr(dgroup), ptr(dtotal), ptr(clip), ptr(ws))
+    return dgroup, dtotal
+
+
+def frame_head_forward(y, rb, w, b0, T):
+    """prob = clamp(sigmoid((y + rb[row // T]) . w + b0), 1e-7, 1) of y (B*T, N) -> (prob (B*T,), sig (B*T,))."""
+    M, N = y.shape
+    sig, prob = _empty(M, like=y), _empty(M, like=y)
+    call("tag_frame_head_forward", ptr(y), ptr(rb), ptr(w), ptr(b0), ptr(sig), ptr(prob), M // T, T, N)
+    return prob, sig
+
+
+def frame_head_backward(y, rb, w, sig, dprob, T, dw_out=None, db_out=None):
+    """-> (dy (B*T, N), dw (N), db0 (1), drb (B, N))."""
+    M, N = y.shape
+    B = M // T
+    dy, drb = torch.empty_like(y), _empty(B, N, like=y)
+    dw = dw_out if dw_out is not None else _empty(N, like=y)
+    dsum = _empty(N, like=y)
+    ws, clip = _clip_ws(B, N, y)
+    call("tag_frame_head_backward", ptr(y), ptr(rb), ptr(w), ptr(sig), ptr(dprob), ptr(dy), ptr(dw), ptr(dsum), ptr(drb),
+         ptr(clip), B, T, N, ptr(ws))
+    db0 = dsum[:1]
+    if db_out is not None:
+        db_out.copy_(db0)
+        db0 = db_out
+    return dy, dw, db0, drb
+
+
+# ------------------------------------------------------------------------------------------------
 # optimiser step on flat buffers (O1)
 # ------------------------------------------------------------------------------------------------
 

@@ -20,6 +20,8 @@ from .dispatch import (BF16, BNStat, C1_BWD_FUSED_SHAPE, _sfx, _wino_u, act_bf16
                        conv3x3_wgrad, embed_mean_backward_into, embed_mean_forward, eval_pool_fusable, gemm,
                        gru_bidir_backward, gru_bidir_forward, logmel, lppool_leaky_backward, pack_conv_weight,
                        pool_sums_fusable, relu_backward)
+from .dispatch import (bias_bnrelu_backward, bias_bnrelu_forward, bias_bnrelu_pool, bias_bnrelu_pool_backward,
+                       frame_head_backward, frame_head_forward, gemm_bf16, rowgroup_bias_relu, rowgroup_colsum)
 
 # ------------------------------------------------------------------------------------------------
 # Cnn8Rnn: the whole audio encoder as one autograd node (rows F1-F3, A1-A4 forward + backward)
@@ -273,6 +275,240 @@ class Cnn8RnnFunction(TagFunction):
                 _flush()
         sw.join()
         return (None, None, *grads)
+
+
+def check_cross_precision():
+    """CrossCnn8_Rnn runs in fp32 only: its per-clip bias passes have no bf16 or split-fp32 (x3) form."""
+    if cfg.CONV_MATH != "fp32" or act_bf16() or gemm_bf16():
+        raise RuntimeError(f"CrossCnn8_Rnn supports fp32 arithmetic only (CONV_MATH 'fp32', fp32 activations and GEMMs); got "
+                           f"CONV_MATH {cfg.CONV_MATH!r}, ACT_DTYPE {cfg.ACT_DTYPE!r}, GEMM_MATH {cfg.GEMM_MATH!r}")
+
+
+class CrossCnn8RnnFunction(TagFunction):
+    """The early-fusion CrossCnn8_Rnn (models/audio_text_model.py:677-840) below its text encoder, as one autograd node:
+    waveform (B,S) -> frame_sim (B, T', 1).  t1..t4 = conv_block{i}.fc_text(e) (B, C_i), u = fc1_text(e), r = rnn_text(e)
+    (B, 512): differentiable inputs, so autograd sums their six gradients into the text embedding.
+
+    params order: bn0.w, bn0.b, 4 x (conv1.w, bn1.w, bn1.b, conv2.w, bn2.w, bn2.b), fc1.w, fc1.b, rnn (w_ih, w_hh, b_ih, b_hh)
+    x (fwd, reverse), fc_output.w, fc_output.b.  The conv / BatchNorm-statistics / GRU / GEMM launches are Cnn8RnnFunction's;
+    the text bias enters through the per-clip bias passes (dispatch.bias_*), so the conv kernels' fused BatchNorm epilogues
+    (which assume a per-channel shift) are not used.  ``ctx.augment``: (stripes, n_time, None) as in Cnn8RnnFunction."""
+
+    @staticmethod
+    def forward(ctx, waveform, mod, t1, t2, t3, t4, u, r, *params):
+        check_cross_precision()
+        wave = _chk(waveform, "waveform")
+        check_pass_size(wave.shape[0], wave.shape[1] // mod.hop_length + 1)
+        training = mod.training
+        bn_train = training and not mod.freeze_bn
+        p = [_chk(t.detach(), "parameter") for t in params]
+        texts = [_chk(t.detach(), "text bias") for t in (t1, t2, t3, t4)]
+        u_, r_ = _chk(u.detach(), "fc1_text"), _chk(r.detach(), "rnn_text")
+        bn0_w, bn0_b = p[0], p[1]
+        blocks = [p[2 + 6 * i: 8 + 6 * i] for i in range(4)]
+        fc_w, fc_b = p[26], p[27]
+        rnn = p[28:36]
+        wo, bo = p[36], p[37]
+        drop = mod.dropout_p if training else (0.0, 0.0)
+        seeds = [new_seed() for _ in range(5)] if training and (drop[0] > 0 or drop[1] > 0) else [0] * 5
+        need_grad = any(ctx.needs_input_grad[2:])
+        aug = getattr(ctx, "augment", None)
+
+        lm = logmel(wave, mod.n_fft, mod.win_length, mod.hop_length, mod.window, mod.mel_fb)   # (B,F,64)
+        B, Fr, NM = lm.shape
+        for i, t in enumerate(texts + [u_, r_]):
+            if t.dim() != 2 or t.shape[0] != B:
+                raise RuntimeError(f"CrossCnn8_Rnn: text bias {i} has shape {tuple(t.shape)}, expected ({B}, channels)")
+        st0 = bn_stats(lm.view(B * Fr, NM), bn0_w, bn0_b, mod.bn0.running_mean, mod.bn0.running_var, bn_train,
+                       mod.bn0.eps, mod.bn0.momentum)
+        x0 = augment_forward(lm, st0.scale, st0.shift, *aug) if aug is not None else None     # (B,F,64), bn0 applied
+        x = None
+        acts = []
+        for i, (c1w, g1, b1, c2w, g2, b2) in enumerate(blocks):
+            blk = getattr(mod, f"conv_block{i + 1}")
+            t = texts[i]
+            if i == 0:
+                if x0 is None:
+                    y1, part1 = conv3x3_c1_stats(lm, c1w, st0.scale, st0.shift, want_stats=bn_train)
+                else:
+                    y1, part1 = conv3x3_c1_stats(x0, c1w, None, None, want_stats=bn_train)
+                wd1 = None
+            else:
+                wf1, wd1 = pack_conv_weight(c1w, want_dgrad=need_grad, W=x.shape[2])
+                y1, part1 = conv3x3_stats(x, wf1, c1w.shape[0], want_stats=bn_train)
+            C = y1.shape[3]
+            if t.shape[1] != C:
+                raise RuntimeError(f"CrossCnn8_Rnn: conv_block{i + 1} text bias has {t.shape[1]} channels, expected {C}")
+            s1 = bn_stats(y1.view(-1, C), g1, b1, blk.bn1.running_mean, blk.bn1.running_var, bn_train, blk.bn1.eps,
+                          blk.bn1.momentum, partials=part1)
+            a1 = bias_bnrelu_forward(y1, s1, t)                          # relu(bn1(conv1(x)) + t), written out
+            wf2, wd2 = pack_conv_weight(c2w, want_dgrad=need_grad, W=a1.shape[2])
+            y2, part2 = conv3x3_stats(a1, wf2, C, want_stats=bn_train)
+            s2 = bn_stats(y2.view(-1, C), g2, b2, blk.bn2.running_mean, blk.bn2.running_var, bn_train, blk.bn2.eps,
+                          blk.bn2.momentum, partials=part2)
+            ph, pw = CNN8_POOLS[i]
+            xo = bias_bnrelu_pool(y2, s2, t, ph, pw, pool=0, drop_p=drop[0], seed=seeds[i])
+            if need_grad:
+                acts.append((x, y1, s1, a1, y2, s2, wd1, wd2))
+            del a1
+            x = xo
+        Bx, Tp, Wp, C = x.shape
+        xm = _empty(Bx * Tp, C, like=x)
+        call("tag_mean_w_forward", ptr(x), Bx * Tp, Wp, C, float(drop[1]), seeds[4], ptr(xm))
+        M = Bx * Tp
+        fc = gemm(xm, fc_w, M, fc_w.shape[0], C, transB=True, bias=fc_b)
+        h = rowgroup_bias_relu(fc, u_, Tp, out=fc)                       # relu(fc1(x) + fc1_text(e)), in place
+        y, gsave = gru_bidir_forward(h, rnn, Bx, Tp, need_grad)
+        y2d = y.reshape(M, -1)
+        prob, sig = frame_head_forward(y2d, r_, wo.reshape(-1), bo, Tp)
+        if need_grad:
+            ctx.saved = dict(lm=lm, st0=st0, aug=aug, x0=x0, acts=acts, x_last=x, xm=xm, h=h, gsave=gsave, y=y2d, sig=sig,
+                             texts=texts, u=u_, r=r_, p=p, drop=drop, seeds=seeds, sinks=_sinks(params),
+                             params=params if cfg.DIRECT_GRADS else None)
+        mod._last_dropout = dict(p=drop, seeds=seeds)
+        return prob.view(Bx, Tp, 1)
+
+    @staticmethod
+    def backward(ctx, dprob):
+        sv = ctx.saved
+        ctx.saved = None
+        p = sv["p"]
+        drop, seeds = sv["drop"], sv["seeds"]
+        dprob = _chk(dprob, "grad_output")
+        grads: List[Optional[torch.Tensor]] = [None] * len(p)
+        sk, prm = sv["sinks"], sv["params"]
+        y, h = sv["y"], sv["h"]
+        M = y.shape[0]
+        Tp = sv["x_last"].shape[1]
+        wo = p[36]
+        dyh, dwo, dbo, dr = frame_head_backward(y, sv["r"], wo.reshape(-1), sv["sig"], dprob.reshape(-1), Tp)
+        _deliver(grads, sk, 36, dwo.view_as(wo))
+        _deliver(grads, sk, 37, dbo)
+        sw = _SideWgrad(dprob.device)
+        dh, ggru = gru_bidir_backward(dyh.view(M // Tp, Tp, -1), h, sv["gsave"], outs=sk[28:36],
+                                      side=sw if cfg.SIDE_PARAM_GRADS >= 1 else None)
+        for k in range(8):
+            _deliver(grads, sk, 28 + k, ggru[k])
+        dfc = relu_backward(h, dh)
+        du, dfc_b = rowgroup_colsum(dfc, Tp, dtotal=sk[27])
+        _deliver(grads, sk, 27, dfc_b)
+        xm = sv["xm"]
+        fc_w = p[26]
+        _deliver(grads, sk, 26, gemm(dfc, xm, fc_w.shape[0], fc_w.shape[1], M, transA=True, lda=fc_w.shape[0], out=sk[26]))
+        if prm is not None:
+            _ready(list(prm[26:38]))
+            _flush()
+        dtexts = [None] * 4
+        du = du if ctx.needs_input_grad[6] else None
+        dr = dr if ctx.needs_input_grad[7] else None
+        if not any(ctx.needs_input_grad[2:6]) and not any(ctx.needs_input_grad[8:34]):
+            # freeze_cnn (models/audio_text_model.py:703-707): nothing below the GRU takes a gradient, the text encoder
+            # included -- the conv stack's backward is not run
+            sw.join()
+            return (None, None, *dtexts, du, dr, *grads)
+        dxm = gemm(dfc, fc_w, M, fc_w.shape[1], fc_w.shape[0])
+        x_last = sv["x_last"]
+        Bx, Tp, Wp, C = x_last.shape
+        dx = torch.empty_like(x_last)
+        call("tag_mean_w_backward", ptr(dxm), Bx * Tp, Wp, C, float(drop[1]), seeds[4], ptr(dx))
+        lm, st0 = sv["lm"], sv["st0"]
+        texts = sv["texts"]
+        for i in range(3, -1, -1):
+            x_in, y1, s1, a1, y2, s2, wd1, wd2 = sv["acts"][i]
+            c1w, g1, b1, c2w, g2, b2 = p[2 + 6 * i: 8 + 6 * i]
+            o = 2 + 6 * i
+            ph, pw = CNN8_POOLS[i]
+            t = texts[i]
+            dy2, dg2, db2, clip2 = bias_bnrelu_pool_backward(y2, s2, g2, t, dx, ph, pw, pool=0, drop_p=drop[0], seed=seeds[i],
+                                                             dg_out=sk[o + 4], db_out=sk[o + 5])
+            _deliver(grads, sk, o + 4, dg2)
+            _deliver(grads, sk, o + 5, db2)
+            del dx
+            _deliver(grads, sk, o + 3, sw.wgrad(a1, dy2, out=sk[o + 3]))
+            da1 = conv3x3(dy2, wd2, y1.shape[3])                       # plain conv2 dgrad
+            sw.release()
+            del dy2
+            dy1, dg1, db1, dtexts[i] = bias_bnrelu_backward(y1, s1, g1, t, da1, prev=clip2, dg_out=sk[o + 1], db_out=sk[o + 2])
+            del da1, clip2
+            _deliver(grads, sk, o + 1, dg1)
+            _deliver(grads, sk, o + 2, db1)
+            if i > 0:
+                _deliver(grads, sk, o, sw.wgrad(x_in, dy1, out=sk[o]))
+                dx = conv3x3(dy1, wd1, x_in.shape[3])
+                sw.release()
+            else:
+                x0, aug = sv["x0"], sv["aug"]
+                if x0 is None:
+                    dw0, dbn0 = conv3x3_c1_backward(lm, dy1, c1w, st0.scale, st0.shift, out=sk[2], bn_bwd=None)
+                else:
+                    dw0, dx0 = conv3x3_c1_backward(x0, dy1, c1w, None, None, out=sk[2], bn_bwd=None)
+                    dbn0 = augment_backward(dx0, lm.shape[0], *aug)
+                    del dx0
+                _deliver(grads, sk, 2, dw0)
+                Bq, Fr, NM = lm.shape
+                dg0, db0 = bn_param_grad(lm.view(Bq * Fr, NM), dbn0.view(Bq * Fr, NM), st0, dg_out=sk[0], db_out=sk[1])
+                _deliver(grads, sk, 0, dg0)
+                _deliver(grads, sk, 1, db0)
+            del dy1
+            sv["acts"][i] = None
+            sw.release()
+            if prm is not None:
+                _ready(prm[o:o + 6] + ((prm[0], prm[1]) if i == 0 else ()))
+                _flush()
+        sw.join()
+        return (None, None, *dtexts, du, dr, *grads)
+
+
+class ConvTextBlockFunction(TagFunction):
+    """ConvTextBlock.forward on its own (models/audio_text_model.py:614-636): channels-last x (B,H,W,Cin), t = fc_text(text)
+    (B, C) -> dropout-free pool(relu(bn2(conv2(relu(bn1(conv1(x)) + t))) + t)) (B, H/ph, W/pw, C); the passes of
+    CrossCnn8RnnFunction's blocks.  ``bns`` = (bn1, bn2): their running statistics are updated in train mode."""
+
+    @staticmethod
+    def forward(ctx, x, t, bns, ph, pw, pool, c1w, g1, b1, c2w, g2, b2):
+        check_cross_precision()
+        x, t_ = _chk(x, "x"), _chk(t.detach(), "text bias")
+        c1w, g1, b1, c2w, g2, b2 = (_chk(v.detach(), "parameter") for v in (c1w, g1, b1, c2w, g2, b2))
+        bn1, bn2 = bns
+        B, H, W, Cin = x.shape
+        C = c1w.shape[0]
+        if t_.shape != (B, C):
+            raise RuntimeError(f"ConvTextBlock: text bias of shape {tuple(t_.shape)}, expected {(B, C)}")
+        train1, train2 = bn1.training, bn2.training
+        if Cin == 1:
+            y1, part1 = conv3x3_c1_stats(x.view(B, H, W), c1w, want_stats=train1)
+            wd1 = None
+        elif Cin % 32 == 0:
+            wf1, wd1 = pack_conv_weight(c1w, want_dgrad=True, W=W)
+            y1, part1 = conv3x3_stats(x, wf1, C, want_stats=train1)
+        else:
+            raise RuntimeError(f"ConvTextBlock: in_channels must be 1 or a multiple of 32, got {Cin}")
+        s1 = bn_stats(y1.view(-1, C), g1, b1, bn1.running_mean, bn1.running_var, train1, bn1.eps, bn1.momentum, partials=part1)
+        a1 = bias_bnrelu_forward(y1, s1, t_)
+        wf2, wd2 = pack_conv_weight(c2w, want_dgrad=True, W=W)
+        y2, part2 = conv3x3_stats(a1, wf2, C, want_stats=train2)
+        s2 = bn_stats(y2.view(-1, C), g2, b2, bn2.running_mean, bn2.running_var, train2, bn2.eps, bn2.momentum, partials=part2)
+        out = bias_bnrelu_pool(y2, s2, t_, ph, pw, pool=pool)
+        ctx.saved = (x, t_, y1, s1, a1, y2, s2, wd1, wd2, c1w, g1, g2, ph, pw, pool)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, t_, y1, s1, a1, y2, s2, wd1, wd2, c1w, g1, g2, ph, pw, pool = ctx.saved
+        ctx.saved = None
+        B, H, W, Cin = x.shape
+        C = y1.shape[3]
+        dy2, dg2, db2, clip2 = bias_bnrelu_pool_backward(y2, s2, g2, t_, _chk(dout, "grad"), ph, pw, pool=pool)
+        dc2 = conv3x3_wgrad(a1, dy2)
+        da1 = conv3x3(dy2, wd2, C)
+        dy1, dg1, db1, dt = bias_bnrelu_backward(y1, s1, g1, t_, da1, prev=clip2)
+        if Cin == 1:
+            dc1 = conv3x3_c1_wgrad(x.view(B, H, W), dy1)
+            dx = conv3x3_c1_dgrad(dy1, c1w).view(B, H, W, 1)
+        else:
+            dc1 = conv3x3_wgrad(x, dy1)
+            dx = conv3x3(dy1, wd1, Cin)
+        return dx, dt, None, None, None, None, dc1, dg1, db1, dc2, dg2, db2
 
 
 class SpecAugmentFunction(TagFunction):

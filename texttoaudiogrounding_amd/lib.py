@@ -39,6 +39,15 @@ _SIGS = {
     "tag_bn_param_grad": (c_int, [P, P, c_long, c_int, P, P, P, P, P, P]),
     "tag_augment_forward": (c_int, [P, P, P, P, c_int, c_int, P, P, c_int, c_int, c_int, P]),
     "tag_augment_backward": (c_int, [P, P, c_int, c_int, P, P, c_int, c_int, c_int, P]),
+    "tag_clip_reduce_ws_bytes": (c_size_t, [c_int, c_int]),
+    "tag_bias_bnrelu_forward": (c_int, [P, P, P, P, P, c_int, c_long, c_int, P]),
+    "tag_bias_bnrelu_pool_forward": (c_int, [P] * 5 + [c_int] * 7 + [c_float, c_uint64, P]),
+    "tag_bias_bnrelu_pool_backward": (c_int, [P] * 12 + [c_int] * 7 + [c_float, c_uint64, c_int, P, P]),
+    "tag_bias_bnrelu_backward": (c_int, [P] * 14 + [c_int, c_long, c_int, c_int, P, P]),
+    "tag_rowgroup_bias_relu": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "tag_rowgroup_colsum": (c_int, [P, c_int, c_int, c_int, P, P, P, P, P]),
+    "tag_frame_head_forward": (c_int, [P] * 6 + [c_int] * 3 + [P]),
+    "tag_frame_head_backward": (c_int, [P] * 10 + [c_int] * 3 + [P, P]),
     "tag_pack_conv_weight": (c_int, [P, P, P, c_int, c_int, P]),
     "tag_conv3x3_stats_rows": (c_int, [c_int, c_int, c_int, c_int]),
     "tag_conv3x3_x3_stats_rows": (c_int, [c_int, c_int, c_int, c_int]),

@@ -1,10 +1,16 @@
-"""Model composition (mirror of BiEncoder, models/audio_text_model.py:16-98 in the reference)."""
+"""Model composition (mirror of BiEncoder, models/audio_text_model.py:16-98 in the reference) and the early-fusion
+CrossCnn8_Rnn grounding model (models/audio_text_model.py:571-840)."""
+import sys
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from .. import ops
+from .. import engine, torch_ops
+from .audio_encoder import _MelFrontendBuffers, slaney_mel_filterbank
+from .augmentation import SpecAugmentation
+from .panns import init_bn, init_layer
 
 
 class BiEncoder(nn.Module):
@@ -224,3 +230,180 @@ class AudioTextAlignByPhrase(nn.Module):
         if input_dict.get("output_matrix", False):
             output["sim_matrix"] = sim_matrix
         return output
+
+
+class ConvTextBlock(nn.Module):
+    """PANNs conv block with the text added between BatchNorm and ReLU (models/audio_text_model.py:571-636): the reference's
+    parameters and state-dict keys (conv1, conv2 without bias; bn1, bn2; fc_text).  Inside CrossCnn8_Rnn the whole-model node
+    reads them; ``forward`` is the block on its own."""
+
+    def __init__(self, in_channels, out_channels, text_emb_dim):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=(3, 3), stride=(1, 1), padding=(1, 1), bias=False)
+        self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=(3, 3), stride=(1, 1), padding=(1, 1), bias=False)
+        self.bn1 = nn.BatchNorm2d(out_channels)
+        self.bn2 = nn.BatchNorm2d(out_channels)
+        self.fc_text = nn.Linear(text_emb_dim, out_channels)
+        self.init_weight()
+
+    def init_weight(self):
+        init_layer(self.conv1)
+        init_layer(self.conv2)
+        init_layer(self.fc_text)
+        init_bn(self.bn1)
+        init_bn(self.bn2)
+
+    def forward(self, audio, text, pool_size=(2, 2), pool_type="avg"):
+        """audio NCHW (B, Cin, T, F), text (B, text_emb_dim) -> (B, C, T/ph, F/pw)."""
+        if pool_type not in ops.POOL_TYPES:
+            raise Exception("Incorrect argument!")
+        ph, pw = (pool_size, pool_size) if isinstance(pool_size, int) else (int(pool_size[0]), int(pool_size[1]))
+        if (ph, pw) not in ops.POOL_SIZES:
+            raise RuntimeError(f"ConvTextBlock: pool_size {(ph, pw)} has no kernel instance (built: {sorted(ops.POOL_SIZES)})")
+        t = ops.LinearFunction.apply(text, self.fc_text.weight, self.fc_text.bias)
+        for m in (self.bn1, self.bn2):
+            if m.training:
+                m.num_batches_tracked += 1
+        x = audio.permute(0, 2, 3, 1).contiguous()               # channels-last (plumbing copy)
+        y = ops.ConvTextBlockFunction.apply(x, t, (self.bn1, self.bn2), ph, pw, ops.POOL_TYPES[pool_type], self.conv1.weight,
+                                            self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias)
+        return y.permute(0, 3, 1, 2).contiguous()
+
+
+class CrossCnn8_Rnn(nn.Module):
+    """Early-fusion grounding model (models/audio_text_model.py:639-840): the phrase embedding e = text_encoder(...)["seq_emb"]
+    enters every conv layer as a per-(clip, channel) bias (conv_block{i}.fc_text(e)), fc1 (fc1_text(e)) and the GRU output
+    (rnn_text(e)); frame_sim (B, T', 1) = clamp(sigmoid(fc_output(.)), 1e-7, 1).  Same constructor, submodule names and
+    state-dict keys as the reference (plus the two melspec buffers, as Cnn8Rnn).  Below the text encoder and the six text
+    linears the model is ONE operator, tag::cross_cnn8rnn (ops.CrossCnn8RnnFunction).  fp32 only."""
+
+    def __init__(self, sample_rate, text_encoder, freeze_cnn=False, freeze_bn=False, upsample=False):
+        super().__init__()
+        self.text_encoder = text_encoder
+        self.interpolate_ratio = 4
+        self.downsample_ratio = 4
+        self.upsample = upsample
+        self.freeze_cnn = freeze_cnn
+        self.freeze_bn = freeze_bn
+        self.hop_length = int(0.010 * sample_rate)
+        self.win_length = int(0.032 * sample_rate)
+        self.n_fft = self.win_length
+        if self.n_fft not in (1024, 2048):
+            raise ValueError(f"the HIP log-mel frontend supports n_fft 1024/2048 (sample_rate 32000/64000), got {self.n_fft}")
+        f_max = 14000 if sample_rate == 32000 else int(sample_rate / 2)
+        self.melspec_extractor = _MelFrontendBuffers(
+            torch.hann_window(self.win_length),
+            slaney_mel_filterbank(self.n_fft // 2 + 1, 50.0, float(f_max), 64, sample_rate))
+        self.spec_augmenter = SpecAugmentation(time_drop_width=64, time_stripes_num=2, freq_drop_width=8, freq_stripes_num=2)
+        self.text_emb_dim = text_encoder.embed_dim
+        self.bn0 = nn.BatchNorm2d(64)
+        self.conv_block1 = ConvTextBlock(1, 64, self.text_emb_dim)
+        self.conv_block2 = ConvTextBlock(64, 128, self.text_emb_dim)
+        self.conv_block3 = ConvTextBlock(128, 256, self.text_emb_dim)
+        self.conv_block4 = ConvTextBlock(256, 512, self.text_emb_dim)
+        self.fc1 = nn.Linear(512, 512, bias=True)
+        self.fc1_text = nn.Linear(self.text_emb_dim, 512)
+        self.rnn = nn.GRU(512, 256, bidirectional=True, batch_first=True)
+        self.rnn_text = nn.Linear(self.text_emb_dim, 512)
+        self.fc_output = nn.Linear(512, 1)
+        self.dropout_p = (0.2, 0.5)     # F.dropout sites of the reference forward (:757-766, :812)
+        self.init_weight()
+        if self.freeze_cnn:
+            for param in self.parameters():
+                param.requires_grad = False
+            for param in self.rnn.parameters():
+                param.requires_grad = True
+
+    def init_weight(self):
+        init_bn(self.bn0)
+        init_layer(self.fc1)
+        init_layer(self.fc1_text)
+        init_layer(self.rnn_text)
+        init_layer(self.fc_output)
+
+    def load_pretrained(self, pretrained, output_fn=sys.stdout.write, training=True, cnn_only=False):
+        """Shape-matched merge of a checkpoint (models/audio_text_model.py:709-736); ``cnn_only`` in training drops every key that
+        starts with ``rnn``, ``fc1`` or ``fc_output`` (so ``rnn_text.*`` and ``fc1_text.*`` too, as the reference's prefix
+        test does)."""
+        state_dict = pretrained if isinstance(pretrained, dict) else torch.load(pretrained, map_location="cpu")
+        if "model" in state_dict:
+            state_dict = state_dict["model"]
+        model_dict = self.state_dict()
+        pretrained_dict = {k: v for k, v in state_dict.items() if k in model_dict and model_dict[k].shape == v.shape}
+        if cnn_only and training:
+            pretrained_dict = {k: v for k, v in pretrained_dict.items()
+                               if not (k.startswith("rnn") or k.startswith("fc1") or k.startswith("fc_output"))}
+        output_fn(f"Loading pretrained keys {pretrained_dict.keys()}")
+        model_dict.update(pretrained_dict)
+        self.load_state_dict(model_dict, strict=True)
+
+    def train(self, mode: bool = True):
+        super().train(mode=mode)
+        if self.freeze_bn:
+            for m in self.modules():
+                if m.__class__.__name__.find("BatchNorm") != -1:
+                    m.eval()
+        return self
+
+    @property
+    def window(self):
+        return self.melspec_extractor.spectrogram.window
+
+    @property
+    def mel_fb(self):
+        return self.melspec_extractor.mel_scale.fb
+
+    def _blocks(self):
+        return [getattr(self, f"conv_block{i}") for i in range(1, 5)]
+
+    def _flat_params(self):
+        ps = [self.bn0.weight, self.bn0.bias]
+        for blk in self._blocks():
+            ps += [blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, blk.conv2.weight, blk.bn2.weight, blk.bn2.bias]
+        ps += [self.fc1.weight, self.fc1.bias]
+        for sfx in ("", "_reverse"):
+            ps += [getattr(self.rnn, f"weight_ih_l0{sfx}"), getattr(self.rnn, f"weight_hh_l0{sfx}"),
+                   getattr(self.rnn, f"bias_ih_l0{sfx}"), getattr(self.rnn, f"bias_hh_l0{sfx}")]
+        ps += [self.fc_output.weight, self.fc_output.bias]
+        return ps
+
+    def _check_args(self, waveform, specaug, mixup_lambda):
+        """Train-mode augmentation arguments, checked before any launch: () or (stripes,) on the device."""
+        self._last_specaug = None
+        if not self.training:
+            return ()
+        if mixup_lambda is not None:
+            raise ValueError("CrossCnn8_Rnn: mixup is not supported. The reference's do_mixup halves the clips while the text "
+                             "embedding keeps one row per clip, so B text rows would meet B/2 clips (a silent broadcast at "
+                             "B = 2, an error for B >= 4); pass mixup_lambda=None")
+        if not specaug:
+            return ()
+        frames = waveform.shape[1] // self.hop_length + 1
+        stripes = self.spec_augmenter.draw(waveform.shape[0], frames, self.bn0.num_features)
+        self._last_specaug = stripes
+        return (torch_ops.stage_to_device(stripes, waveform.device, torch.int32),)
+
+    def forward(self, input_dict):
+        ops.check_cross_precision()
+        waveform = input_dict["waveform"]
+        augment = self._check_args(waveform, input_dict["specaug"], input_dict.get("mixup_lambda", None))
+        e = self.text_encoder(input_dict)["seq_emb"]
+        texts = [ops.LinearFunction.apply(e, blk.fc_text.weight, blk.fc_text.bias) for blk in self._blocks()]
+        texts += [ops.LinearFunction.apply(e, self.fc1_text.weight, self.fc1_text.bias),
+                  ops.LinearFunction.apply(e, self.rnn_text.weight, self.rnn_text.bias)]
+        if self.training and not self.freeze_bn:
+            ops.bump_bn_counters(self, [self.bn0, *(b.bn1 for b in self._blocks()), *(b.bn2 for b in self._blocks())])
+        params = self._flat_params()
+        need = torch.is_grad_enabled() and any(t.requires_grad for t in list(params) + texts)
+        prev, engine._RECORDING = engine._RECORDING, torch.is_grad_enabled()
+        try:
+            prob = torch.ops.tag.cross_cnn8rnn(waveform, texts, params, torch_ops.encoder_token(self), need, *augment)
+        finally:
+            engine._RECORDING = prev
+            torch_ops._ENC_HANDOVER[0] = None
+        length = torch.div(torch.as_tensor(input_dict["waveform_len"]), self.hop_length, rounding_mode="floor") + 1
+        length = torch.div(length, self.interpolate_ratio, rounding_mode="floor")
+        if self.interpolate_ratio != 1 and self.upsample:
+            prob = ops.UpsampleLinearFunction.apply(prob.squeeze(2), self.interpolate_ratio).unsqueeze(2)
+            length = length * self.interpolate_ratio
+        return {"frame_sim": prob, "length": length}

@@ -472,6 +472,43 @@ def _(waveform, params, module_token, need_grad):
 register_autograd("tag::crnn_encoder", _enc_backward, setup_context=_enc_setup)
 
 
+@custom_op("tag::cross_cnn8rnn", mutates_args=())
+def cross_cnn8rnn(waveform: Tensor, texts: List[Tensor], params: List[Tensor], module_token: int, need_grad: bool,
+                  specaug_stripes: Optional[Tensor] = None) -> Tensor:
+    """CrossCnn8_Rnn.forward of models/audio_text_model.py:785-840 below its text encoder: waveform (B,S) -> frame_sim
+    (B, T', 1) before the optional x4 upsampling.  texts = [conv_block1..4.fc_text(e), fc1_text(e), rnn_text(e)] (B, C);
+    params in CrossCnn8_Rnn._flat_params() order.  BatchNorm running statistics: module state, as tag::cnn8rnn_encoder.
+    specaug_stripes: as tag::cnn8rnn_encoder (no mixup: the reference's cannot run, see CrossCnn8_Rnn)."""
+    mod = _ENC_MODULES[module_token]
+    augment = None
+    if specaug_stripes is not None:
+        augment = (specaug_stripes, mod.spec_augmenter.time_dropper.stripes_num, None)
+    ctx = _EncCtx((False, False) + tuple(bool(need_grad and t.requires_grad) for t in list(texts) + list(params)), augment)
+    y = ops.CrossCnn8RnnFunction.forward(ctx, waveform, mod, *texts, *params)
+    _ENC_HANDOVER[0] = (ops.CrossCnn8RnnFunction, ctx) if need_grad else None
+    return y
+
+
+@cross_cnn8rnn.register_fake
+def _(waveform, texts, params, module_token, need_grad, specaug_stripes=None):
+    mod = _ENC_MODULES[module_token]
+    return waveform.new_empty(waveform.shape[0], _enc_fake_frames(mod, waveform), 1)
+
+
+def _cross_setup(ctx, inputs, output):
+    _enc_setup(ctx, inputs, output)
+    ctx.n_args = 6 if inputs[5] is not None else 5
+
+
+def _cross_backward(ctx, dy):
+    g = _enc_backward(ctx, dy)                # (None, [texts..., params...], None, ...)
+    flat = g[1]
+    return (None, flat[:6], flat[6:]) + (None,) * (ctx.n_args - 3)
+
+
+register_autograd("tag::cross_cnn8rnn", _cross_backward, setup_context=_cross_setup)
+
+
 def stage_to_device(t, device, dtype):
     """A small host table (stripes, mixup lambda) -> ``device`` through pinned memory, non-blocking (a pageable host->device
     copy waits for the stream to drain: the host would stall mid-step, runner.py stages the lengths the same way)."""
@@ -516,4 +553,5 @@ def _(frame_sim, thresholds, window_size, n_connect):
 
 OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_relu_pool", "conv3x3_bn_relu_pool_backward",
             "gru_bidir", "gru_bidir_backward", "embed_mean", "embed_mean_backward", "frame_match", "frame_match_backward",
-            "align_dot", "align_dot_backward", "frame_bce", "frame_bce_backward", "segments", "cnn8rnn_encoder", "crnn_encoder"]
+            "align_dot", "align_dot_backward", "frame_bce", "frame_bce_backward", "segments", "cnn8rnn_encoder", "crnn_encoder",
+            "cross_cnn8rnn"]
