@@ -720,6 +720,38 @@ int tag_frame_head_forward(const float* y, const float* rb, const float* w, cons
 int tag_frame_head_backward(const float* y, const float* rb, const float* w, const float* sig, const float* dprob, float* dy,
                             float* dw, float* dsum, float* drb, double* clip, int B, int T, int N, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Early-fusion CrossCDur (models/audio_text_model.py:461-568): BatchNorm sits in FRONT of each conv and the text is added to the
+ * RAW conv output, leaky(conv(bn(x)) + bias[b, c]), so the bias is one add in the conv kernel's epilogue and the forward has
+ * no pass of its own for it.  fp32, channels-last; bias (B, Cout).  With an all-zero bias the output equals the unbiased
+ * entry's bit for bit.  A shape without an instance returns TAG_EINVAL (tag_last_error names the entry), it is not launched.
+ *   tag_conv3x3_forward_bias     y = conv(prologue(x)) + bias[b]: the halo-tile kernel (EPI == 4) at W 16 | 4, Cin 32 | 128,
+ *                                Cout 128, prologue 2 (scale*leaky(x)+shift) | 3 (scale*x+shift); wpack of tag_pack_conv_weight
+ *   tag_conv3x3_c1_forward_bias  the Cin = 1 conv (x (B,H,W), optional per-column affine) + bias[b]: W % 4 == 0, Cout / 4 a
+ *                                divisor of 256; a workgroup may hold rows of two clips, the bias row is the pixel's own clip
+ *   tag_leaky_forward / _backward  leaky_relu(z, 0.1) and dz = dout * (z > 0 ? 1 : 0.1) over n % 4 == 0 floats: the activation of a
+ *                                CDurTextBlock used outside the model (inside it the pool pass / the next conv's prologue has it)
+ * The gradient of the bias is the per-clip sum of dz, dt[b, c] = sum over (h, w) of dz[b, h, w, c]: emitted by the pass that
+ * writes dz (below), or tag_rowgroup_colsum over dz viewed as (B, H*W, C) in a pass of its own.
+ *   tag_lppool_leaky_backward_clip  tag_lppool_leaky_backward + dt (B, C); clip (B, 2, C) doubles (slot 0 = the sums),
+ *                                ws: tag_clip_reduce_ws_bytes(B, C) bytes.  dy bit-identical to the plain entry's
+ *   tag_bn_act_backward_clip     tag_bn_act_backward over x (B, HW, C) + dt (B, C) of dx; ws: tag_bn_backward_ws_bytes(B*HW, C),
+ *                                ws_clip: tag_clip_reduce_ws_bytes(B, C).  dx, dgamma, dbeta bit-identical to the plain entry's
+ * Both fold fp64 partial rows that never straddle two clips in a fixed order (no atomics): bitwise repeatable.
+ * The frame head is tag_frame_head_forward / _backward at N = 256, the x4 upsampling tag_upsample_linear_*.
+ */
+int tag_conv3x3_forward_bias(const float* x, const float* wpack, int prologue, const float* in_scale, const float* in_shift,
+                             const float* bias, float* y, int B, int H, int W, int Cin, int Cout, void* stream);
+int tag_conv3x3_c1_forward_bias(const float* x, const float* col_scale, const float* col_shift, const float* w,
+                                const float* bias, float* y, int B, int H, int W, int Cout, void* stream);
+int tag_lppool_leaky_backward_clip(const float* y, const float* dout, float* dy, float* dt, double* clip, int B, int H, int W,
+                                   int C, int ph, int pw, float drop_p, uint64_t seed, void* ws, void* stream);
+int tag_bn_act_backward_clip(const float* x, int pre_op, const float* mean, const float* invstd, const float* gamma,
+                             const float* du, float* dx, float* dgamma, float* dbeta, float* dt, double* clip, int B, long HW,
+                             int C, int bn_train, void* ws, void* ws_clip, void* stream);
+int tag_leaky_forward(const float* z, float* out, long n, void* stream);
+int tag_leaky_backward(const float* z, const float* dout, float* dz, long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1518,3 +1518,224 @@ extern "C" int tag_frame_head_backward(const float* y, const float* rb, const fl
     TAG_LAUNCH_CHECK();
     return clip_fold_and_total(partials, nblk, B, N, clip, nullptr, w, drb, dw, dsum, st);
 }
+
+// ------------------------------------------------------------------------------------------
+// LeakyReLU(0.1) on its own: the activation of a CDurTextBlock used OUTSIDE CrossCDur (models/audio_text_model.py:461-479; inside
+// the model it is folded into the pool pass or the next conv's prologue).  n % 4 == 0.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void leaky_fwd_kernel(const float4* __restrict__ z, float4* __restrict__ out, long n4) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const float4 v = z[i];
+        out[i] = make_float4(leaky01(v.x), leaky01(v.y), leaky01(v.z), leaky01(v.w));
+    }
+}
+__global__ __launch_bounds__(256) void leaky_bwd_kernel(const float4* __restrict__ z, const float4* __restrict__ dout,
+                                                        float4* __restrict__ dz, long n4) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const float4 v = z[i], g = dout[i];
+        dz[i] = make_float4(v.x > 0.0f ? g.x : 0.1f * g.x, v.y > 0.0f ? g.y : 0.1f * g.y, v.z > 0.0f ? g.z : 0.1f * g.z,
+                            v.w > 0.0f ? g.w : 0.1f * g.w);
+    }
+}
+extern "C" int tag_leaky_forward(const float* z, float* out, long n, void* stream) {
+    TAG_CHECK_ARG(z && out && n > 0 && n % 4 == 0);
+    hipLaunchKernelGGL(leaky_fwd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const float4*>(z), reinterpret_cast<float4*>(out), n / 4);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int tag_leaky_backward(const float* z, const float* dout, float* dz, long n, void* stream) {
+    TAG_CHECK_ARG(z && dout && dz && n > 0 && n % 4 == 0);
+    hipLaunchKernelGGL(leaky_bwd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const float4*>(z), reinterpret_cast<const float4*>(dout), reinterpret_cast<float4*>(dz),
+                       n / 4);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Backward passes of CrossCDur that also emit the per-clip sums of what they write: the text enters as a per-clip bias on the raw
+// conv output z, so d bias[b, c] = sum over (h, w) of dz[b, h, w, c], and dz is the output of lppool_leaky_bwd_kernel (blocks 1,
+// 3, 5) or bn_act_bwd_apply_kernel (blocks 2, 4).  CLIP forms of those two kernels: one clip per blockIdx.y, the same arithmetic
+// per element (dz is bit-identical to the plain kernels'), every thread adds what it stores to fp64 sums of its channel quad,
+// folded through LDS into partial rows [clip][blk][2][C] (slot 1 unused, zero) that never straddle two clips;
+// clip_fold_kernel folds them in a fixed order (no atomics) -- the protocol of the per-clip bias passes above.  They replace a
+// tag_rowgroup_colsum pass over dz.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void clip_block_fold(double s[4], int tpr, int rpi, int rsub, int c, int C,
+                                                double* __restrict__ partials) {
+    __shared__ double sred[256][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sred[threadIdx.x][j] = s[j];
+    __syncthreads();
+    if (rsub == 0) {
+        for (int q = 1; q < rpi; ++q)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[j] += sred[threadIdx.x + q * tpr][j];
+        double* p = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * C;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { p[c + j] = s[j]; p[C + c + j] = 0.0; }
+    }
+}
+
+template <int PH, int PW>
+__global__ __launch_bounds__(256) void lppool_leaky_bwd_clip_kernel(const float* __restrict__ y, const float* __restrict__ dout,
+                                                                    float* __restrict__ dy, int H, int W, int C, float drop_p,
+                                                                    uint64_t seed, double* __restrict__ partials) {
+    const int Ho = H / PH, Wo = W / PW, C4 = C >> 2, rpi = 256 / C4;
+    const int c = (threadIdx.x % C4) << 2, rsub = threadIdx.x / C4;
+    const int Hs = (H + PH - 1) / PH, Ws = (W + PW - 1) / PW;
+    const int slots = Hs * Ws;                                  // of ONE clip
+    const int b = blockIdx.y;
+    const float keep_scale = drop_p > 0.0f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    double acc[4] = {0, 0, 0, 0};
+    for (int r = blockIdx.x * rpi + rsub; r < slots; r += gridDim.x * rpi) {
+        const int ws = r % Ws, hs = r / Ws;
+        const bool full = hs < Ho && ws < Wo;
+        float a[PH][PW][4], yv[PH][PW][4], sum[4] = {0, 0, 0, 0};
+        bool ex[PH][PW];
+#pragma unroll
+        for (int dh = 0; dh < PH; ++dh)
+#pragma unroll
+            for (int dw = 0; dw < PW; ++dw) {
+                const int h = hs * PH + dh, w = ws * PW + dw;
+                ex[dh][dw] = h < H && w < W;
+                float4 v = make_float4(0, 0, 0, 0);
+                if (ex[dh][dw]) v = *reinterpret_cast<const float4*>(y + (((size_t)b * H + h) * W + w) * C + c);
+                const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    yv[dh][dw][j] = vv[j];
+                    a[dh][dw][j] = leaky01(vv[j]);
+                    const float a2 = a[dh][dw][j] * a[dh][dw][j];
+                    sum[j] += a2 * a2;
+                }
+            }
+        float k[4] = {0, 0, 0, 0};
+        if (full) {
+            const size_t oi = (((size_t)b * Ho + hs) * Wo + ws) * C + c;
+            const float4 g4 = *reinterpret_cast<const float4*>(dout + oi);
+            float g[4] = {g4.x, g4.y, g4.z, g4.w};
+            const uint64_t bits = drop_p > 0.0f ? tag_keep4_bits(seed, (uint64_t)(oi >> 2)) : 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (drop_p > 0.0f) g[j] = tag_keep4(bits, j, tag_keep4_threshold(drop_p)) ? g[j] * keep_scale : 0.0f;
+                const float out = sqrtf(sqrtf(sum[j]));
+                k[j] = out > 0.0f ? g[j] / (out * out * out) : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int dh = 0; dh < PH; ++dh)
+#pragma unroll
+            for (int dw = 0; dw < PW; ++dw) {
+                if (!ex[dh][dw]) continue;
+                float o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float aa = a[dh][dw][j];
+                    const float da = k[j] * aa * aa * aa;
+                    o[j] = yv[dh][dw][j] > 0.0f ? da : 0.1f * da;
+                    acc[j] += o[j];
+                }
+                const int h = hs * PH + dh, w = ws * PW + dw;
+                *reinterpret_cast<float4*>(dy + (((size_t)b * H + h) * W + w) * C + c) = make_float4(o[0], o[1], o[2], o[3]);
+            }
+    }
+    clip_block_fold(acc, C4, rpi, rsub, c, C, partials);
+}
+
+// bn_act_bwd_apply_kernel clip by clip: rows = rows of ONE clip, the BatchNorm count is that of all clips
+__global__ __launch_bounds__(256) void bn_act_bwd_apply_clip_kernel(BnActBwdFn fn, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ dgamma,
+                                                                    const float* __restrict__ dbeta, int bn_train,
+                                                                    long rows, float* __restrict__ dx,
+                                                                    double* __restrict__ partials) {
+    const int C = fn.C, tpr = C >> 2, rpi = 256 / tpr;
+    const int c = (threadIdx.x % tpr) << 2, rsub = threadIdx.x / tpr;
+    const float invN = 1.0f / (float)(rows * gridDim.y);
+    const long r0 = (long)blockIdx.y * rows;
+    fn.prep(c);
+    float k0[4], k1[4], k2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        k0[j] = (gamma ? gamma[c + j] : 1.0f) * fn.invstd[c + j];
+        k1[j] = bn_train ? dbeta[c + j] * invN : 0.0f;
+        k2[j] = bn_train ? dgamma[c + j] * invN : 0.0f;
+    }
+    const float mv[4] = {fn.m.x, fn.m.y, fn.m.z, fn.m.w}, iv[4] = {fn.is.x, fn.is.y, fn.is.z, fn.is.w};
+    double acc[4] = {0, 0, 0, 0};
+    for (long r = (long)blockIdx.x * rpi + rsub; r < rows; r += (long)gridDim.x * rpi) {
+        const float4 xv = *reinterpret_cast<const float4*>(fn.x + (size_t)(r0 + r) * C + c);
+        const float4 g = *reinterpret_cast<const float4*>(fn.du + (size_t)(r0 + r) * C + c);
+        const float xx[4] = {xv.x, xv.y, xv.z, xv.w}, gg[4] = {g.x, g.y, g.z, g.w};
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float v = fn.pre == 1 ? leaky01(xx[j]) : xx[j];
+            const float dv = k0[j] * (gg[j] - k1[j] - (v - mv[j]) * iv[j] * k2[j]);
+            o[j] = (fn.pre == 1 && xx[j] <= 0.0f) ? 0.1f * dv : dv;
+            acc[j] += o[j];
+        }
+        *reinterpret_cast<float4*>(dx + (size_t)(r0 + r) * C + c) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+    clip_block_fold(acc, tpr, rpi, rsub, c, C, partials);
+}
+
+// workgroups per clip of the two kernels above: ~4 iterations per thread, at most 2048 partial rows over all clips
+// (tag_clip_reduce_ws_bytes)
+static int clip_apply_blocks(long rows_per_clip, int C, int B) {
+    const int rpi = 256 / (C >> 2);
+    long nb = (rows_per_clip + (long)rpi * 4 - 1) / ((long)rpi * 4);
+    const int cap = B >= 2048 ? 1 : (2048 / B < RED_MAX_BLOCKS ? 2048 / B : RED_MAX_BLOCKS);
+    if (nb > cap) nb = cap;
+    return (int)(nb < 1 ? 1 : nb);
+}
+
+// tag_lppool_leaky_backward that also writes dt (B, C) = per-clip sums of dy; clip (B, 2, C) doubles (slot 0 = the sums),
+// ws: tag_clip_reduce_ws_bytes(B, C) bytes.  dy is bit-identical to tag_lppool_leaky_backward's.
+extern "C" int tag_lppool_leaky_backward_clip(const float* y, const float* dout, float* dy, float* dt, double* clip, int B,
+                                              int H, int W, int C, int ph, int pw, float drop_p, uint64_t seed, void* ws,
+                                              void* stream) {
+    TAG_CHECK_ARG(y && dout && dy && dt && clip && ws && B > 0 && B <= 65535 && vec_ok(C) && H / ph > 0 && W / pw > 0);
+    TAG_CHECK_ARG((long)((H + ph - 1) / ph) * ((W + pw - 1) / pw) < (1L << 31));
+    double* partials = static_cast<double*>(ws);
+    hipStream_t st = as_stream(stream);
+    const int nb = clip_apply_blocks((long)((H + ph - 1) / ph) * ((W + pw - 1) / pw), C, B);
+    bool launched = false;
+#define LP_CLIP hipLaunchKernelGGL((lppool_leaky_bwd_clip_kernel<PH, PW>), dim3(nb, B), dim3(256), 0, st, y, dout, dy, H, W, C, \
+                                   drop_p, seed, partials)
+    DISPATCH_POOL(2, 4, LP_CLIP)
+    DISPATCH_POOL(1, 4, LP_CLIP)
+    DISPATCH_POOL(2, 2, LP_CLIP)
+#undef LP_CLIP
+    TAG_CHECK_ARG(launched);
+    TAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(clip_fold_kernel, dim3(cdiv(C, 16), B), dim3(FOLD_T), 0, st, partials, nb, C, clip, nullptr, nullptr, dt);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+// tag_bn_act_backward over x (B, HW, C) that also writes dt (B, C) = per-clip sums of dx; ws: tag_bn_backward_ws_bytes(B*HW, C)
+// bytes, ws_clip: tag_clip_reduce_ws_bytes(B, C) bytes.  dx, dgamma, dbeta are bit-identical to tag_bn_act_backward's.
+extern "C" int tag_bn_act_backward_clip(const float* x, int pre_op, const float* mean, const float* invstd, const float* gamma,
+                                        const float* du, float* dx, float* dgamma, float* dbeta, float* dt, double* clip, int B,
+                                        long HW, int C, int bn_train, void* ws, void* ws_clip, void* stream) {
+    TAG_CHECK_ARG(x && mean && invstd && du && dx && dgamma && dbeta && dt && clip && ws && ws_clip && vec_ok(C));
+    TAG_CHECK_ARG((pre_op == 0 || pre_op == 1) && B > 0 && B <= 65535 && HW > 0);
+    const long rows = (long)B * HW;
+    double* partials = static_cast<double*>(ws);
+    double* cpart = static_cast<double*>(ws_clip);
+    hipStream_t st = as_stream(stream);
+    const int nblk = red_blocks(rows, C);
+    BnActBwdFn fn{x, mean, invstd, du, C, pre_op};
+    hipLaunchKernelGGL(reduce2_kernel<BnActBwdFn>, dim3(nblk), dim3(256), 256 * 8 * sizeof(double), st, fn, rows, C, partials);
+    TAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, st, partials, nblk, C, dgamma, dbeta);
+    const int nb = clip_apply_blocks(HW, C, B);
+    hipLaunchKernelGGL(bn_act_bwd_apply_clip_kernel, dim3(nb, B), dim3(256), 0, st, fn, gamma, dgamma, dbeta, bn_train, HW, dx,
+                       cpart);
+    TAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(clip_fold_kernel, dim3(cdiv(C, 16), B), dim3(FOLD_T), 0, st, cpart, nb, C, clip, nullptr, nullptr, dt);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}

@@ -325,6 +325,10 @@ struct BnBwdEpi {
     unsigned long long seed;
     int kind;               // 1 | 2 | 3 = the EPI instance to launch (host side only)
 };
+// EPI == 4 (the early-fusion CrossCDur, models/audio_text_model.py:461-479): y = conv(prologue(x)) + bias[img, cout] -- the text
+// enters on the RAW conv output, so it is one add on the quad-transposed registers in front of the store and no pass of its own.
+// `yref` carries the (B, Cout) bias table (the struct's other fields are unused); a workgroup's tile lies inside ONE image, so the
+// table row is wave-uniform.  Forward launches only (launch_halo_bias), no statistics.
 
 template <int BN_, int PRO, int TW, int EPI = 0>
 __global__ __launch_bounds__(256, BN_ == 64 ? 4 : (BN_ == 256 ? 2 : 3)) void conv3x3_halo_kernel(const float* __restrict__ x, const float* __restrict__ wp,
@@ -603,6 +607,8 @@ __global__ __launch_bounds__(256, BN_ == 64 ? 4 : (BN_ == 256 ? 2 : 3)) void con
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int nq = n0 + wn0 + j * 32 + (ml & ~3);       // first of the quad's 4 couts
+            f32x4 bq = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (EPI == 4) bq = ldg4(epi.yref + (size_t)img * Cout + (nq < Cout ? nq : 0));    // the clip's bias of these 4 couts
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -619,6 +625,7 @@ __global__ __launch_bounds__(256, BN_ == 64 ? 4 : (BN_ == 256 ? 2 : 3)) void con
                     const float r13 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s13), 0x4E, 0xF, 0xF, true));
                     if (hi) { x0 = r02; x1 = r13; } else { x2 = r02; x3 = r13; }
                     // now x_t = cout nq + t of the pixel behind register 4 rq + c4
+                    if (EPI == 4) { x0 += bq[0]; x1 += bq[1]; x2 += bq[2]; x3 += bq[3]; }
                     const int m = wm0 + i * 32 + halo_row_to_pix(c4 + 8 * rq + 4 * kl);
                     const int h = h0 + m / TW, w = w0 + m % TW;
                     if (EPI != 3 && h < H && nq < Cout)         // (EPI == 3 writes the POOLED tensor only, below)
@@ -1524,6 +1531,42 @@ __global__ __launch_bounds__(256) void conv_c1_fwd4_kernel(const float* __restri
     }
 }
 
+// conv_c1_fwd4_kernel with a per-clip bias on its output (CrossCDur block 1): y = conv(affine(x)) + bias[b, cout].  The pixel
+// groups run over the whole batch, so a workgroup may hold rows of two clips: the bias row is the group's own clip m / (H W).
+// Same summation order as conv_c1_fwd4_kernel, the bias added last: an all-zero table gives its output bit for bit.
+__global__ __launch_bounds__(256) void conv_c1_fwd4_bias_kernel(const float* __restrict__ x, const float* __restrict__ cs,
+                                                                const float* __restrict__ ct, const float* __restrict__ w,
+                                                                const float* __restrict__ bias, float* __restrict__ y, long M,
+                                                                int H, int W, int Cout) {
+    const int C4 = Cout >> 2, gpi = 256 / C4;   // requires 256 % C4 == 0: a thread keeps its channel quad
+    const long groups = M >> 2;                 // W % 4 == 0 -> M % 4 == 0 and a group never straddles a row
+    const int c = (threadIdx.x % C4) << 2;
+    const long HW = (long)H * W;
+    float wr[4][9];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int t = 0; t < 9; ++t) wr[j][t] = w[(c + j) * 9 + t];
+    for (long gi = (long)blockIdx.x * gpi + threadIdx.x / C4; gi < groups; gi += (long)gridDim.x * gpi) {
+        const long m = gi << 2;
+        const long b = m / HW;
+        const int hw = (int)(m - b * HW);
+        const int h = hw / W, w0 = hw % W;
+        const float4 bv = *reinterpret_cast<const float4*>(bias + b * Cout + c);
+        float xin[3][6];
+        c1_patch(x, cs, ct, H, W, m, h, w0, xin);
+#pragma unroll
+        for (int px = 0; px < 4; ++px) {
+            float o[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = fmaf(xin[tap / 3][px + tap % 3], wr[j][tap], o[j]);
+            *reinterpret_cast<float4*>(y + (m + px) * Cout + c) = make_float4(o[0] + bv.x, o[1] + bv.y, o[2] + bv.z, o[3] + bv.w);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void conv_c1_wgrad4_kernel(const float* __restrict__ x, const float* __restrict__ cs,
                                                              const float* __restrict__ ct,
                                                              const float* __restrict__ dy, double* __restrict__ partials,
@@ -2166,6 +2209,61 @@ extern "C" int tag_conv3x3_forward(const float* x, const float* wpack, int prolo
     return 0;
 }
 
+// Launch of the EPI == 4 instances: the 128-cout tile of tag_conv3x3_forward's statistics-free launch (same geometry, LDS size and
+// summation order, so an all-zero bias gives that entry's output bit for bit), prologues 2 and 3.
+template <int TW>
+static void launch_halo_bias(const float* x, const float* wp, int pro, const float* s, const float* t, const float* bias, float* y,
+                             int B, int H, int W, int Cin, int Cout, hipStream_t st) {
+    constexpr int BN_ = 128;
+    using G = HaloGeom<TW>;
+    const int col_tiles = W / TW;
+    const int row_tiles = ((H + G::TH - 1) / G::TH) * col_tiles, n_tiles = (Cout + BN_ - 1) / BN_;
+    const int grid = B * row_tiles * n_tiles;
+    auto magic = [](unsigned d, unsigned* mul, unsigned* shr) {            // n / d = (mulhi(n, mul) + n) >> shr for n < 2^31
+        unsigned l = 0;
+        while ((1u << l) < d) ++l;
+        *shr = l;
+        *mul = (unsigned)((((unsigned long long)1 << 32) * ((1ull << l) - d)) / d + 1);
+    };
+    unsigned nt_mul, nt_shr, rt_mul, rt_shr;
+    magic((unsigned)n_tiles, &nt_mul, &nt_shr);
+    magic((unsigned)row_tiles, &rt_mul, &rt_shr);
+    const size_t lds = (size_t)(G::ASZ + 2 * halo_stage<BN_>() * BN_ + 2 * ((Cin + 3) / 4 * 4)) * sizeof(float);
+    const BnBwdEpi epi{bias, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0ull, 4};
+#define LAUNCH_BIAS(P)                                                                                            \
+    {                                                                                                             \
+        static bool attr_set = false;                                                                             \
+        if (!attr_set) {                                                                                          \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<BN_, P, TW, 4>),         \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
+            attr_set = true;                                                                                      \
+        }                                                                                                         \
+        hipLaunchKernelGGL((conv3x3_halo_kernel<BN_, P, TW, 4>), dim3(grid), dim3(256), lds, st, x, wp, s, t, y,  \
+                           (float*)nullptr, epi, B, H, W, Cin, Cout, nt_mul, nt_shr, rt_mul, rt_shr, col_tiles);  \
+    }
+    if (pro == 2) LAUNCH_BIAS(2) else LAUNCH_BIAS(3)
+#undef LAUNCH_BIAS
+}
+
+// y = conv(prologue(x)) + bias[b, cout], bias (B, Cout): the conv of a CDurTextBlock (models/audio_text_model.py:461-479), the
+// text added in the kernel's epilogue.  Served: the halo-tile kernel at W = 16 or 4, Cin 32 or 128, Cout 128, prologue 2
+// (BatchNorm after LeakyReLU) or 3 (BatchNorm alone); anything else is TAG_EINVAL.  No BatchNorm statistics.
+extern "C" int tag_conv3x3_forward_bias(const float* x, const float* wpack, int prologue, const float* in_scale,
+                                        const float* in_shift, const float* bias, float* y, int B, int H, int W, int Cin,
+                                        int Cout, void* stream) {
+    TAG_CHECK_ARG(x && wpack && bias && y && in_scale && in_shift && B > 0 && H > 0);
+    if (!(conv_impl() == 0 && (W == 16 || W == 4) && (Cin == 32 || Cin == 128) && Cout == 128 && (prologue == 2 || prologue == 3))) {
+        tag_set_error("%s", "tag_conv3x3_forward_bias: unserved shape (W 16 | 4, Cin 32 | 128, Cout 128, prologue 2 | 3, halo-tile kernel)");
+        return TAG_EINVAL;
+    }
+    TAG_CHECK_ARG((long)B * H * W < (1L << 31) && (long)H * W * Cin * 4 < (1L << 32));
+    hipStream_t st = as_stream(stream);
+    if (W == 4) launch_halo_bias<4>(x, wpack, prologue, in_scale, in_shift, bias, y, B, H, W, Cin, Cout, st);
+    else launch_halo_bias<16>(x, wpack, prologue, in_scale, in_shift, bias, y, B, H, W, Cin, Cout, st);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
 // dgrad convolution + the reduction half of the BatchNorm+ReLU backward its output flows into (see the EPI == 1 epilogue).
 // Only the halo-tile kernel has it: widths 8/16/32/64 (tag_conv3x3_stats_rows > 0); other shapes use tag_conv3x3_forward +
 // tag_bnrelu_backward.
@@ -2418,6 +2516,24 @@ extern "C" int tag_conv3x3_c1_forward(const float* x, const float* col_scale, co
         hipLaunchKernelGGL(conv_c1_fwd_kernel, dim3((int)nb), dim3(256), 0, as_stream(stream), x, col_scale,
                            col_shift, w, y, M, H, W, Cout);
     }
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
+
+// y = conv(affine(x)) + bias[b, cout] of the Cin = 1 convolution (CrossCDur block 1): W % 4 == 0 and Cout in {4, 8, 16, 32, 64,
+// 128, ...} with 256 % (Cout / 4) == 0 (the 4-pixel kernel); anything else is TAG_EINVAL.
+extern "C" int tag_conv3x3_c1_forward_bias(const float* x, const float* col_scale, const float* col_shift, const float* w,
+                                           const float* bias, float* y, int B, int H, int W, int Cout, void* stream) {
+    TAG_CHECK_ARG(x && w && bias && y && B > 0 && H > 0 && (col_scale == nullptr) == (col_shift == nullptr));
+    if (!(W > 0 && W % 4 == 0 && Cout >= 4 && Cout % 4 == 0 && 256 % (Cout / 4) == 0)) {
+        tag_set_error("%s", "tag_conv3x3_c1_forward_bias: unserved shape (W a multiple of 4, Cout / 4 a divisor of 256)");
+        return TAG_EINVAL;
+    }
+    const long M = (long)B * H * W;
+    long nb = ((M / 4) * (Cout / 4) + 255) / 256;
+    if (nb > 8192) nb = 8192;
+    hipLaunchKernelGGL(conv_c1_fwd4_bias_kernel, dim3((int)nb), dim3(256), 0, as_stream(stream), x, col_scale, col_shift, w, bias,
+                       y, M, H, W, Cout);
     TAG_LAUNCH_CHECK();
     return 0;
 }

@@ -1099,6 +1099,77 @@ def frame_head_backward(y, rb, w, sig, dprob, T, dw_out=None, db_out=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# biased convs of the early-fusion CrossCDur (models/audio_text_model.py:461-568): the text is added to the RAW conv output,
+# leaky(conv(bn(x)) + t[b, c]), so the bias lives in the conv kernels' epilogue (fp32, direct kernels only)
+# ------------------------------------------------------------------------------------------------
+
+def _check_clip_bias(bias, B, Cout):
+    if bias.dim() != 2 or bias.shape[0] != B or bias.shape[1] != Cout:
+        raise RuntimeError(f"per-clip bias of shape {tuple(bias.shape)}, expected ({B}, {Cout})")
+
+
+def conv3x3_bias(x, wpack, Cout, prologue, scale, shift, bias):
+    """y = conv(prologue(x)) + bias[b, cout] of a channels-last x (B,H,W,Cin); wpack: the fp32 forward pack of pack_conv_weight.
+    A shape without an instance raises (TAG_EINVAL of tag_conv3x3_forward_bias)."""
+    B, H, W, Cin = x.shape
+    _check_clip_bias(bias, B, Cout)
+    if wpack.dtype != F32 or x.dtype != F32:
+        raise RuntimeError("conv3x3_bias: fp32 activations and the fp32 weight pack only")
+    y = _empty(B, H, W, Cout, like=x)
+    with _timed(("conv3x3_halo_kernel", B, H, W, Cin, Cout), 2.0 * B * H * W * 9 * Cin * Cout):
+        call("tag_conv3x3_forward_bias", ptr(x), ptr(wpack), prologue, ptr(scale), ptr(shift), ptr(bias), ptr(y), B, H, W, Cin,
+             Cout)
+    return y
+
+
+def conv3x3_c1_bias(x, w, col_scale, col_shift, bias):
+    """y = conv(affine(x)) + bias[b, cout] of the Cin = 1 convolution: x (B,H,W), w (Cout,1,3,3) -> (B,H,W,Cout)."""
+    B, H, W = x.shape
+    Cout = w.shape[0]
+    _check_clip_bias(bias, B, Cout)
+    y = _empty(B, H, W, Cout, like=x)
+    call("tag_conv3x3_c1_forward_bias", ptr(x), ptr(col_scale), ptr(col_shift), ptr(w), ptr(bias), ptr(y), B, H, W, Cout)
+    return y
+
+
+def lppool_leaky_backward_clip(y, dout, ph, pw, drop_p=0.0, seed=0):
+    """lppool_leaky_backward that also returns dt (B, C), the per-clip sums of dy, from the same pass."""
+    B, H, W, C = y.shape
+    dy, dt = torch.empty_like(y), _empty(B, C, like=y)
+    ws, clip = _clip_ws(B, C, y)
+    call("tag_lppool_leaky_backward_clip", ptr(y), ptr(dout), ptr(dy), ptr(dt), ptr(clip), B, H, W, C, ph, pw, float(drop_p), seed,
+         ptr(ws))
+    return dy, dt
+
+
+def bn_act_backward_clip(x, pre_op, st: BNStat, gamma, du, dg_out=None, db_out=None):
+    """bn_act_backward of a channels-last x (B,H,W,C) that also returns dt (B, C), the per-clip sums of dx, from its apply pass."""
+    B, C = x.shape[0], x.shape[-1]
+    rows = x.numel() // C
+    dx, dt = torch.empty_like(x), _empty(B, C, like=x)
+    dg = dg_out if dg_out is not None else _empty(C, like=x)
+    db = db_out if db_out is not None else _empty(C, like=x)
+    ws = _ws(query("tag_bn_backward_ws_bytes", rows, C), x)
+    wsc, clip = _clip_ws(B, C, x)
+    call("tag_bn_act_backward_clip", ptr(x), pre_op, ptr(st.mean), ptr(st.invstd), ptr(gamma), ptr(du), ptr(dx), ptr(dg), ptr(db),
+         ptr(dt), ptr(clip), B, rows // B, C, int(st.train), ptr(ws), ptr(wsc))
+    return dx, dg, db, dt
+
+
+def leaky_forward(z):
+    """leaky_relu(z, 0.1) of a contiguous fp32 tensor (numel % 4 == 0)."""
+    out = torch.empty_like(z)
+    call("tag_leaky_forward", ptr(z), ptr(out), z.numel())
+    return out
+
+
+def leaky_backward(z, dout):
+    dz = torch.empty_like(z)
+    call("tag_leaky_backward", ptr(z), ptr(dout), ptr(dz), z.numel())
+    return dz
+
+
+# ------------------------------------------------------------------------------------------------
 # optimiser step on flat buffers (O1)
 # ------------------------------------------------------------------------------------------------
 

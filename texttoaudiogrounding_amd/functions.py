@@ -21,7 +21,8 @@ from .dispatch import (BF16, BNStat, C1_BWD_FUSED_SHAPE, _sfx, _wino_u, act_bf16
                        gru_bidir_backward, gru_bidir_forward, logmel, lppool_leaky_backward, pack_conv_weight,
                        pool_sums_fusable, relu_backward)
 from .dispatch import (bias_bnrelu_backward, bias_bnrelu_forward, bias_bnrelu_pool, bias_bnrelu_pool_backward,
-                       frame_head_backward, frame_head_forward, gemm_bf16, rowgroup_bias_relu, rowgroup_colsum)
+                       bn_act_backward_clip, conv3x3_bias, conv3x3_c1_bias, frame_head_backward, frame_head_forward, gemm_bf16, leaky_backward,
+                       leaky_forward, lppool_leaky_backward_clip, rowgroup_bias_relu, rowgroup_colsum)
 
 # ------------------------------------------------------------------------------------------------
 # Cnn8Rnn: the whole audio encoder as one autograd node (rows F1-F3, A1-A4 forward + backward)
@@ -638,6 +639,222 @@ class CrnnFunction(TagFunction):
                 _deliver(grads, sk, k, grads[k])
         _ready(sv["params"])
         return (None, None, *grads)
+
+
+def check_cross_cdur_precision():
+    """CrossCDur runs in fp32 only: the biased conv epilogues exist for the fp32 direct kernels alone."""
+    if cfg.CONV_MATH != "fp32" or act_bf16() or gemm_bf16():
+        raise RuntimeError(f"CrossCDur supports fp32 arithmetic only (CONV_MATH 'fp32', fp32 activations and GEMMs); got "
+                           f"CONV_MATH {cfg.CONV_MATH!r}, ACT_DTYPE {cfg.ACT_DTYPE!r}, GEMM_MATH {cfg.GEMM_MATH!r}")
+
+
+def _clip_sums(dz):
+    """dt[b, c] = sum over (h, w) of a channels-last gradient dz (B,H,W,C): the gradient of a per-clip bias added to z."""
+    B, H, W, C = dz.shape
+    return rowgroup_colsum(dz.view(B * H * W, C), H * W)[0]
+
+
+class CrossCDurFunction(TagFunction):
+    """The early-fusion CrossCDur (models/audio_text_model.py:482-568) below its text encoder, as one autograd node: waveform
+    (B,S) -> frame_sim (B, T').  t1..t5 = block{i}.fc_text(e) (B, C_i), r = fc_text(e) (B, 256): differentiable inputs, so
+    autograd sums their six gradients into the text embedding.
+
+    params order: 5 x (bn.w, bn.b, conv.w) for block1..5, gru (w_ih, w_hh, b_ih, b_hh) x (fwd, reverse), fc_output.w,
+    fc_output.b.  CrnnFunction's layer plan with z_i = conv_i(bn_i(.)) + t_i[b, c] written by the biased conv kernels
+    (dispatch.conv3x3_c1_bias / conv3x3_bias) where CrnnFunction writes y_i: the forward has no extra pass over the activations.
+    The statistics of bn_{i+1} are taken over leaky(z_i), bias included.  Backward: dt_i = per-clip sums of dz_i, emitted by
+    the pass that writes dz_i (dispatch.*_backward_clip; 2 % of the step faster than a rowgroup_colsum pass over each dz,
+    docs/experiments_cross_cdur.md)."""
+
+    @staticmethod
+    def forward(ctx, waveform, mod, t1, t2, t3, t4, t5, r, *params):
+        check_cross_cdur_precision()
+        wave = _chk(waveform, "waveform")
+        check_pass_size(wave.shape[0], wave.shape[1] // mod.hop_length + 1)
+        training = mod.training
+        p = [_chk(t.detach(), "parameter") for t in params]
+        texts = [_chk(t.detach(), "text bias") for t in (t1, t2, t3, t4, t5)]
+        r_ = _chk(r.detach(), "fc_text")
+        blk = [p[3 * i: 3 * i + 3] for i in range(5)]
+        rnn = p[15:23]
+        wo, bo = p[23], p[24]
+        bns = mod._bn_modules()
+        drop = mod.dropout_p if training else 0.0
+        seed = new_seed() if training and drop > 0 else 0
+
+        lm = logmel(wave, mod.n_fft, mod.win_length, mod.hop_length, mod.window, mod.mel_fb)   # (B,F,64)
+        B, Fr, NM = lm.shape
+        for i, t in enumerate(texts + [r_]):
+            C = 2 * rnn[1].shape[1] if i == 5 else blk[i][2].shape[0]
+            if t.dim() != 2 or t.shape[0] != B or t.shape[1] != C:
+                raise RuntimeError(f"CrossCDur: text bias {i + 1} has shape {tuple(t.shape)}, expected ({B}, {C})")
+
+        def stats(x2d, i, pre_op):
+            return bn_stats(x2d, blk[i][0], blk[i][1], bns[i].running_mean, bns[i].running_var, training, bns[i].eps,
+                            bns[i].momentum, pre_op)
+
+        st = [None] * 5
+        st[0] = stats(lm.view(-1, 1), 0, 0)                       # BatchNorm2d(1): one scalar affine
+        cs, ct = st[0].scale.expand(NM).contiguous(), st[0].shift.expand(NM).contiguous()
+        z1 = conv3x3_c1_bias(lm, blk[0][2], cs, ct, texts[0])      # (B,F,64,32)
+        a1 = bnact_pool(z1, None, 2, 4, act=2, pool=1)            # leaky + LPPool -> (B,F/2,16,32)
+        st[1] = stats(a1.view(-1, a1.shape[3]), 1, 0)
+        wf1, wd1 = pack_conv_weight(blk[1][2], W=a1.shape[2])
+        z2 = conv3x3_bias(a1, wf1, 128, 3, st[1].scale, st[1].shift, texts[1])
+        st[2] = stats(z2.view(-1, 128), 2, 1)                     # over leaky(z2)
+        wf2, wd2 = pack_conv_weight(blk[2][2], W=z2.shape[2])
+        z3 = conv3x3_bias(z2, wf2, 128, 2, st[2].scale, st[2].shift, texts[2])
+        a3 = bnact_pool(z3, None, 2, 4, act=2, pool=1)            # (B,F/4,4,128)
+        st[3] = stats(a3.view(-1, 128), 3, 0)
+        wf3, wd3 = pack_conv_weight(blk[3][2], W=a3.shape[2])
+        z4 = conv3x3_bias(a3, wf3, 128, 3, st[3].scale, st[3].shift, texts[3])
+        st[4] = stats(z4.view(-1, 128), 4, 1)
+        wf4, wd4 = pack_conv_weight(blk[4][2], W=z4.shape[2])
+        z5 = conv3x3_bias(z4, wf4, 128, 2, st[4].scale, st[4].shift, texts[4])
+        a5 = bnact_pool(z5, None, 1, 4, act=2, pool=1, drop_p=drop, seed=seed)     # (B,T',1,128)
+        Bx, Tp = a5.shape[0], a5.shape[1]
+        x2d = a5.view(Bx * Tp, -1)
+        need_grad = any(ctx.needs_input_grad[2:])
+        y, gsave = gru_bidir_forward(x2d, rnn, Bx, Tp, need_grad)
+        y2d = y.reshape(Bx * Tp, -1)
+        prob, sig = frame_head_forward(y2d, r_, wo.reshape(-1), bo, Tp)
+        if need_grad:
+            ctx.saved = dict(lm=lm, cs=cs, ct=ct, st=st, z=[z1, z2, z3, z4, z5], pool=[a1, a3, a5], wd=[wd1, wd2, wd3, wd4],
+                             x2d=x2d, gsave=gsave, y=y2d, sig=sig, r=r_, p=p, drop=drop, seed=seed, sinks=_sinks(params),
+                             params=params if cfg.DIRECT_GRADS else None)
+        mod._last_dropout = dict(p=drop, seeds=[seed])
+        return prob.view(Bx, Tp)
+
+    @staticmethod
+    def backward(ctx, dprob):
+        sv = ctx.saved
+        ctx.saved = None
+        p, st, zs, pools, wd = sv["p"], sv["st"], sv["z"], sv["pool"], sv["wd"]
+        blk = [p[3 * i: 3 * i + 3] for i in range(5)]
+        need = ctx.needs_input_grad
+        need_t, need_p = need[2:8], need[8:]
+        grads: List[Optional[torch.Tensor]] = [None] * len(p)
+        dts: List[Optional[torch.Tensor]] = [None] * 5
+        sk = sv["sinks"]
+        dprob = _chk(dprob, "grad_output")
+        y2d = sv["y"]
+        Tp = pools[2].shape[1]
+        wo = p[23]
+        dyh, dwo, dbo, dr = frame_head_backward(y2d, sv["r"], wo.reshape(-1), sv["sig"], dprob.reshape(-1), Tp)
+        grads[23], grads[24] = dwo.view_as(wo), dbo
+        dx2d, grads[15:23] = gru_bidir_backward(dyh.view(y2d.shape[0] // Tp, Tp, -1), sv["x2d"], sv["gsave"], outs=sk[15:23])
+        z1, z2, z3, z4, z5 = zs
+        a1, a3, a5 = pools
+
+        def wgrad(k, x, dz, prologue, s):
+            if need_p[k]:                                      # a frozen conv weight: its weight-gradient conv is not launched
+                grads[k] = conv3x3_wgrad(x, dz, prologue=prologue, scale=s.scale, shift=s.shift, out=sk[k])
+
+        def pool_bwd(i, z, dout, ph, pw, drop_p=0.0, seed=0):
+            """dz_i of a pooled block and, when t_i takes a gradient, dt_i from the same pass."""
+            if need_t[i]:
+                dz, dts[i] = lppool_leaky_backward_clip(z, dout, ph, pw, drop_p, seed)
+                return dz
+            return lppool_leaky_backward(z, dout, ph, pw, drop_p, seed)
+
+        def bn_bwd(i, k, z, s, du):
+            """dz_i of a block whose output feeds a BatchNorm directly (leaky in the next conv's prologue), and dt_i."""
+            if need_t[i]:
+                dz, grads[k], grads[k + 1], dts[i] = bn_act_backward_clip(z, 1, s, blk[i + 1][0], du, dg_out=sk[k], db_out=sk[k + 1])
+            else:
+                dz, grads[k], grads[k + 1] = bn_act_backward(z, 1, s, blk[i + 1][0], du, dg_out=sk[k], db_out=sk[k + 1])
+            return dz
+
+        # block5: conv(bn(leaky(z4))) + t5
+        dz5 = pool_bwd(4, z5, dx2d.view(a5.shape), 1, 4, sv["drop"], sv["seed"])
+        wgrad(14, z4, dz5, 2, st[4])
+        du = conv3x3(dz5, wd[3], 128)
+        del dz5
+        dz4 = bn_bwd(3, 12, z4, st[4], du)
+        # block4: conv(bn(a3)) + t4
+        wgrad(11, a3, dz4, 3, st[3])
+        du = conv3x3(dz4, wd[2], 128)
+        del dz4
+        da3, grads[9], grads[10] = bn_act_backward(a3, 0, st[3], blk[3][0], du, dg_out=sk[9], db_out=sk[10])
+        dz3 = pool_bwd(2, z3, da3, 2, 4)
+        del da3
+        # block3
+        wgrad(8, z2, dz3, 2, st[2])
+        du = conv3x3(dz3, wd[1], 128)
+        del dz3
+        dz2 = bn_bwd(1, 6, z2, st[2], du)
+        # block2
+        wgrad(5, a1, dz2, 3, st[1])
+        du = conv3x3(dz2, wd[0], a1.shape[3])
+        del dz2
+        da1, grads[3], grads[4] = bn_act_backward(a1, 0, st[1], blk[1][0], du, dg_out=sk[3], db_out=sk[4])
+        dz1 = pool_bwd(0, z1, da1, 2, 4)
+        del da1, du
+        # block1: conv(bn_scalar(lm)) + t1
+        lm = sv["lm"]
+        if need_p[2]:
+            grads[2] = conv3x3_c1_wgrad(lm, dz1, sv["cs"], sv["ct"], out=sk[2])
+        if need_p[0] or need_p[1]:
+            du0 = conv3x3_c1_dgrad(dz1, blk[0][2])                                 # (B,F,64) grad wrt bn output
+            B, Fr, NM = lm.shape
+            st0c = BNStat()
+            st0c.mean, st0c.invstd = st[0].mean.expand(NM).contiguous(), st[0].invstd.expand(NM).contiguous()
+            dgc, dbc = bn_param_grad(lm.view(B * Fr, NM), du0.view(B * Fr, NM), st0c)
+            grads[0], grads[1] = dgc.sum().view(1), dbc.sum().view(1)               # 64 columns share one channel
+        for k in range(len(grads)):
+            if not need_p[k]:
+                grads[k] = None
+            elif grads[k] is not None:
+                _deliver(grads, sk, k, grads[k])
+        _ready(sv["params"])
+        return (None, None, *dts, dr if need_t[5] else None, *grads)
+
+
+class CDurTextBlockFunction(TagFunction):
+    """CDurTextBlock.forward on its own (models/audio_text_model.py:473-479): channels-last x (B,H,W,Cin), t = fc_text(text)
+    (B, Cout) -> leaky(conv(bn(x)) + t) (B,H,W,Cout); the launches of CrossCDurFunction's blocks plus a LeakyReLU pass.  ``bn``:
+    its running statistics are updated in train mode.  Cin = 1: no gradient for x (BatchNorm2d(1)'s input gradient has no kernel;
+    the block's input there is the spectrogram)."""
+
+    @staticmethod
+    def forward(ctx, x, t, bn, g, b, cw):
+        check_cross_cdur_precision()
+        x, t_ = _chk(x, "x"), _chk(t.detach(), "text bias")
+        g, b, cw = (_chk(v.detach(), "parameter") for v in (g, b, cw))
+        B, H, W, Cin = x.shape
+        Cout = cw.shape[0]
+        if Cin == 1 and ctx.needs_input_grad[0]:
+            raise RuntimeError("CDurTextBlock: the input gradient of the Cin = 1 block has no kernel")
+        st = bn_stats(x.view(-1, Cin), g, b, bn.running_mean, bn.running_var, bn.training, bn.eps, bn.momentum)
+        if Cin == 1:
+            cs, ct = st.scale.expand(W).contiguous(), st.shift.expand(W).contiguous()
+            z = conv3x3_c1_bias(x.view(B, H, W), cw, cs, ct, t_)
+            wd = None
+        else:
+            cs = ct = None
+            wf, wd = pack_conv_weight(cw, W=W)
+            z = conv3x3_bias(x, wf, Cout, 3, st.scale, st.shift, t_)
+        ctx.saved = (x, z, st, cs, ct, wd, g, cw)
+        return leaky_forward(z)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, z, st, cs, ct, wd, g, cw = ctx.saved
+        ctx.saved = None
+        B, H, W, Cin = x.shape
+        dz = leaky_backward(z, _chk(dout, "grad"))
+        dt = _clip_sums(dz)
+        if Cin == 1:
+            dcw = conv3x3_c1_wgrad(x.view(B, H, W), dz, cs, ct)
+            du0 = conv3x3_c1_dgrad(dz, cw)
+            stc = BNStat()
+            stc.mean, stc.invstd = st.mean.expand(W).contiguous(), st.invstd.expand(W).contiguous()
+            dgc, dbc = bn_param_grad(x.view(B * H, W), du0.view(B * H, W), stc)
+            return None, dt, None, dgc.sum().view(1), dbc.sum().view(1), dcw
+        dcw = conv3x3_wgrad(x, dz, prologue=3, scale=st.scale, shift=st.shift)
+        du = conv3x3(dz, wd, Cin)
+        dx, dg, db = bn_act_backward(x, 0, st, g, du)
+        return dx, dt, None, dg, db, dcw
 
 
 # ------------------------------------------------------------------------------------------------

@@ -58,6 +58,12 @@ _SIGS = {
     "tag_bn_stats_from_partials": (c_int, [P, c_int, c_int, P, P, c_float, c_float, P, P, P, P, P, P, P, P]),
     "tag_conv3x3_forward": (c_int, [P, P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "tag_conv3x3_dgrad_bnsums": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "tag_conv3x3_forward_bias": (c_int, [P, P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "tag_conv3x3_c1_forward_bias": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "tag_lppool_leaky_backward_clip": (c_int, [P] * 5 + [c_int] * 6 + [c_float, c_uint64, P, P]),
+    "tag_bn_act_backward_clip": (c_int, [P, c_int] + [P] * 9 + [c_int, c_long, c_int, c_int, P, P, P]),
+    "tag_leaky_forward": (c_int, [P, P, c_long, P]),
+    "tag_leaky_backward": (c_int, [P, P, P, c_long, P]),
     "tag_set_option": (c_int, [ctypes.c_char_p, c_int]),
     "tag_conv3x3_wino_ok": (c_int, [c_int] * 5),
     "tag_pack_conv_weight_wino": (c_int, [P, P, P, c_int, c_int, P]),

@@ -1,5 +1,5 @@
-"""Model composition (mirror of BiEncoder, models/audio_text_model.py:16-98 in the reference) and the early-fusion
-CrossCnn8_Rnn grounding model (models/audio_text_model.py:571-840)."""
+"""Model composition (mirror of BiEncoder, models/audio_text_model.py:16-98 in the reference) and the early-fusion grounding
+models CrossCnn8_Rnn (models/audio_text_model.py:571-840) and CrossCDur (models/audio_text_model.py:461-568)."""
 import sys
 from typing import Optional
 
@@ -8,9 +8,10 @@ import torch.nn as nn
 
 from .. import ops
 from .. import engine, torch_ops
-from .audio_encoder import _MelFrontendBuffers, slaney_mel_filterbank
+from .audio_encoder import _MelFrontendBuffers, htk_mel_filterbank, slaney_mel_filterbank
 from .augmentation import SpecAugmentation
 from .panns import init_bn, init_layer
+from .utils import init_weights
 
 
 class BiEncoder(nn.Module):
@@ -405,5 +406,117 @@ class CrossCnn8_Rnn(nn.Module):
         length = torch.div(length, self.interpolate_ratio, rounding_mode="floor")
         if self.interpolate_ratio != 1 and self.upsample:
             prob = ops.UpsampleLinearFunction.apply(prob.squeeze(2), self.interpolate_ratio).unsqueeze(2)
+            length = length * self.interpolate_ratio
+        return {"frame_sim": prob, "length": length}
+
+
+class CDurTextBlock(nn.Module):
+    """CDur block with the text added to the raw conv output (models/audio_text_model.py:461-479):
+    leaky_0.1(conv(bn(x)) + fc_text(text)[:, :, None, None]); the reference's submodules and state-dict keys (bn, conv without
+    bias, activation, fc_text).  Inside CrossCDur the whole-model node reads them; ``forward`` is the block on its own."""
+
+    def __init__(self, cin, cout, text_emb_dim, kernel_size=3, padding=1):
+        super().__init__()
+        if kernel_size != 3 or padding != 1:
+            raise ValueError("CDurTextBlock: the HIP conv kernels are 3x3 / pad 1")
+        self.bn = nn.BatchNorm2d(cin)
+        self.conv = nn.Conv2d(cin, cout, kernel_size, padding=padding, bias=False)
+        self.activation = nn.LeakyReLU(0.1, True)
+        self.fc_text = nn.Linear(text_emb_dim, cout)
+
+    def forward(self, x, text):
+        """x NCHW (B, Cin, T, F), text (B, text_emb_dim) -> (B, Cout, T, F).  Shapes: those the biased conv kernels serve
+        (Cin 1 with F a multiple of 4; Cin 32 | 128 -> Cout 128 with F 16 | 4)."""
+        t = ops.LinearFunction.apply(text, self.fc_text.weight, self.fc_text.bias)
+        if self.bn.training:
+            self.bn.num_batches_tracked += 1
+        xl = x.permute(0, 2, 3, 1).contiguous()                  # channels-last (plumbing copy)
+        y = ops.CDurTextBlockFunction.apply(xl, t, self.bn, self.bn.weight, self.bn.bias, self.conv.weight)
+        return y.permute(0, 3, 1, 2).contiguous()
+
+
+class CrossCDur(nn.Module):
+    """Early-fusion grounding model on the CDur CRNN (models/audio_text_model.py:482-568): the phrase embedding
+    e = text_encoder(...)["seq_emb"] enters every conv layer as a per-(clip, channel) bias on the raw conv output
+    (block{i}.fc_text(e)) and the GRU output (fc_text(e)); frame_sim (B, T') = clamp(sigmoid(fc_output(.)), 1e-7, 1), 2-D.
+    Same constructor, attributes, submodule names and state-dict keys as the reference (plus the two melspec buffers, as
+    CrnnEncoder).  Below the text encoder and the six text linears the model is ONE operator, tag::cross_cdur
+    (ops.CrossCDurFunction).  fp32 only.  The forward reads neither ``specaug`` nor ``mixup_lambda`` (the reference's does not).
+
+    Reference quirk, mirrored: the constructor ends with ``self.apply(init_weights)``, which runs over the text encoder too --
+    an nn.Embedding inside it is re-drawn (kaiming-uniform, models/utils.py:5-20), whatever its own constructor did."""
+
+    def __init__(self, sample_rate, text_encoder, upsample=False):
+        super().__init__()
+        self.text_encoder = text_encoder
+        self.n_fft = 2048
+        self.win_length = 40 * sample_rate // 1000
+        self.hop_length = 20 * sample_rate // 1000
+        if self.win_length > self.n_fft:
+            raise ValueError("win_length must not exceed n_fft=2048")
+        self.melspec_extractor = _MelFrontendBuffers(
+            torch.hann_window(self.win_length),
+            htk_mel_filterbank(self.n_fft // 2 + 1, 0.0, float(sample_rate // 2), 64, sample_rate))
+        self.text_emb_dim = text_encoder.embed_dim
+        self.block1 = CDurTextBlock(1, 32, self.text_emb_dim)
+        self.pool1 = nn.LPPool2d(4, (2, 4))
+        self.block2 = CDurTextBlock(32, 128, self.text_emb_dim)
+        self.block3 = CDurTextBlock(128, 128, self.text_emb_dim)
+        self.pool2 = nn.LPPool2d(4, (2, 4))
+        self.block4 = CDurTextBlock(128, 128, self.text_emb_dim)
+        self.block5 = CDurTextBlock(128, 128, self.text_emb_dim)
+        self.pool3 = nn.LPPool2d(4, (1, 4))
+        self.dropout = nn.Dropout(0.3)
+        self.dropout_p = 0.3
+        self.gru = nn.GRU(self.get_rnn_input_dim(), 128, bidirectional=True, batch_first=True)
+        self.fc_text = nn.Linear(self.text_emb_dim, 256)
+        self.fc_output = nn.Linear(256, 1)
+        self.apply(init_weights)
+        self.interpolate_ratio = 4
+        self.upsample = upsample
+
+    def get_rnn_input_dim(self):
+        """Channels x mel bins after the three pools (the reference probes it with a dummy forward): 128 x (64 // 64)."""
+        return self.block5.conv.out_channels * (64 // 4 // 4 // 4)
+
+    window = property(lambda self: self.melspec_extractor.spectrogram.window)
+    mel_fb = property(lambda self: self.melspec_extractor.mel_scale.fb)
+
+    def _blocks(self):
+        return [getattr(self, f"block{i}") for i in range(1, 6)]
+
+    def _bn_modules(self):
+        return [b.bn for b in self._blocks()]
+
+    def _flat_params(self):
+        ps = []
+        for b in self._blocks():
+            ps += [b.bn.weight, b.bn.bias, b.conv.weight]
+        for sfx in ("", "_reverse"):
+            ps += [getattr(self.gru, f"weight_ih_l0{sfx}"), getattr(self.gru, f"weight_hh_l0{sfx}"),
+                   getattr(self.gru, f"bias_ih_l0{sfx}"), getattr(self.gru, f"bias_hh_l0{sfx}")]
+        ps += [self.fc_output.weight, self.fc_output.bias]
+        return ps
+
+    def forward(self, input_dict):
+        ops.check_cross_cdur_precision()
+        waveform = input_dict["waveform"]
+        e = self.text_encoder(input_dict)["seq_emb"]
+        texts = [ops.LinearFunction.apply(e, b.fc_text.weight, b.fc_text.bias) for b in self._blocks()]
+        texts.append(ops.LinearFunction.apply(e, self.fc_text.weight, self.fc_text.bias))
+        if self.training:
+            ops.bump_bn_counters(self, self._bn_modules())
+        params = self._flat_params()
+        need = torch.is_grad_enabled() and any(t.requires_grad for t in list(params) + texts)
+        prev, engine._RECORDING = engine._RECORDING, torch.is_grad_enabled()
+        try:
+            prob = torch.ops.tag.cross_cdur(waveform, texts, params, torch_ops.encoder_token(self), need)
+        finally:
+            engine._RECORDING = prev
+            torch_ops._ENC_HANDOVER[0] = None
+        length = torch.div(torch.as_tensor(input_dict["waveform_len"]), self.hop_length, rounding_mode="floor") + 1
+        length = torch.div(length, self.interpolate_ratio, rounding_mode="floor")
+        if self.interpolate_ratio != 1 and self.upsample:
+            prob = ops.UpsampleLinearFunction.apply(prob, self.interpolate_ratio)
             length = length * self.interpolate_ratio
         return {"frame_sim": prob, "length": length}

@@ -509,6 +509,33 @@ def _cross_backward(ctx, dy):
 register_autograd("tag::cross_cnn8rnn", _cross_backward, setup_context=_cross_setup)
 
 
+@custom_op("tag::cross_cdur", mutates_args=())
+def cross_cdur(waveform: Tensor, texts: List[Tensor], params: List[Tensor], module_token: int, need_grad: bool) -> Tensor:
+    """CrossCDur.forward of models/audio_text_model.py:539-568 below its text encoder: waveform (B,S) -> frame_sim (B, T')
+    before the optional x4 upsampling.  texts = [block1..5.fc_text(e), fc_text(e)] (B, C); params in
+    CrossCDur._flat_params() order.  BatchNorm running statistics: module state, as tag::crnn_encoder."""
+    mod = _ENC_MODULES[module_token]
+    ctx = _EncCtx((False, False) + tuple(bool(need_grad and t.requires_grad) for t in list(texts) + list(params)))
+    y = ops.CrossCDurFunction.forward(ctx, waveform, mod, *texts, *params)
+    _ENC_HANDOVER[0] = (ops.CrossCDurFunction, ctx) if need_grad else None
+    return y
+
+
+@cross_cdur.register_fake
+def _(waveform, texts, params, module_token, need_grad):
+    mod = _ENC_MODULES[module_token]
+    return waveform.new_empty(waveform.shape[0], (waveform.shape[1] // mod.hop_length + 1) // mod.interpolate_ratio)
+
+
+def _cdur_backward(ctx, dy):
+    g = _enc_backward(ctx, dy)                # (None, [texts..., params...], None, ...)
+    flat = g[1]
+    return (None, flat[:6], flat[6:], None, None)
+
+
+register_autograd("tag::cross_cdur", _cdur_backward, setup_context=_enc_setup)
+
+
 def stage_to_device(t, device, dtype):
     """A small host table (stripes, mixup lambda) -> ``device`` through pinned memory, non-blocking (a pageable host->device
     copy waits for the stream to drain: the host would stall mid-step, runner.py stages the lengths the same way)."""
@@ -554,4 +581,4 @@ def _(frame_sim, thresholds, window_size, n_connect):
 OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_relu_pool", "conv3x3_bn_relu_pool_backward",
             "gru_bidir", "gru_bidir_backward", "embed_mean", "embed_mean_backward", "frame_match", "frame_match_backward",
             "align_dot", "align_dot_backward", "frame_bce", "frame_bce_backward", "segments", "cnn8rnn_encoder", "crnn_encoder",
-            "cross_cnn8rnn"]
+            "cross_cnn8rnn", "cross_cdur"]

@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
-"""Training step of the early-fusion CrossCnn8_Rnn against the BiEncoder (Cnn8Rnn + EmbeddingAgg(5221, 512) + DotProduct), both
-through StrongRunner.train_step at B x 10 s, fp32, dropout on, ALTERNATED in one process and timed with device events; plus one
-eval forward of each.  Prints one JSON object (median / spread / peak memory per model, the step ratio).
+"""Training step of an early-fusion model against its late-fusion twin, both through StrongRunner.train_step at B x 10 s, fp32,
+dropout on, ALTERNATED in one process and timed with device events; plus one eval forward of each.  Prints one JSON object
+(median / spread / peak memory per model, the step ratio).
 
-    python tools/cross_bench.py [--rounds 5] [--steps 10] [--B 64] [--out FILE.json]
+--model cnn8rnn (default): CrossCnn8_Rnn against BiEncoder(Cnn8Rnn + EmbeddingAgg(5221, 512) + DotProduct);
+--model cdur: CrossCDur(32000, EmbeddingAgg(5221, 256)) against BiEncoder(CrnnEncoder(32000, 256) + EmbeddingAgg(5221, 256) +
+ExpNegL2), the strong eg_config.
+
+    python tools/cross_bench.py [--model cnn8rnn|cdur] [--rounds 5] [--steps 10] [--B 64] [--out FILE.json]
+
+--device-batch stages the batch on the device once, as bench.py does; without it every step re-stages the host batch (82 MB of
+waveform at B = 64 x 10 s), which dominates the short CRNN steps.
 
 Per-kernel times: a separate profiler run with few steps, e.g.
     rocprofv3 --kernel-trace --stats -d OUT -o run -- python tools/cross_bench.py --rounds 1 --steps 2
@@ -21,6 +28,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import tag_oracle as O  # noqa: E402
 from texttoaudiogrounding_amd.models import audio_encoder, audio_text_model, match, text_encoder  # noqa: E402
 from texttoaudiogrounding_amd.runner import StrongRunner  # noqa: E402
+
+
+def clip_sum_bytes(B, frames=501):
+    """HBM bytes each per-clip bias-gradient pass of CrossCDur reads at B clips of `frames` frames, fp32: dz of block 1 to 5."""
+    f2, f4 = frames // 2, frames // 4
+    return {"rowgroup_colsum": [B * h * w * c * 4 for h, w, c in ((frames, 64, 32), (f2, 16, 128), (f2, 16, 128), (f4, 4, 128),
+                                                                  (f4, 4, 128))]}
 
 
 def pass_bytes(B, frames=1001):
@@ -41,23 +55,35 @@ def pass_bytes(B, frames=1001):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=["cnn8rnn", "cdur"], default="cnn8rnn")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--B", type=int, default=64)
     ap.add_argument("--out", default=None)
     ap.add_argument("--bytes", action="store_true")
+    ap.add_argument("--device-batch", action="store_true",
+                    help="stage the batch on the device once (as bench.py does) instead of re-staging the host batch every step")
     a = ap.parse_args()
     if a.bytes:
-        print(json.dumps(pass_bytes(a.B)))
+        print(json.dumps(clip_sum_bytes(a.B) if a.model == "cdur" else pass_bytes(a.B)))
         return
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    bi = audio_text_model.BiEncoder(audio_encoder.Cnn8Rnn(32000), text_encoder.EmbeddingAgg(5221, 512), match.DotProduct(), 512)
-    cross = audio_text_model.CrossCnn8_Rnn(32000, text_encoder.EmbeddingAgg(5221, 512))
+    if a.model == "cdur":
+        bi = audio_text_model.BiEncoder(audio_encoder.CrnnEncoder(32000, 256), text_encoder.EmbeddingAgg(5221, 256),
+                                        match.ExpNegL2(), 256)
+        cross = audio_text_model.CrossCDur(32000, text_encoder.EmbeddingAgg(5221, 256))
+        hop, T = 640, 125
+    else:
+        bi = audio_text_model.BiEncoder(audio_encoder.Cnn8Rnn(32000), text_encoder.EmbeddingAgg(5221, 512), match.DotProduct(), 512)
+        cross = audio_text_model.CrossCnn8_Rnn(32000, text_encoder.EmbeddingAgg(5221, 512))
+        hop, T = 320, 250
     runners = {"biencoder": StrongRunner(bi, device=dev), "cross": StrongRunner(cross, device=dev)}
-    b = O.synthetic_batch(a.B, 320000, seed=99, ragged=True)
-    T = 250
+    b = O.synthetic_batch(a.B, 320000, seed=99, ragged=True, hop=hop)
     b["label"] = (torch.rand(a.B, T, generator=torch.Generator().manual_seed(1)) > 0.7).float()
+
+    if a.device_batch:
+        b = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in b.items()}
 
     def step(name):
         return runners[name].train_step({k: (v.clone() if torch.is_tensor(v) else v) for k, v in b.items()})
@@ -97,7 +123,7 @@ def main():
     res = {n: {"step_ms_median": float(np.median(t)), "step_ms_min": float(np.min(t)), "step_ms_max": float(np.max(t)),
                "peak_alloc_gib": peak[n] / 2 ** 30, "eval_forward_ms": ev[n]} for n, t in times.items()}
     res["ratio_cross_over_biencoder"] = res["cross"]["step_ms_median"] / res["biencoder"]["step_ms_median"]
-    res["config"] = {"B": a.B, "seconds": 10, "rounds": a.rounds, "steps": a.steps}
+    res["config"] = {"model": a.model, "device_batch": a.device_batch, "B": a.B, "seconds": 10, "rounds": a.rounds, "steps": a.steps}
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
