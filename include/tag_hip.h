@@ -752,6 +752,44 @@ int tag_bn_act_backward_clip(const float* x, int pre_op, const float* mean, cons
 int tag_leaky_forward(const float* z, float* out, long n, void* stream);
 int tag_leaky_backward(const float* z, const float* dout, float* dz, long n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The class-mapping baseline AudioTagging (models/audio_text_model.py:405-458): encoder -> fc_output -> sigmoid -> pooling
+ * over time, trained with ClipBceLoss / MaskedFrameBceLoss / ClipMaskedFrameBceLoss (losses.py:38-43, 157-183).  The three
+ * products of the head are tag_gemm (act 5 = sigmoid for logits -> prob) and the bias gradient is tag_colsum; the passes
+ * below are fp32 on the native (B, T, C) layout, classes innermost, any C and T (rows need 4-byte alignment only): the lanes
+ * of a wave run over the classes, workgroups over (clip, class tile[, frame slab]).  Sums over frames are folded in a fixed
+ * order (no atomics): bitwise repeatable.  length: int64 (B); frames t >= min(length[b], T) are outside every reduction.
+ *   tag_class_pool_forward        clip (B, C) = *_with_lens(prob, length) (models/utils.py:49-84); mode 0 mean | 1 max |
+ *                                 2 linear_softmax sum p^2 / sum p | 3 exp_softmax sum e^p p / sum e^p (p in [0, 1]: no
+ *                                 stabiliser, equal to the reference's max-subtracted form to rounding).  aux (B, C) is what
+ *                                 the backward needs: 2: sum p; 3: sum e^p; 1: index of the FIRST maximum, as a float; 0: zero
+ *   tag_tagging_head_backward     dlogit (B, T, C) = (dprob + dclip * d clip / d prob) * prob * (1 - prob) in one pass:
+ *                                 the pooling term (0: 1 / len; 1: 1 at the stored index; 2: (2 p - clip) / sum p;
+ *                                 3: e^p / sum e^p * (1 + p - clip)) is zero outside the valid frames.  dprob (B, ld_dprob, C)
+ *                                 with ld_dprob >= T frames per clip, or null; dclip (B, C) or null; dlogit may BE dprob
+ *                                 (then ld_dprob == T)
+ *   tag_masked_frame_bce_forward  MaskedFrameBceLoss (losses.py:157-170): loss[0] = sum(bce * len_mask * cls_mask) /
+ *                                 sum(len_mask * cls_mask) over the first Tt frames, len_mask from clamp(length, 1, Tt),
+ *                                 cls_mask (B, C) or null = all ones (an all-zero mask gives the reference's 0 / 0).  BCE as
+ *                                 tag_frame_bce_*: logs clamped at -100.  prob (B, ld_t, C), label (B, ld_label_t, C) with
+ *                                 ld_t, ld_label_t >= Tt FRAMES PER CLIP (views truncated in time need no copy).  fp64
+ *                                 partials, one per workgroup, folded in a fixed order
+ *   tag_masked_frame_bce_backward dprob (B, Tt, C), contiguous: dloss[0] / den * cls_mask * (p - y) / max(p (1 - p), 1e-12),
+ *                                 zero where masked
+ *   ws of both: tag_masked_frame_bce_ws_bytes(B, Tt, C) bytes.
+ */
+int tag_class_pool_forward(const float* prob, const int64_t* length, float* clip, float* aux, int B, int T, int C, int mode,
+                           void* stream);
+int tag_tagging_head_backward(const float* prob, const float* dprob, const float* dclip, const float* clip, const float* aux,
+                              const int64_t* length, float* dlogit, int B, int T, int C, int mode, int ld_dprob,
+                              void* stream);
+size_t tag_masked_frame_bce_ws_bytes(int B, int Tt, int C);
+int tag_masked_frame_bce_forward(const float* prob, int ld_t, const float* label, int ld_label_t, const int64_t* length,
+                                 const float* cls_mask, int B, int Tt, int C, float* loss, void* ws, void* stream);
+int tag_masked_frame_bce_backward(const float* prob, int ld_t, const float* label, int ld_label_t, const int64_t* length,
+                                  const float* cls_mask, int B, int Tt, int C, const float* dloss, float* dprob, void* ws,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

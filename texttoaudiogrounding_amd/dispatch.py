@@ -976,6 +976,73 @@ def frame_bce_backward(sim, label, length, Tt, dloss):
     return ds
 
 
+# ---- AudioTagging head (csrc/tagging.hip): (B, T, C) passes with the classes innermost ----
+def class_pool_forward(prob, length, mode):
+    """*_with_lens pooling of prob (B,T,C) over the frames < length[b] -> clip (B,C), aux (B,C) (what the backward needs)."""
+    p = _chk(prob, "frame_sim")
+    B, T, C = p.shape
+    clip, aux = _empty(B, C, like=p), _empty(B, C, like=p)
+    call("tag_class_pool_forward", ptr(p), ptr(length), ptr(clip), ptr(aux), B, T, C, int(mode))
+    return clip, aux
+
+
+def tagging_head_dlogit(prob, dprob, dclip, clip, aux, length, mode, out=None):
+    """dlogit (B,T,C) = (dprob + dclip * d clip / d prob) * prob (1 - prob); dprob / dclip may be None; out may be dprob."""
+    p = _chk(prob, "frame_sim")
+    B, T, C = p.shape
+    dp = _chk(dprob, "grad") if dprob is not None else None
+    dc = _chk(dclip, "grad") if dclip is not None else None
+    out = out if out is not None else torch.empty_like(p)
+    call("tag_tagging_head_backward", ptr(p), ptr(dp), ptr(dc), ptr(clip), ptr(aux), ptr(length), ptr(out), B, T, C, int(mode),
+         T)
+    return out
+
+
+def _frames_per_clip(t, name):
+    """(B,Tt,C) fp32 device tensor, possibly a view truncated in time -> (tensor, frames per clip of its buffer); anything
+    else strided is made contiguous."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a tensor on the MI355X (cuda) device, got {t.device}; "
+                           "the HIP path has no CPU fallback")
+    if t.dtype != F32:
+        raise RuntimeError(f"{name}: expected float32, got {t.dtype}")
+    B, Tt, C = t.shape
+    s0, s1, s2 = t.stride()
+    if (C == 1 or s2 == 1) and (Tt == 1 or s1 == C) and (B == 1 or (s0 % C == 0 and s0 >= Tt * C)):
+        return t, (s0 // C if B > 1 else Tt)
+    return t.contiguous(), Tt
+
+
+def _masked_bce_args(prob, label, length, cls_mask):
+    p, ld_p = _frames_per_clip(prob, "frame_sim")
+    y, ld_y = _frames_per_clip(label, "strong_label")
+    if y.shape != p.shape:
+        raise RuntimeError(f"frame_sim {tuple(p.shape)} and strong_label {tuple(y.shape)} must be aligned first "
+                           "(ClassMappingRunner.forward does it)")
+    B, Tt, C = p.shape
+    m = _chk(cls_mask, "strong_label_mask") if cls_mask is not None else None
+    if m is not None and tuple(m.shape) != (B, C):
+        raise RuntimeError(f"strong_label_mask: expected {(B, C)}, got {tuple(m.shape)}")
+    ws = _ws(query("tag_masked_frame_bce_ws_bytes", B, Tt, C), p)
+    return p, ld_p, y, ld_y, m, B, Tt, C, ws
+
+
+def masked_frame_bce_forward(prob, label, length, cls_mask=None):
+    """MaskedFrameBceLoss (losses.py:157-170) on prob / label (B,Tt,C), clamp(length, 1, Tt), cls_mask (B,C) -> 0-dim loss."""
+    p, ld_p, y, ld_y, m, B, Tt, C, ws = _masked_bce_args(prob, label, length, cls_mask)
+    loss = _empty(1, like=p)
+    call("tag_masked_frame_bce_forward", ptr(p), ld_p, ptr(y), ld_y, ptr(length), ptr(m), B, Tt, C, ptr(loss), ptr(ws))
+    return loss.view(())
+
+
+def masked_frame_bce_backward(prob, label, length, cls_mask, dloss):
+    p, ld_p, y, ld_y, m, B, Tt, C, ws = _masked_bce_args(prob, label, length, cls_mask)
+    dp = _empty(B, Tt, C, like=p)
+    call("tag_masked_frame_bce_backward", ptr(p), ld_p, ptr(y), ld_y, ptr(length), ptr(m), B, Tt, C,
+         ptr(_chk(dloss.reshape(1), "grad")), ptr(dp), ptr(ws))
+    return dp
+
+
 def _l2norm_rows(x, rows, D):
     y = torch.empty_like(x)
     call("tag_l2norm_rows_forward", ptr(x), ptr(y), rows, D)

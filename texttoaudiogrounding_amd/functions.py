@@ -23,6 +23,7 @@ from .dispatch import (BF16, BNStat, C1_BWD_FUSED_SHAPE, _sfx, _wino_u, act_bf16
 from .dispatch import (bias_bnrelu_backward, bias_bnrelu_forward, bias_bnrelu_pool, bias_bnrelu_pool_backward,
                        bn_act_backward_clip, conv3x3_bias, conv3x3_c1_bias, frame_head_backward, frame_head_forward, gemm_bf16, leaky_backward,
                        leaky_forward, lppool_leaky_backward_clip, rowgroup_bias_relu, rowgroup_colsum)
+from .dispatch import class_pool_forward, tagging_head_dlogit
 
 # ------------------------------------------------------------------------------------------------
 # Cnn8Rnn: the whole audio encoder as one autograd node (rows F1-F3, A1-A4 forward + backward)
@@ -1314,6 +1315,75 @@ class SimPoolFunction(TagFunction):
 
 POOL_MODES = {"mean": 0, "max": 1, "linear_softmax": 2, "exp_softmax": 3}
 TEXT_MODES = {"mean": 0, "sum": 1, "max": 2, "mean_sum": 3}
+
+
+def check_tagging_precision(embedding):
+    """The AudioTagging head's passes are fp32: it runs behind the encoder in every mode that hands over an fp32 embedding
+    (the GEMMs follow GEMM_MATH like every other linear); anything else is refused before any launch."""
+    if embedding.dtype != F32:
+        raise RuntimeError(f"AudioTagging: the head takes an fp32 embedding, the encoder handed over {embedding.dtype} "
+                           f"(CONV_MATH {cfg.CONV_MATH!r}, ACT_DTYPE {cfg.ACT_DTYPE!r}, GEMM_MATH {cfg.GEMM_MATH!r})")
+
+
+def tagging_head_forward(embedding, weight, bias, length, mode):
+    """AudioTagging.forward below the encoder (models/audio_text_model.py:441-453): sigmoid(fc_output(embedding)) and its
+    pooling over the valid frames -> frame_sim (B,T,C), clip_sim (B,C), aux (B,C)."""
+    x = _chk(embedding, "embedding")
+    B, T, E = x.shape
+    w, b = _chk(weight, "weight"), _chk(bias, "bias")
+    C = w.shape[0]
+    if tuple(w.shape) != (C, E) or tuple(b.shape) != (C,):
+        raise RuntimeError(f"tagging head: weight {tuple(w.shape)} / bias {tuple(b.shape)} do not fit an embedding of {E}")
+    prob = gemm(x.view(B * T, E), w, B * T, C, E, transB=True, bias=b, act=5).view(B, T, C)
+    clip, aux = class_pool_forward(prob, length, mode)
+    return prob, clip, aux
+
+
+def tagging_head_backward(embedding, weight, prob, clip, aux, length, mode, dprob, dclip, need=(True, True, True),
+                          outs=(None, None)):
+    """-> (dembedding, dweight, dbias), None where ``need`` is off; outs: where dweight / dbias are written (or None)."""
+    B, T, E = embedding.shape
+    C = weight.shape[0]
+    M = B * T
+    dlogit = tagging_head_dlogit(prob, dprob, dclip, clip, aux, length, mode).view(M, C)
+    x2 = embedding.view(M, E)
+    dx = gemm(dlogit, weight, M, E, C).view(B, T, E) if need[0] else None
+    dw = gemm(dlogit, x2, C, E, M, transA=True, lda=C, out=outs[0]) if need[1] else None
+    db = colsum(dlogit, M, C, out=outs[1]) if need[2] else None
+    return dx, dw, db
+
+
+class TaggingHeadFunction(TagFunction):
+    """The AudioTagging head as one node: embedding (B,T,E), fc_output.weight (C,E), fc_output.bias (C), length (B) int64,
+    mode (POOL_MODES) -> frame_sim (B,T,C), clip_sim (B,C).  Saves prob, clip, aux; parameter gradients go through the
+    direct-gradient sinks like LinearFunction's."""
+
+    @staticmethod
+    def forward(ctx, embedding, weight, bias, length, mode):
+        x = _chk(embedding, "embedding")
+        w_, b_ = _chk(weight.detach(), "weight"), _chk(bias.detach(), "bias")
+        prob, clip, aux = tagging_head_forward(x, w_, b_, length, mode)
+        ctx.save_for_backward(x, w_, prob, clip, aux, length)
+        ctx.mode = mode
+        ctx.set_materialize_grads(False)          # an unused output arrives as None, not as a 34 MB zero fill
+        ctx.sinks = _sinks([embedding, weight, bias])
+        ctx.params = [weight, bias] if cfg.DIRECT_GRADS else None
+        return prob, clip
+
+    @staticmethod
+    def backward(ctx, dprob, dclip):
+        x, w, prob, clip, aux, length = ctx.saved_tensors
+        sk = ctx.sinks
+        need = tuple(ctx.needs_input_grad[:3])
+        dx, dw, db = tagging_head_backward(x, w, prob, clip, aux, length, ctx.mode, dprob, dclip, need,
+                                           (sk[1] if need[1] else None, sk[2] if need[2] else None))
+        g = [dx, None, None, None, None]
+        if need[1]:
+            _deliver(g, sk, 1, dw)
+        if need[2]:
+            _deliver(g, sk, 2, db)
+        _ready(ctx.params)
+        return tuple(g)
 
 
 class MaxMarginFunction(TagFunction):

@@ -188,6 +188,11 @@ _SIGS = {
     "tag_sumsq_ws_bytes": (c_size_t, [c_long]),
     "tag_sumsq": (c_int, [P, c_long, P, P, P]),
     "tag_adam_step": (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_int, P, c_float, c_float, P]),
+    "tag_class_pool_forward": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "tag_tagging_head_backward": (c_int, [P] * 7 + [c_int] * 5 + [P]),
+    "tag_masked_frame_bce_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "tag_masked_frame_bce_forward": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, P, P]),
+    "tag_masked_frame_bce_backward": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, P, P, P]),
 }
 
 _lib = None

@@ -69,3 +69,31 @@ class ClipFrameBceLoss(nn.Module):
         frame = torch.ops.tag.frame_bce(fs2.contiguous(), lab2, length, T)
         clip = self.clip_loss_fn.forward_tensor(output[self.clip_prob_key], output[self.clip_label_key])
         return (1 - self.frame_weight) * clip + self.frame_weight * frame
+
+
+class MaskedFrameBceLoss(nn.Module):
+    """losses.py:157-170 in the reference, for the class-mapping baseline: frame BCE over frame_sim / strong_label (B,T,C),
+    masked by the clip lengths and by strong_label_mask (B,C): sum(bce * len_mask * cls_mask) / sum(len_mask * cls_mask).
+    The reference is defined when max(length) == T; here every length in [1, T] is served.  One pass over the native
+    layout (tag_masked_frame_bce_*); frame_sim / strong_label truncated in time by the runner are read as views."""
+
+    def forward(self, output: Dict):
+        fs = output["frame_sim"]
+        lab = output["strong_label"].to(fs.device).float()
+        mask = output["strong_label_mask"].to(fs.device).float().contiguous()
+        length = torch.as_tensor(output["length"]).long().to(fs.device).contiguous()
+        return torch.ops.tag.masked_frame_bce(fs, lab, length, mask)
+
+
+class ClipMaskedFrameBceLoss(nn.Module):
+    """losses.py:173-183 in the reference: (1 - w) * ClipBceLoss(clip_sim, weak_label) + w * MaskedFrameBceLoss."""
+
+    def __init__(self, frame_weight):
+        super().__init__()
+        self.clip_loss_fn = ClipBceLoss()
+        self.frame_loss_fn = MaskedFrameBceLoss()
+        self.frame_weight = frame_weight
+
+    def forward(self, output: Dict):
+        return (1 - self.frame_weight) * self.clip_loss_fn.forward_tensor(output["clip_sim"], output["weak_label"]) + \
+            self.frame_weight * self.frame_loss_fn(output)

@@ -1,5 +1,6 @@
 """Model composition (mirror of BiEncoder, models/audio_text_model.py:16-98 in the reference) and the early-fusion grounding
-models CrossCnn8_Rnn (models/audio_text_model.py:571-840) and CrossCDur (models/audio_text_model.py:461-568)."""
+models CrossCnn8_Rnn (models/audio_text_model.py:571-840) and CrossCDur (models/audio_text_model.py:461-568), and the
+class-mapping baseline AudioTagging (models/audio_text_model.py:405-458)."""
 import sys
 from typing import Optional
 
@@ -520,3 +521,47 @@ class CrossCDur(nn.Module):
             prob = ops.UpsampleLinearFunction.apply(prob, self.interpolate_ratio)
             length = length * self.interpolate_ratio
         return {"frame_sim": prob, "length": length}
+
+
+class AudioTagging(nn.Module):
+    """The class-mapping baseline (mirror of models/audio_text_model.py:405-458 in the reference; trained by
+    python_scripts/training/mapping_to_class/run_strong.py / run_weak.py): phrases are mapped to a fixed set of sound
+    classes, the audio encoder is followed by fc_output + sigmoid, and the frame probabilities (B,T',C) are pooled over
+    the valid frames into clip probabilities (B,C).  Also the shape of the tagging checkpoints the encoders are
+    pre-trained from (``backbone.*`` keys).  Below the encoder the forward is ONE node (ops.TaggingHeadFunction: the
+    GEMM with the sigmoid in its epilogue, then a class-innermost pooling pass); no clamp on the sigmoid, as in the
+    reference."""
+
+    def __init__(self, audio_encoder, classes_num, pooling="linear_softmax"):
+        super().__init__()
+        self.backbone = audio_encoder
+        self.fc_output = nn.Linear(audio_encoder.embed_dim, classes_num)
+        self.pooling = pooling
+
+    def load_pretrained(self, pretrained, output_fn, training=True, cnn_only=False):
+        if isinstance(pretrained, dict):
+            state_dict = pretrained
+        else:
+            state_dict = torch.load(pretrained, map_location="cpu")
+        if "model" in state_dict:
+            state_dict = state_dict["model"]
+        model_dict = self.state_dict()
+        pretrained_dict = {k: v for k, v in state_dict.items() if (k in model_dict) and (model_dict[k].shape == v.shape)}
+        if cnn_only and training:
+            pretrained_dict = {k: v for k, v in pretrained_dict.items()
+                               if not k.startswith(("backbone.rnn", "backbone.fc1", "fc_output"))}
+        output_fn(f"Loading pretrained keys {pretrained_dict.keys()}")
+        model_dict.update(pretrained_dict)
+        self.load_state_dict(model_dict, strict=True)
+
+    def forward(self, input_dict):
+        if self.pooling not in ops.POOL_MODES:
+            raise Exception(f"Unsupported pooling {self.pooling}")
+        output = self.backbone(input_dict)
+        embedding = output["embedding"]
+        ops.check_tagging_precision(embedding)
+        length = output["length"]
+        len_dev = torch.as_tensor(length).long().to(embedding.device).contiguous()
+        prob, clip_prob = ops.TaggingHeadFunction.apply(embedding, self.fc_output.weight, self.fc_output.bias, len_dev,
+                                                        ops.POOL_MODES[self.pooling])
+        return {"frame_sim": prob, "clip_sim": clip_prob, "length": length}

@@ -15,7 +15,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .losses import FrameBceLoss
+from .losses import ClipMaskedFrameBceLoss, FrameBceLoss
 from .utils.train_util import init_obj_from_str
 
 
@@ -256,7 +256,8 @@ class StrongRunner:
         ops.SEED_RANK = self.rank
 
     # Runner.forward (run_strong.py:92-120)
-    def forward(self, batch: Dict, training: bool = True):
+    def _stage(self, batch: Dict):
+        """Moves the batch's tensors to the device, in place (Runner.forward, run_strong.py:94-101)."""
         for k, v in batch.items():
             if k in ("waveform_len", "text_len"):
                 # small integer arrays: staged through pinned memory so that no copy blocks the host mid-step (a
@@ -268,6 +269,9 @@ class StrongRunner:
                 batch[k] = v.long()
             elif isinstance(v, torch.Tensor):
                 batch[k] = v.long().to(self.device) if k == "text" else v.float().to(self.device)
+
+    def forward(self, batch: Dict, training: bool = True):
+        self._stage(batch)
         input_dict = {"specaug": False}
         input_dict.update(batch)
         output = self.model(input_dict)
@@ -319,6 +323,36 @@ class StrongRunner:
         v = float(loss.item())
         ops.check_async_errors()
         return v
+
+
+class ClassMappingRunner(StrongRunner):
+    """Training-step driver of the class-mapping baseline (Runner.forward of python_scripts/training/mapping_to_class/
+    run_strong.py:89-116, and run_weak.py for ``label``-only batches): AudioTagging + a loss that reads the output dict
+    (ClipMaskedFrameBceLoss, MaskedFrameBceLoss, ClipBceLoss).  Flat parameters, direct gradients, clip + Adam and the
+    gradient buckets are StrongRunner's."""
+
+    def __init__(self, model, loss_fn=None, **kwargs):
+        super().__init__(model, **kwargs)
+        self.loss_fn = loss_fn if loss_fn is not None else ClipMaskedFrameBceLoss(0.5)
+
+    def forward(self, batch: Dict, training: bool = True):
+        self._stage(batch)
+        input_dict = {"specaug": False}
+        input_dict.update(batch)
+        output = self.model(input_dict)
+        if training:
+            output.update(batch)
+            if "strong_label" in batch:
+                strong_label, frame_sim = batch["strong_label"], output["frame_sim"]
+                tt = min(frame_sim.size(1), strong_label.size(1))
+                # views: the masked BCE kernels take the frames per clip of each buffer, nothing is copied
+                if frame_sim.size(1) != tt:
+                    frame_sim = frame_sim[:, :tt, :]
+                if strong_label.size(1) != tt:
+                    strong_label = strong_label[:, :tt, :]
+                output.update({"frame_sim": frame_sim, "strong_label": strong_label,
+                               "length": torch.clamp(output["length"], 1, tt)})
+        return output
 
 
 def init_distributed(backend: Optional[str] = None):

@@ -358,6 +358,88 @@ def _bce_backward(ctx, dloss):
 register_autograd("tag::frame_bce", _bce_backward, setup_context=_bce_setup)
 
 
+# ------------------------------------------------------------------------------------------------ AudioTagging head + masked BCE
+@custom_op("tag::tagging_head", mutates_args=())
+def tagging_head(embedding: Tensor, weight: Tensor, bias: Tensor, length: Tensor, mode: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """AudioTagging.forward below the encoder (models/audio_text_model.py:441-453): sigmoid(embedding @ weight^T + bias)
+    (B,T,C), its pooling over the frames < length[b] (mode: ops.POOL_MODES) (B,C), and aux (B,C) for the backward."""
+    return ops.tagging_head_forward(embedding, weight, bias, length, mode)
+
+
+@tagging_head.register_fake
+def _(embedding, weight, bias, length, mode):
+    B, T, _ = embedding.shape
+    C = weight.shape[0]
+    return embedding.new_empty(B, T, C), embedding.new_empty(B, C), embedding.new_empty(B, C)
+
+
+@custom_op("tag::tagging_head_backward", mutates_args=())
+def tagging_head_backward(embedding: Tensor, weight: Tensor, prob: Tensor, clip: Tensor, aux: Tensor, length: Tensor, mode: int,
+                          dprob: Optional[Tensor], dclip: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (dembedding, dweight, dbias)."""
+    return ops.tagging_head_backward(embedding.contiguous(), weight.contiguous(), prob, clip, aux, length, mode, dprob, dclip)
+
+
+@tagging_head_backward.register_fake
+def _(embedding, weight, prob, clip, aux, length, mode, dprob, dclip):
+    return torch.empty_like(embedding), torch.empty_like(weight), weight.new_empty(weight.shape[0])
+
+
+def _taghead_setup(ctx, inputs, output):
+    embedding, weight, _bias, length, mode = inputs
+    prob, clip, aux = output
+    ctx.save_for_backward(embedding, weight, prob, clip, aux, length)
+    ctx.mode = mode
+    ctx.set_materialize_grads(False)
+
+
+def _taghead_backward(ctx, dprob, dclip, _daux):
+    embedding, weight, prob, clip, aux, length = ctx.saved_tensors
+    if dprob is None and dclip is None:
+        return None, None, None, None, None
+    dx, dw, db = torch.ops.tag.tagging_head_backward(embedding, weight, prob, clip, aux, length, ctx.mode, dprob, dclip)
+    return dx, dw, db, None, None
+
+
+register_autograd("tag::tagging_head", _taghead_backward, setup_context=_taghead_setup)
+
+
+@custom_op("tag::masked_frame_bce", mutates_args=())
+def masked_frame_bce(frame_sim: Tensor, label: Tensor, length: Tensor, cls_mask: Optional[Tensor]) -> Tensor:
+    """MaskedFrameBceLoss (losses.py:157-170) over frame_sim / label (B,Tt,C) (views truncated in time are read in place),
+    frames < clamp(length, 1, Tt), classes weighted by cls_mask (B,C) (None = all ones): -> 0-dim loss."""
+    return ops.masked_frame_bce_forward(frame_sim, label, length, cls_mask)
+
+
+@masked_frame_bce.register_fake
+def _(frame_sim, label, length, cls_mask):
+    return frame_sim.new_empty(())
+
+
+@custom_op("tag::masked_frame_bce_backward", mutates_args=())
+def masked_frame_bce_backward(frame_sim: Tensor, label: Tensor, length: Tensor, cls_mask: Optional[Tensor],
+                              dloss: Tensor) -> Tensor:
+    return ops.masked_frame_bce_backward(frame_sim, label, length, cls_mask, dloss)
+
+
+@masked_frame_bce_backward.register_fake
+def _(frame_sim, label, length, cls_mask, dloss):
+    return frame_sim.new_empty(frame_sim.shape)
+
+
+def _mbce_setup(ctx, inputs, output):
+    frame_sim, label, length, cls_mask = inputs
+    ctx.save_for_backward(frame_sim, label, length, cls_mask)
+
+
+def _mbce_backward(ctx, dloss):
+    frame_sim, label, length, cls_mask = ctx.saved_tensors
+    return torch.ops.tag.masked_frame_bce_backward(frame_sim, label, length, cls_mask, dloss), None, None, None
+
+
+register_autograd("tag::masked_frame_bce", _mbce_backward, setup_context=_mbce_setup)
+
+
 # ------------------------------------------------------------------------------------------------ the fused audio encoders
 # ``tag::cnn8rnn_encoder`` / ``tag::crnn_encoder``: log-mel -> conv stack -> (fc1) -> BiGRU as ONE operator each (rows F1-F3,
 # A1-A4), what models/audio_encoder.py Cnn8Rnn.forward / CrnnEncoder.forward call -- the hot 97 % of the step goes through the
@@ -581,4 +663,5 @@ def _(frame_sim, thresholds, window_size, n_connect):
 OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_relu_pool", "conv3x3_bn_relu_pool_backward",
             "gru_bidir", "gru_bidir_backward", "embed_mean", "embed_mean_backward", "frame_match", "frame_match_backward",
             "align_dot", "align_dot_backward", "frame_bce", "frame_bce_backward", "segments", "cnn8rnn_encoder", "crnn_encoder",
-            "cross_cnn8rnn", "cross_cdur"]
+            "cross_cnn8rnn", "cross_cdur", "tagging_head", "tagging_head_backward", "masked_frame_bce",
+            "masked_frame_bce_backward"]

@@ -134,3 +134,18 @@ def connect_clusters(x, n=1):
     if x.ndim == 1:
         return connect_clusters_(x, n)
     return np.apply_along_axis(lambda a: connect_clusters_(a, n=n), -2, x)
+
+
+def class_frame_sim(frame_sim: torch.Tensor, text_idx) -> torch.Tensor:
+    """The class-mapping baseline's scores of the queried classes (mapping_to_class/run_strong.py:209,
+    ``frame_sim[idx, :, text_idx]``): frame_sim (B,T,C) + text_idx (B) -> the contiguous (B,T) matrix
+    ``segments_for_thresholds`` takes."""
+    if frame_sim.ndim != 3:
+        raise ValueError(f"frame_sim: expected (B,T,C), got {tuple(frame_sim.shape)}")
+    idx = torch.as_tensor(text_idx).long().to(frame_sim.device).reshape(-1)
+    B, T, C = frame_sim.shape
+    if idx.numel() != B:
+        raise ValueError(f"text_idx: expected {B} class indices, got {idx.numel()}")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= C):
+        raise IndexError(f"text_idx out of range for {C} classes")
+    return frame_sim.gather(2, idx.view(B, 1, 1).expand(B, T, 1)).squeeze(2).contiguous()
