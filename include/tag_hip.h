@@ -423,6 +423,30 @@ int tag_gru_timed_out(const void* host_copy_of_err_word);
 int tag_gru_disable_xcd_fast(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * T3: row-local GRU recurrence of the text side, PyTorch gate order (r,z,n), h0 = 0, ALL L padded positions, one launch
+ * per layer for every direction and step: RnnEncoder.forward, models/text_encoder.py:117-125
+ * (``token_emb, h = self.rnn(x)`` :119 over the padded batch, ``mean_with_lens(token_emb, text_len)`` :123,
+ * models/utils.py mean_with_lens).  Rows never interact: a workgroup owns 16 rows x all H units of one direction, h in
+ * LDS, W_hh streamed from L2, exact fp32 MFMA; no cooperative launch, no flags, no atomics (two runs are bit-identical).
+ * Any R >= 1, L >= 1, 1 <= H <= 512, dirs 1 | 2; anything else is TAG_EINVAL.
+ *   gi       (R,L,dirs,3H): x W_ih^T + b_ih for all directions (a tag_gemm)
+ *   w_hh     (dirs,3H,H), b_hh (dirs,3H)
+ *   text_len (R) int64, nullable when seq_mean is
+ *   y        (R,L,dirs*H) hidden states, direction d in [d*H, (d+1)*H)
+ *   gates    (R,L,dirs,4H) nullable: r, z, n and h_{t-1} W_hn^T + b_hn, saved for the backward pass
+ *   seq_mean (R,dirs*H) nullable: sum of y over t < min(text_len, L), divided by text_len (the last layer's seq_emb)
+ * backward (reverse time order, same tiling):
+ *   dy (R,L,dirs*H) nullable, dseq (R,dirs*H) nullable (not both): dL/dy, and dL/dseq_mean whose share dseq / text_len is
+ *   added at the valid positions; y, gates: the forward's; outputs dgi, dgh (R,L,dirs,3H) and hprev (R,L,dirs,H) = h_{t-1},
+ *   from which the caller forms dW_ih = dgi^T x, dW_hh = dgh^T hprev, the bias column sums and dx = dgi W_ih. */
+int tag_text_gru_forward(const float* gi, const float* w_hh, const float* b_hh, const int64_t* text_len /* nullable */,
+                         float* y, float* gates /* nullable */, float* seq_mean /* nullable */, int R, int L, int H, int dirs,
+                         void* stream);
+int tag_text_gru_backward(const float* dy /* nullable */, const float* dseq /* nullable */, const int64_t* text_len,
+                          const float* y, const float* gates, const float* w_hh, float* dgi, float* dgh, float* hprev, int R,
+                          int L, int H, int dirs, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * T1 + T2: nn.Embedding gather + mean over valid tokens
  * models/text_encoder.py:39-43,79-88; models/utils.py:33-58.
  * text (B,L) int64, text_len (B) int64, table (V,D); token_emb (B,L,D) nullable; seq_emb (B,D).

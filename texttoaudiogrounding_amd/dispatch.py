@@ -833,6 +833,139 @@ def gru_bidir_backward(dy, x2d, sv, outs=None, side=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# text GRU (row T3): per layer one input-projection GEMM + ONE row-local recurrence launch (csrc/text_gru.hip), and its backward
+# ------------------------------------------------------------------------------------------------
+
+def _text_gru_layer_params(params, l, dirs):
+    """[w_ih, w_hh, b_ih, b_hh] of layer l with the directions joined: (dirs*3H, I), (dirs, 3H, H), (dirs*3H,), (dirs, 3H)."""
+    pl = params[4 * dirs * l: 4 * dirs * (l + 1)]
+    Hh, I = pl[1].shape[1], pl[0].shape[1]
+    if dirs == 1:
+        return [pl[0].contiguous(), pl[1].contiguous().view(1, 3 * Hh, Hh), pl[2].contiguous(), pl[3].contiguous().view(1, 3 * Hh)]
+    return [_joined(pl[0], pl[4], (6 * Hh, I)), _joined(pl[1], pl[5], (2, 3 * Hh, Hh)), _joined(pl[2], pl[6], (6 * Hh,)),
+            _joined(pl[3], pl[7], (2, 3 * Hh))]
+
+
+def text_gru_dropout_seed(seed, l):
+    """Seed of the dropout behind layer l of a stacked text GRU (one operator seed, one mask per layer)."""
+    return (int(seed) + l) % (2 ** 62)
+
+
+def text_gru_recurrence(gi, w_hh, b_hh, text_len, need_grad):
+    """ONE launch of tag_text_gru_forward: gi (R, L, dirs, 3H), w_hh (dirs, 3H, H), b_hh (dirs, 3H), text_len (R) int64 or
+    None -> y (R, L, dirs*H), gates (R, L, dirs, 4H) or None, seq_mean (R, dirs*H) or None (text_len is None)."""
+    gi = _chk(gi, "gi")
+    R, L, dirs, H3 = gi.shape
+    Hh = H3 // 3
+    if text_len is not None and (not text_len.is_cuda or text_len.dtype != torch.long):
+        raise RuntimeError("text_gru: text_len must be an int64 tensor on the device (no CPU fallback)")
+    y = _empty(R, L, dirs * Hh, like=gi)
+    gates = _empty(R, L, dirs, 4 * Hh, like=gi) if need_grad else None
+    seq = _empty(R, dirs * Hh, like=gi) if text_len is not None else None
+    call("tag_text_gru_forward", ptr(gi), ptr(_chk(w_hh, "w_hh")), ptr(_chk(b_hh, "b_hh")), ptr(text_len), ptr(y), ptr(gates),
+         ptr(seq), R, L, Hh, dirs)
+    return y, gates, seq
+
+
+def text_gru_recurrence_backward(dy, dseq, text_len, y, gates, w_hh):
+    """ONE launch of tag_text_gru_backward: dy (R, L, dirs*H) or None, dseq (R, dirs*H) or None -> dgi, dgh (R, L, dirs, 3H) and
+    hprev (R, L, dirs, H)."""
+    R, L, dirs, H4 = gates.shape
+    Hh = H4 // 4
+    dy = _chk(dy, "grad") if dy is not None else None
+    dseq = _chk(dseq, "grad") if dseq is not None else None
+    dgi = _empty(R, L, dirs, 3 * Hh, like=y)
+    dgh = _empty(R, L, dirs, 3 * Hh, like=y)
+    hprev = _empty(R, L, dirs, Hh, like=y)
+    call("tag_text_gru_backward", ptr(dy), ptr(dseq), ptr(text_len), ptr(y), ptr(gates), ptr(w_hh), ptr(dgi), ptr(dgh),
+         ptr(hprev), R, L, Hh, dirs)
+    return dgi, dgh, hprev
+
+
+def text_gru_dropout(x2d, p, seed, backward):
+    """Inter-layer dropout of the stacked text GRU on (M, D) rows: keep mask = tag_dropout_mask(seed) over the flat index,
+    kept values scaled by 1 / (1 - p) (the W = 1 case of the mean-over-W + dropout kernels); the backward applies the same mask."""
+    M, D = x2d.shape
+    out = _empty(M, D, like=x2d)
+    call("tag_mean_w_backward" if backward else "tag_mean_w_forward", ptr(_chk(x2d, "x")), M, 1, D, float(p), seed, ptr(out))
+    return out
+
+
+def text_gru_forward(x, text_len, params, dirs, layers, need_grad, drop_p=0.0, seed=0):
+    """nn.GRU(batch_first=True) over ALL L padded positions + mean_with_lens (models/text_encoder.py:119-123).
+    x (R, L, E) embedded tokens; text_len (R) int64 on the device; params = nn.GRU's flat weights, per layer and direction
+    [w_ih, w_hh, b_ih, b_hh].  drop_p > 0: dropout on the output of every layer but the last (the counter-based keep mask
+    tag_dropout_mask materialises, seed text_gru_dropout_seed(seed, l), index = flat index of (R, L, dirs*H)).
+    -> token_emb (R, L, dirs*H), seq_emb (R, dirs*H), saved state per layer (None unless need_grad)."""
+    x = _chk(x, "x")
+    R, L, _ = x.shape
+    Hh = params[1].shape[1]
+    M, D = R * L, dirs * Hh
+    inp = x.view(M, -1)
+    saved, y, seq = [], None, None
+    for l in range(layers):
+        w_ih, w_hh, b_ih, b_hh = _text_gru_layer_params(params, l, dirs)
+        last = l == layers - 1
+        gi = gemm(inp, w_ih, M, 3 * D, inp.shape[1], transB=True, bias=b_ih)
+        y, gates, seq = text_gru_recurrence(gi.view(R, L, dirs, 3 * Hh), w_hh, b_hh, text_len if last else None, need_grad)
+        if need_grad:
+            saved.append(dict(x=inp, y=y, gates=gates, w_ih=w_ih, w_hh=w_hh))
+        if not last:
+            inp = y.view(M, D)
+            if drop_p > 0.0:
+                inp = text_gru_dropout(inp, drop_p, text_gru_dropout_seed(seed, l), backward=False)
+    return y, seq, (saved if need_grad else None)
+
+
+def text_gru_backward(dtok, dseq, text_len, saved, dirs, drop_p=0.0, seed=0, outs=None, need=None, need_dx=True):
+    """-> (dx (R, L, E) or None, parameter gradients in nn.GRU's flat order).  dtok (R, L, dirs*H) / dseq (R, dirs*H): either
+    may be None.  outs: optional destination per parameter (flat-gradient views), written directly; need: per parameter,
+    False skips its GEMM / column sum (requires_grad = False: freeze_text_encoder) and leaves None."""
+    layers = len(saved)
+    Hh = saved[0]["w_hh"].shape[2]
+    R, L, D = saved[0]["y"].shape
+    M = R * L
+    n = 4 * dirs * layers
+    outs = list(outs) if outs is not None else [None] * n
+    need = list(need) if need is not None else [True] * n
+    g = [None] * n
+    dy, dsq, dx = dtok, dseq, None
+    for l in range(layers - 1, -1, -1):
+        sv = saved[l]
+        x2d = sv["x"]
+        I = x2d.shape[1]
+        dgi, dgh, hprev = text_gru_recurrence_backward(dy, dsq, text_len, sv["y"], sv["gates"], sv["w_hh"])
+        base = 4 * dirs * l
+        o = outs[base: base + 4 * dirs]
+        nd = need[base: base + 4 * dirs]
+        for which, src in ((2, dgi), (3, dgh)):             # bias gradients: ONE column sum over all directions when possible
+            idx = [4 * d + which for d in range(dirs)]
+            if not any(nd[i] for i in idx):
+                continue
+            sink = o[idx[0]] if dirs == 1 else _adjacent_view(o[idx[0]], o[idx[1]], (6 * Hh,))
+            tot = colsum(src, M, 3 * D, out=sink if all(nd[i] for i in idx) else None)
+            for d, i in enumerate(idx):
+                if nd[i]:
+                    part = tot[d * 3 * Hh:(d + 1) * 3 * Hh]
+                    if o[i] is not None and part.data_ptr() != o[i].data_ptr():
+                        o[i].copy_(part)
+                    g[base + i] = o[i] if o[i] is not None else part
+        for d in range(dirs):
+            if nd[4 * d]:
+                g[base + 4 * d] = gemm(dgi.view(M, 3 * D)[:, d * 3 * Hh:], x2d, 3 * Hh, I, M, transA=True, lda=3 * D, out=o[4 * d])
+            if nd[4 * d + 1]:
+                g[base + 4 * d + 1] = gemm(dgh.view(M, 3 * D)[:, d * 3 * Hh:], hprev.view(M, D)[:, d * Hh:], 3 * Hh, Hh, M,
+                                           transA=True, lda=3 * D, ldb=D, out=o[4 * d + 1])
+        if l > 0 or need_dx:
+            dx = gemm(dgi, sv["w_ih"], M, I, 3 * D)
+        if l > 0:
+            if drop_p > 0.0:
+                dx = text_gru_dropout(dx, drop_p, text_gru_dropout_seed(seed, l - 1), backward=True)
+            dy, dsq = dx.view(R, L, I), None
+    return (dx.view(R, L, -1) if need_dx else None), g
+
+
+# ------------------------------------------------------------------------------------------------
 # One conv3x3 -> BatchNorm -> ReLU (-> pool) stage as a standalone operator: what SURVEY.md section 8(b) lists as
 # ``conv3x3_bn_relu[_pool]`` and what ConvBlock.forward (models/panns.py:46-62) is made of.  The fused Cnn8Rnn node (functions.py)
 # never materialises relu(bn(y)); this stage does (its output IS that tensor, pooled), so that it composes like an nn.Module.

@@ -24,6 +24,8 @@ from .dispatch import (bias_bnrelu_backward, bias_bnrelu_forward, bias_bnrelu_po
                        bn_act_backward_clip, conv3x3_bias, conv3x3_c1_bias, frame_head_backward, frame_head_forward, gemm_bf16, leaky_backward,
                        leaky_forward, lppool_leaky_backward_clip, rowgroup_bias_relu, rowgroup_colsum)
 from .dispatch import class_pool_forward, tagging_head_dlogit
+from .dispatch import text_gru_backward, text_gru_forward
+from . import engine
 
 # ------------------------------------------------------------------------------------------------
 # Cnn8Rnn: the whole audio encoder as one autograd node (rows F1-F3, A1-A4 forward + backward)
@@ -926,6 +928,38 @@ class EmbedMeanFunction(TagFunction):
             _ready([ctx.table])
             return None, None, None, None
         return dtab, None, None, None
+
+
+class TextGruFunction(TagFunction):
+    """torch.ops.tag.text_gru with direct gradients (StrongRunner): the recurrence of RnnEncoder (models/text_encoder.py:119-123)
+    whose parameter gradients go straight into their flat-gradient views; a parameter with requires_grad = False
+    (freeze_text_encoder) costs no GEMM and its flat-gradient rows are not touched.  Same kernels as the operator."""
+
+    @staticmethod
+    def forward(ctx, x, text_len, dirs, layers, drop_p, seed, *params):
+        need = engine._RECORDING and any(ctx.needs_input_grad)
+        tok, seq, saved = text_gru_forward(x, text_len, [p.detach() for p in params], dirs, layers, need, drop_p, seed)
+        ctx.tg = (saved, text_len, dirs, drop_p, seed)
+        ctx.sinks = _sinks(list(params))
+        ctx.params = list(params) if cfg.DIRECT_GRADS else None
+        ctx.set_materialize_grads(False)
+        return tok, seq
+
+    @staticmethod
+    def backward(ctx, dtok, dseq):
+        saved, text_len, dirs, drop_p, seed = ctx.tg
+        sk, need = ctx.sinks, list(ctx.needs_input_grad[6:])
+        n = len(need)
+        if (dtok is None and dseq is None) or saved is None:
+            return (None,) * (6 + n)
+        dx, g = text_gru_backward(dtok, dseq, text_len, saved, dirs, drop_p, seed, outs=[sk[i] for i in range(n)], need=need,
+                                  need_dx=ctx.needs_input_grad[0])
+        grads = [None] * n
+        for i in range(n):
+            if need[i]:
+                _deliver(grads, sk, i, g[i])
+        _ready(ctx.params)
+        return (dx, None, None, None, None, None, *grads)
 
 
 class Seq2SeqAttentionFunction(TagFunction):

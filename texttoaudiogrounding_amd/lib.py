@@ -125,6 +125,8 @@ _SIGS = {
     "tag_gru_disable_xcd_fast": (c_int, []),
     "tag_gru_forward": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "tag_gru_backward": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
+    "tag_text_gru_forward": (c_int, [P] * 7 + [c_int] * 4 + [P]),
+    "tag_text_gru_backward": (c_int, [P] * 9 + [c_int] * 4 + [P]),
     "tag_embed_mean_forward": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_mean_backward": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_check_ids": (c_int, [P, c_long, c_int, P, P]),

@@ -1,4 +1,5 @@
-"""Word-embedding text encoder (mirror of models/text_encoder.py:14-43,61-88 in the reference)."""
+"""Learned text encoders: the word-embedding bag EmbeddingAgg and the recurrent RnnEncoder (mirror of
+models/text_encoder.py:14-43,61-125 in the reference)."""
 from typing import Dict
 
 import numpy as np
@@ -94,3 +95,49 @@ class EmbeddingAgg(nn.Module):
         if self.agg == "attention":
             seq = self.attn(tok, lens)
         return {"token_emb": tok, "seq_emb": seq}
+
+
+class RnnEncoder(nn.Module):
+    """models/text_encoder.py:91-125: EmbeddingLayer -> nn.GRU(batch_first=True) over the tokens -> mean over the valid tokens.
+
+    ``self.rnn`` is an nn.GRU that only HOLDS the parameters (state-dict keys ``rnn.weight_ih_l0`` ..., torch's default
+    init); the recurrence runs in the row-local HIP kernels of csrc/text_gru.hip (``torch.ops.tag.text_gru``).  As in the
+    reference the GRU runs UNPACKED over all L padded positions with h0 = 0: pad tokens are looked up like any other (row 0 of
+    the table, which therefore receives gradient), the reverse direction starts at the padded end, ``token_emb`` is non-zero
+    at padded positions, and the result of a row depends on the batch's padded L.  Only ``seq_emb`` masks: it is the mean
+    of ``token_emb`` over the first ``text_len`` positions.
+
+    ``rnn_type`` "GRU" is implemented; "RNN" and "LSTM" raise NotImplementedError (the HIP path has no eager fallback).
+    Inter-layer dropout (train mode, num_layers > 1, dropout > 0) uses the project's counter-based keep mask
+    (``tag_dropout_mask``), seeded from torch's global generator like the audio encoders' dropouts (ops.new_seed, decorrelated
+    per rank by ops.SEED_RANK): the same rule as nn.GRU's, not torch's random stream."""
+
+    def __init__(self, vocab_size, embed_dim, hidden_dim, num_layers, dropout, bidirectional, rnn_type, pooling="mean"):
+        super().__init__()
+        self.embedding = EmbeddingLayer(vocab_size, embed_dim)
+        assert rnn_type in ("RNN", "GRU", "LSTM")
+        if rnn_type != "GRU":
+            raise NotImplementedError(f"RnnEncoder: rnn_type {rnn_type!r} has no HIP kernel (only \"GRU\"); there is no eager fallback")
+        self.rnn = nn.GRU(input_size=embed_dim, hidden_size=hidden_dim, num_layers=num_layers, batch_first=True,
+                          dropout=dropout, bidirectional=bidirectional)
+        self.embed_dim = hidden_dim * (bidirectional + 1)
+        self.pooling = pooling
+
+    def forward(self, input_dict):
+        x = self.embedding(input_dict)
+        lead = tuple(x.shape[:-2])
+        x = x.reshape(-1, x.shape[-2], x.shape[-1])
+        text_len = torch.as_tensor(input_dict["text_len"]).long().to(x.device).reshape(-1).contiguous()
+        rnn = self.rnn
+        dirs = 2 if rnn.bidirectional else 1
+        params = [getattr(rnn, n) for names in rnn._all_weights for n in names]
+        p = float(rnn.dropout) if (self.training and rnn.num_layers > 1) else 0.0
+        seed = ops.new_seed() if p > 0.0 else 0
+        if ops.DIRECT_GRADS:
+            token_emb, seq = ops.TextGruFunction.apply(x, text_len, dirs, rnn.num_layers, p, seed, *params)
+        else:
+            token_emb, seq, _ = torch.ops.tag.text_gru(x, text_len, params, dirs, rnn.num_layers, p, seed)
+        out = {"token_emb": token_emb.view(*lead, *token_emb.shape[1:])}
+        if self.pooling == "mean":
+            out["seq_emb"] = seq.view(*lead, seq.shape[-1])
+        return out

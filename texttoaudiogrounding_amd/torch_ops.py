@@ -24,6 +24,7 @@ import torch
 from torch import Tensor
 from torch.library import custom_op, register_autograd
 
+from . import dispatch as _dispatch
 from . import engine, ops
 
 __all__ = ["OP_NAMES"]
@@ -244,6 +245,84 @@ def _embed_backward(ctx, dseq, dtok):
 
 
 register_autograd("tag::embed_mean", _embed_backward, setup_context=_embed_setup)
+
+
+# ------------------------------------------------------------------------------------------------ T3 text GRU
+def _tgru_saved(x, tok, saved, params, dirs, layers, drop_p, seed):
+    """The per-layer state ops.text_gru_backward expects, from what the operator returned: saved = the gates of every layer,
+    then the hidden states of every layer but the last (the last layer's are token_emb); a deeper layer's input is the
+    (dropped) output of the layer below, replayed from its seed."""
+    R, L, _ = x.shape
+    ys = list(saved[layers:]) + [tok]
+    out, inp = [], x.reshape(R * L, -1)
+    for l in range(layers):
+        w_ih, w_hh, _, _ = _dispatch._text_gru_layer_params(list(params), l, dirs)
+        out.append(dict(x=inp, y=ys[l], gates=saved[l], w_ih=w_ih, w_hh=w_hh))
+        inp = ys[l].reshape(R * L, -1)
+        if drop_p > 0.0 and l + 1 < layers:
+            inp = _dispatch.text_gru_dropout(inp, drop_p, _dispatch.text_gru_dropout_seed(seed, l), backward=False)
+    return out
+
+
+@custom_op("tag::text_gru", mutates_args=())
+def text_gru(x: Tensor, text_len: Tensor, params: List[Tensor], dirs: int, layers: int, drop_p: float,
+             seed: int) -> Tuple[Tensor, Tensor, List[Tensor]]:
+    """nn.GRU(E, H, layers, batch_first=True, bidirectional = dirs == 2), h0 = 0, over ALL padded positions of x (R, L, E), then
+    the mean over the valid tokens (models/text_encoder.py:119-123): -> token_emb (R, L, dirs*H), seq_emb (R, dirs*H) and the
+    saved state (gates (R, L, dirs, 4H) per layer, then the hidden states of every layer but the last).  params: nn.GRU's
+    flat weights.  drop_p > 0 applies the inter-layer dropout (the caller passes 0 in eval mode) with the keep mask of ``seed``."""
+    tok, seq, saved = ops.text_gru_forward(x, text_len, list(params), dirs, layers, True, drop_p, seed)
+    return tok, seq, [sv["gates"] for sv in saved] + [sv["y"] for sv in saved[:-1]]
+
+
+@text_gru.register_fake
+def _(x, text_len, params, dirs, layers, drop_p, seed):
+    R, L, _ = x.shape
+    H = params[1].shape[1]
+    return (x.new_empty(R, L, dirs * H), x.new_empty(R, dirs * H),
+            [x.new_empty(R, L, dirs, 4 * H) for _ in range(layers)] + [x.new_empty(R, L, dirs * H) for _ in range(layers - 1)])
+
+
+@custom_op("tag::text_gru_backward", mutates_args=())
+def text_gru_backward(dtok: Optional[Tensor], dseq: Optional[Tensor], x: Tensor, text_len: Tensor, tok: Tensor,
+                      saved: List[Tensor], params: List[Tensor], dirs: int, layers: int, drop_p: float, seed: int,
+                      need: List[bool], need_dx: bool) -> List[Tensor]:
+    """-> [dx] + one gradient per parameter; an entry that is not needed (need[i] / need_dx False) is an empty tensor."""
+    sv = _tgru_saved(x, tok, saved, params, dirs, layers, drop_p, seed)
+    dx, g = ops.text_gru_backward(dtok, dseq, text_len, sv, dirs, drop_p, seed, need=list(need), need_dx=need_dx)
+    none = lambda: x.new_empty(0)                                                    # noqa: E731
+    return [dx.clone() if dx is not None else none()] + [t.clone() if t is not None else none() for t in g]
+
+
+@text_gru_backward.register_fake
+def _(dtok, dseq, x, text_len, tok, saved, params, dirs, layers, drop_p, seed, need, need_dx):
+    return [torch.empty_like(x) if need_dx else x.new_empty(0)] + [torch.empty_like(p) if n else x.new_empty(0)
+                                                                    for p, n in zip(params, need)]
+
+
+def _tgru_setup(ctx, inputs, output):
+    x, text_len, params, dirs, layers, drop_p, seed = inputs
+    tok, _, saved = output
+    ctx.save_for_backward(x, text_len, tok, *saved, *params)
+    ctx.meta = (dirs, layers, drop_p, seed, len(saved))
+    ctx.need = [bool(p.requires_grad) for p in params]
+    ctx.need_dx = bool(x.requires_grad)
+
+
+def _tgru_backward(ctx, dtok, dseq, _dsaved):
+    dirs, layers, drop_p, seed, ns = ctx.meta
+    x, text_len, tok = ctx.saved_tensors[:3]
+    saved, params = list(ctx.saved_tensors[3:3 + ns]), list(ctx.saved_tensors[3 + ns:])
+    if dtok is not None:
+        dtok = dtok.contiguous()
+    if dseq is not None:
+        dseq = dseq.contiguous()
+    g = torch.ops.tag.text_gru_backward(dtok, dseq, x, text_len, tok, saved, params, dirs, layers, drop_p, seed, ctx.need,
+                                        ctx.need_dx)
+    return (g[0] if ctx.need_dx else None, None, [t if n else None for t, n in zip(g[1:], ctx.need)], None, None, None, None)
+
+
+register_autograd("tag::text_gru", _tgru_backward, setup_context=_tgru_setup)
 
 
 # ------------------------------------------------------------------------------------------------ M1/M2 frame x phrase heads
@@ -664,4 +743,4 @@ OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_r
             "gru_bidir", "gru_bidir_backward", "embed_mean", "embed_mean_backward", "frame_match", "frame_match_backward",
             "align_dot", "align_dot_backward", "frame_bce", "frame_bce_backward", "segments", "cnn8rnn_encoder", "crnn_encoder",
             "cross_cnn8rnn", "cross_cdur", "tagging_head", "tagging_head_backward", "masked_frame_bce",
-            "masked_frame_bce_backward"]
+            "masked_frame_bce_backward", "text_gru", "text_gru_backward"]
