@@ -948,13 +948,14 @@ def audio_mean_text_mean(sim, audio_len, text_len):
     return (s * tm[None, :, :]).sum(2) / torch.as_tensor(text_len).to(sim.dtype).view(1, -1)
 
 
-def max_margin_ranking_loss(x, margin=1.0, lamda1=1.0):
-    """MaxMarginRankingLoss(fix_norm=True) (losses.py:226-264)."""
+def max_margin_ranking_loss(x, margin=1.0, lamda1=1.0, fix_norm=True):
+    """MaxMarginRankingLoss (losses.py:226-264): mean of relu(m - (x_ii - x_ij)) and relu(m - (x_ii - lamda1 x_ji)) over the
+    pairs i != j (fix_norm=True), or over all n^2 pairs, the diagonal ones included (fix_norm=False)."""
     n = x.shape[0]
     d = torch.diag(x).view(-1, 1)
-    off = ~torch.eye(n, dtype=torch.bool)
-    t1 = F.relu(margin - (d - x))[off]
-    t2 = F.relu(margin - (d - lamda1 * x.t()))[off]
+    keep = ~torch.eye(n, dtype=torch.bool) if fix_norm else torch.ones(n, n, dtype=torch.bool)
+    t1 = F.relu(margin - (d - x))[keep]
+    t2 = F.relu(margin - (d - lamda1 * x.t()))[keep]
     return torch.cat([t1, t2]).mean()
 
 
