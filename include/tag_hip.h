@@ -447,6 +447,36 @@ int tag_text_gru_backward(const float* dy /* nullable */, const float* dseq /* n
                           int L, int H, int dirs, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * T4: self-attention of the text side: SelfAttention.forward, models/text_encoder.py:261-268
+ * (``cat(cls_token, x)`` :263, ``self.pe(x)`` :264 = + sinusoidal positions then dropout, ``self.mha(x, x, x, padding_mask)``
+ * :267 with keys >= text_len + 1 masked).  The in- and out-projections are tag_gemm calls; tag_text_selfattn_* is the
+ * scaled-dot-product core over the PACKED in-projection, tag_text_cls_pe_* builds the attention input.  Rows and heads
+ * never interact: one wave owns a (row, head) pair, the S x S weights live in wave-private LDS, dq / dk / dv of the pair
+ * are complete fixed-order sums; no partials, no workspace, no atomics (two runs are bit-identical).  Exact fp32 on the VALU.
+ * R >= 1, 2 <= S <= 64, E <= 1024, head_dim = E/H in {16, 32} or a multiple of 64; anything else is TAG_EINVAL.
+ *   qkv   (R,S,3E) [q|k|v] exactly as the in-projection GEMM leaves it; head h = channels [h*E/H, (h+1)*E/H) of each part
+ *   klen  (R) int64 valid keys, 1 ... S (clamped into that range): keys >= klen get -inf before the softmax; queries are
+ *         NOT masked (padded positions produce output, as in the reference); scale 1/sqrt(E/H)
+ *   ctx   (R,S,E)
+ *   attn  (R,H,S,S) nullable: the softmax weights BEFORE dropout (exactly 0 at keys >= klen), saved for the backward pass
+ *   drop_p / seed: dropout on the weights, tag_keep(seed, flat index of (R,H,S,S)) -- what tag_dropout_mask materialises
+ * backward: qkv, attn, dctx (R,S,E), klen -> dqkv (R,S,3E) packed the same way, every element written; the caller forms
+ *   dW_in = dqkv^T x (one tag_gemm), db_in (one tag_colsum) and dx = dqkv W_in.
+ * tag_text_cls_pe_forward:  x (R,L+1,E) = dropout([cls ; tok] + pe[:L+1]); tok (R,L,E), cls (E), pe (>= L+1 rows of E);
+ *   keep mask = tag_keep(seed, flat index of (R,L+1,E)).
+ * tag_text_cls_pe_backward: dx (R,L+1,E) through the same mask -> dtok (R,L,E) (nullable) and dcls_rows (R,E) (nullable),
+ *   the gradient rows of the cls position, whose column sum (tag_colsum: fixed order, no atomics) is dcls (E).
+ * ------------------------------------------------------------------------------------------- */
+int tag_text_selfattn_forward(const float* qkv, const int64_t* klen, float* ctx, float* attn /* nullable */, int R, int S,
+                              int E, int H, float drop_p, uint64_t seed, void* stream);
+int tag_text_selfattn_backward(const float* qkv, const float* attn, const float* dctx, const int64_t* klen, float* dqkv,
+                               int R, int S, int E, int H, float drop_p, uint64_t seed, void* stream);
+int tag_text_cls_pe_forward(const float* tok, const float* cls, const float* pe, float* x, int R, int L, int E, float drop_p,
+                            uint64_t seed, void* stream);
+int tag_text_cls_pe_backward(const float* dx, float* dtok /* nullable */, float* dcls_rows /* nullable */, int R, int L,
+                             int E, float drop_p, uint64_t seed, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * T1 + T2: nn.Embedding gather + mean over valid tokens
  * models/text_encoder.py:39-43,79-88; models/utils.py:33-58.
  * text (B,L) int64, text_len (B) int64, table (V,D); token_emb (B,L,D) nullable; seq_emb (B,D).

@@ -966,6 +966,140 @@ def text_gru_backward(dtok, dseq, text_len, saved, dirs, drop_p=0.0, seed=0, out
 
 
 # ------------------------------------------------------------------------------------------------
+# text self-attention (row T4): cls + positions + dropout, in-projection GEMM, ONE row-local core launch (csrc/text_attn.hip),
+# out-projection GEMM, and its backward
+# ------------------------------------------------------------------------------------------------
+TEXT_SELFATTN_MAX_S = 64
+
+
+def text_selfattn_dropout_seeds(seed):
+    """(seed of the dropout behind the positions, seed of the dropout on the attention weights) from ONE operator seed."""
+    return int(seed) % (2 ** 62), (int(seed) + 1) % (2 ** 62)
+
+
+def text_selfattn_check(E, heads, S=None):
+    """The domain of tag_text_selfattn_*, raised before any launch with the limit named."""
+    if heads < 1 or E % heads != 0:
+        raise ValueError(f"text_selfattn: embed_dim {E} is not divisible by num_heads {heads}")
+    dh = E // heads
+    if E > 1024 or not (dh in (16, 32) or dh % 64 == 0):
+        raise NotImplementedError(f"text_selfattn: head_dim {dh} (embed_dim {E} / {heads} heads) has no HIP kernel: head_dim must be 16, "
+                                  "32 or a multiple of 64 and embed_dim <= 1024; there is no eager fallback")
+    if S is not None and not 2 <= S <= TEXT_SELFATTN_MAX_S:
+        raise ValueError(f"text_selfattn: {S} positions (cls + {S - 1} tokens); the kernel serves 2 ... {TEXT_SELFATTN_MAX_S} "
+                         f"positions, that is 1 ... {TEXT_SELFATTN_MAX_S - 1} tokens")
+
+
+def _klen_chk(klen, R):
+    if not klen.is_cuda or klen.dtype != torch.long or klen.numel() != R:
+        raise RuntimeError("text_selfattn: klen must be an int64 tensor of R entries on the device (no CPU fallback)")
+    return klen.contiguous()
+
+
+def text_selfattn_core(qkv, klen, heads, need_attn=True, drop_p=0.0, seed=0):
+    """ONE launch of tag_text_selfattn_forward: qkv (R, S, 3E) packed [q|k|v] (read in place, any 4-byte aligned view), klen (R)
+    int64 valid keys -> ctx (R, S, E), attn (R, H, S, S) = the weights before dropout, or None."""
+    qkv = _chk(qkv, "qkv")
+    R, S, E3 = qkv.shape
+    E = E3 // 3
+    text_selfattn_check(E, heads, S)
+    klen = _klen_chk(klen, R)
+    ctx = _empty(R, S, E, like=qkv)
+    attn = _empty(R, heads, S, S, like=qkv) if need_attn else None
+    call("tag_text_selfattn_forward", ptr(qkv), ptr(klen), ptr(ctx), ptr(attn), R, S, E, heads, float(drop_p), int(seed))
+    return ctx, attn
+
+
+def text_selfattn_core_backward(qkv, attn, dctx, klen, heads, drop_p=0.0, seed=0):
+    """ONE launch of tag_text_selfattn_backward -> dqkv (R, S, 3E), packed like qkv."""
+    qkv, attn, dctx = _chk(qkv, "qkv"), _chk(attn, "attn"), _chk(dctx, "grad")
+    R, S, E3 = qkv.shape
+    E = E3 // 3
+    text_selfattn_check(E, heads, S)
+    klen = _klen_chk(klen, R)
+    dqkv = _empty(R, S, E3, like=qkv)
+    call("tag_text_selfattn_backward", ptr(qkv), ptr(attn), ptr(dctx), ptr(klen), ptr(dqkv), R, S, E, heads, float(drop_p), int(seed))
+    return dqkv
+
+
+def text_cls_pe_forward(tok, cls, pe, drop_p=0.0, seed=0):
+    """x (R, L+1, E) = dropout([cls ; tok] + pe[:L+1]); tok (R, L, E), cls (E) (any shape of E entries), pe (>= L+1, E)."""
+    tok = _chk(tok, "tok")
+    R, L, E = tok.shape
+    cls, pe = _chk(cls, "cls_token").view(-1), _chk(pe, "pe").view(-1, E)
+    if cls.numel() != E or pe.shape[0] < L + 1:
+        raise ValueError(f"text_cls_pe: cls has {cls.numel()} entries for embed_dim {E}, the position table {pe.shape[0]} rows for "
+                         f"{L + 1} positions")
+    x = _empty(R, L + 1, E, like=tok)
+    call("tag_text_cls_pe_forward", ptr(tok), ptr(cls), ptr(pe), ptr(x), R, L, E, float(drop_p), int(seed))
+    return x
+
+
+def text_cls_pe_backward(dx, drop_p=0.0, seed=0, need_dtok=True, need_dcls=True, dcls_out=None):
+    """dx (R, L+1, E) -> dtok (R, L, E), dcls (E): the masked cls rows summed by tag_colsum (fixed order, no atomics)."""
+    dx = _chk(dx, "grad")
+    R, S, E = dx.shape
+    if not (need_dtok or need_dcls):
+        return None, None
+    dtok = _empty(R, S - 1, E, like=dx) if need_dtok else None
+    rows = _empty(R, E, like=dx) if need_dcls else None
+    call("tag_text_cls_pe_backward", ptr(dx), ptr(dtok), ptr(rows), R, S - 1, E, float(drop_p), int(seed))
+    dcls = colsum(rows, R, E, out=dcls_out.view(-1) if dcls_out is not None else None) if need_dcls else None
+    return dtok, dcls
+
+
+def text_selfattn_forward(tok, text_len, pe, cls, w_in, b_in, w_out, b_out, heads, need_grad, drop_p=0.0, seed=0):
+    """SelfAttention.forward behind the embedding (models/text_encoder.py:263-268): tok (R, L, E) embedded tokens, text_len (R)
+    int64 on the device (0 ... L, clamped), pe (>= L+1, E), cls (E), nn.MultiheadAttention's in_proj (3E, E) / (3E) and out_proj
+    (E, E) / (E).  drop_p > 0 (train): the SAME p on the positions and on the attention weights, keep masks of
+    text_selfattn_dropout_seeds(seed).  -> out (R, L+1, E) (row 0 = seq_emb, the rest = token_emb), saved state or None."""
+    tok = _chk(tok, "tok")
+    R, L, E = tok.shape
+    text_selfattn_check(E, heads, L + 1)
+    s_pe, s_attn = text_selfattn_dropout_seeds(seed)
+    M = R * (L + 1)
+    klen = text_len.clamp(0, L) + 1
+    x = text_cls_pe_forward(tok, cls, pe, drop_p, s_pe)
+    w_in, w_out = _chk(w_in, "in_proj_weight"), _chk(w_out, "out_proj.weight")
+    qkv = gemm(x.view(M, E), w_in, M, 3 * E, E, transB=True, bias=_chk(b_in, "in_proj_bias"))
+    ctx, attn = text_selfattn_core(qkv.view(R, L + 1, 3 * E), klen, heads, need_grad, drop_p, s_attn)
+    out = gemm(ctx.view(M, E), w_out, M, E, E, transB=True, bias=_chk(b_out, "out_proj.bias"))
+    saved = dict(x=x, qkv=qkv, attn=attn, ctx=ctx, klen=klen, w_in=w_in, w_out=w_out) if need_grad else None
+    return out.view(R, L + 1, E), saved
+
+
+def text_selfattn_backward(dout, saved, heads, drop_p=0.0, seed=0, outs=None, need=None, need_dtok=True):
+    """-> (dtok (R, L, E) or None, [dcls, dw_in, db_in, dw_out, db_out]).  outs: optional destination per parameter (flat-gradient
+    views), written directly; need: per parameter, False skips its GEMM / column sum (a frozen parameter) and leaves None."""
+    dout = _chk(dout, "grad")
+    R, S, E = dout.shape
+    M = R * S
+    outs = list(outs) if outs is not None else [None] * 5
+    need = list(need) if need is not None else [True] * 5
+    s_pe, s_attn = text_selfattn_dropout_seeds(seed)
+    g = [None] * 5
+    d2 = dout.view(M, E)
+    if need[3]:
+        g[3] = gemm(d2, saved["ctx"].view(M, E), E, E, M, transA=True, lda=E, out=outs[3])
+    if need[4]:
+        g[4] = colsum(d2, M, E, out=outs[4])
+    if not (need[0] or need[1] or need[2] or need_dtok):
+        return None, g
+    dctx = gemm(d2, saved["w_out"], M, E, E)
+    dqkv = text_selfattn_core_backward(saved["qkv"].view(R, S, 3 * E), saved["attn"], dctx.view(R, S, E), saved["klen"], heads,
+                                       drop_p, s_attn).view(M, 3 * E)
+    if need[1]:
+        g[1] = gemm(dqkv, saved["x"].view(M, E), 3 * E, E, M, transA=True, lda=3 * E, out=outs[1])
+    if need[2]:
+        g[2] = colsum(dqkv, M, 3 * E, out=outs[2])
+    dtok = None
+    if need[0] or need_dtok:
+        dx = gemm(dqkv, saved["w_in"], M, E, 3 * E)
+        dtok, g[0] = text_cls_pe_backward(dx.view(R, S, E), drop_p, s_pe, need_dtok, need[0], dcls_out=outs[0])
+    return dtok, g
+
+
+# ------------------------------------------------------------------------------------------------
 # One conv3x3 -> BatchNorm -> ReLU (-> pool) stage as a standalone operator: what SURVEY.md section 8(b) lists as
 # ``conv3x3_bn_relu[_pool]`` and what ConvBlock.forward (models/panns.py:46-62) is made of.  The fused Cnn8Rnn node (functions.py)
 # never materialises relu(bn(y)); this stage does (its output IS that tensor, pooled), so that it composes like an nn.Module.

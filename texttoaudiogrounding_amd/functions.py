@@ -25,6 +25,7 @@ from .dispatch import (bias_bnrelu_backward, bias_bnrelu_forward, bias_bnrelu_po
                        leaky_forward, lppool_leaky_backward_clip, rowgroup_bias_relu, rowgroup_colsum)
 from .dispatch import class_pool_forward, tagging_head_dlogit
 from .dispatch import text_gru_backward, text_gru_forward
+from .dispatch import text_selfattn_backward, text_selfattn_forward
 from . import engine
 
 # ------------------------------------------------------------------------------------------------
@@ -960,6 +961,39 @@ class TextGruFunction(TagFunction):
                 _deliver(grads, sk, i, g[i])
         _ready(ctx.params)
         return (dx, None, None, None, None, None, *grads)
+
+
+class TextSelfAttnFunction(TagFunction):
+    """torch.ops.tag.text_selfattn with direct gradients (StrongRunner): SelfAttention behind its embedding
+    (models/text_encoder.py:263-268) whose parameter gradients (cls_token, in_proj, out_proj) go straight into their
+    flat-gradient views; a parameter with requires_grad = False costs no GEMM / column sum and its flat-gradient rows are not
+    touched.  Same kernels as the operator."""
+
+    @staticmethod
+    def forward(ctx, tok, text_len, pe, heads, drop_p, seed, *params):
+        need = engine._RECORDING and any(ctx.needs_input_grad)
+        cls, w_in, b_in, w_out, b_out = [p.detach() for p in params]
+        out, saved = text_selfattn_forward(tok, text_len, pe, cls, w_in, b_in, w_out, b_out, heads, need, drop_p, seed)
+        ctx.sa = (saved, heads, drop_p, seed)
+        ctx.shapes = [tuple(p.shape) for p in params]
+        ctx.sinks = _sinks(list(params))
+        ctx.params = list(params) if cfg.DIRECT_GRADS else None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        saved, heads, drop_p, seed = ctx.sa
+        sk, need = ctx.sinks, list(ctx.needs_input_grad[6:])
+        if saved is None:
+            return (None,) * 11
+        dtok, g = text_selfattn_backward(dout, saved, heads, drop_p, seed, outs=[sk[i] for i in range(5)], need=need,
+                                         need_dtok=ctx.needs_input_grad[0])
+        grads = [None] * 5
+        for i in range(5):
+            if need[i]:
+                _deliver(grads, sk, i, g[i] if sk[i] is not None else g[i].view(ctx.shapes[i]))
+        _ready(ctx.params)
+        return (dtok, None, None, None, None, None, *grads)
 
 
 class Seq2SeqAttentionFunction(TagFunction):

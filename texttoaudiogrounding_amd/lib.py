@@ -127,6 +127,10 @@ _SIGS = {
     "tag_gru_backward": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "tag_text_gru_forward": (c_int, [P] * 7 + [c_int] * 4 + [P]),
     "tag_text_gru_backward": (c_int, [P] * 9 + [c_int] * 4 + [P]),
+    "tag_text_selfattn_forward": (c_int, [P] * 4 + [c_int] * 4 + [c_float, c_uint64, P]),
+    "tag_text_selfattn_backward": (c_int, [P] * 5 + [c_int] * 4 + [c_float, c_uint64, P]),
+    "tag_text_cls_pe_forward": (c_int, [P] * 4 + [c_int] * 3 + [c_float, c_uint64, P]),
+    "tag_text_cls_pe_backward": (c_int, [P] * 3 + [c_int] * 3 + [c_float, c_uint64, P]),
     "tag_embed_mean_forward": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_mean_backward": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_check_ids": (c_int, [P, c_long, c_int, P, P]),

@@ -1,5 +1,6 @@
-"""Learned text encoders: the word-embedding bag EmbeddingAgg and the recurrent RnnEncoder (mirror of
-models/text_encoder.py:14-43,61-125 in the reference)."""
+"""Learned text encoders: the word-embedding bag EmbeddingAgg, the recurrent RnnEncoder and the SelfAttention encoder (mirror
+of models/text_encoder.py:14-43,61-145,240-268 in the reference)."""
+import math
 from typing import Dict
 
 import numpy as np
@@ -141,3 +142,79 @@ class RnnEncoder(nn.Module):
         if self.pooling == "mean":
             out["seq_emb"] = seq.view(*lead, seq.shape[-1])
         return out
+
+
+class PositionalEncoding(nn.Module):
+    """Buffer container with the reference's layout (models/text_encoder.py:128-144): ``pe`` (1, max_len, d_model), sin on the
+    even channels and cos on the odd ones; ``p`` is the dropout behind the positions.  The addition and the dropout run in
+    ``tag_text_cls_pe_forward``."""
+
+    def __init__(self, d_model, dropout, max_len=100):
+        super().__init__()
+        if d_model % 2:
+            raise ValueError(f"PositionalEncoding: embed_dim {d_model} is odd; the sin/cos table is defined for even embed_dim only")
+        self.p = float(dropout)
+        pe = torch.zeros(max_len, d_model)
+        position = torch.arange(0, max_len).unsqueeze(1)
+        div_term = torch.exp(torch.arange(0, d_model, 2) * -(math.log(10000.0) / d_model))
+        pe[:, 0::2] = torch.sin(position * div_term)
+        pe[:, 1::2] = torch.cos(position * div_term)
+        self.register_buffer("pe", pe.unsqueeze(0))
+
+
+class SelfAttention(nn.Module):
+    """models/text_encoder.py:240-268: EmbeddingLayer -> learned ``cls_token`` in front -> + sinusoidal positions -> dropout ->
+    ONE nn.MultiheadAttention(batch_first=True) over the phrase, keys >= text_len + 1 masked -> ``seq_emb`` = the cls row,
+    ``token_emb`` = the remaining rows (contextual).
+
+    ``self.mha`` is an nn.MultiheadAttention that only HOLDS the parameters (state-dict keys ``mha.in_proj_weight`` ...,
+    torch's default init); the arithmetic runs in ``torch.ops.tag.text_selfattn``: the two projections are tag_gemm calls, the
+    scaled-dot-product core and the input builder are the row-local HIP kernels of csrc/text_attn.hip.  As in the reference
+    only KEYS are masked: padded query positions produce output, so ``token_emb`` is non-zero at padded positions, and pad
+    tokens are looked up like any other (row 0 of the table, which therefore receives gradient).  ``text_len`` 0 is legal:
+    only the cls key is attended.
+
+    Unlike the reference, every ``text_len`` in [0, L] is served: the reference builds its mask max(text_len) + 1 wide and
+    nn.MultiheadAttention raises whenever the longest phrase does not fill the padded tensor.
+
+    Dropout (train mode): the same ``dropout`` value acts behind the positions and on the attention weights, with the
+    project's counter-based keep masks (``tag_dropout_mask``; seeds ops.text_selfattn_dropout_seeds(ops.new_seed()), drawn
+    from torch's global generator like the audio encoders' dropouts and decorrelated per rank by ops.SEED_RANK): the same
+    rule as nn.Dropout's, not torch's random stream.
+
+    There is no eager fallback: at most 63 tokens (64 positions with cls), head_dim = embed_dim / num_heads in {16, 32} or a
+    multiple of 64, embed_dim even and <= 1024; anything else raises ValueError / NotImplementedError."""
+
+    MAX_TOKENS = ops.TEXT_SELFATTN_MAX_S - 1
+
+    def __init__(self, vocab_size, embed_dim, num_heads, dropout=0.2, pretrained_embedding=None, freeze_embedding=False):
+        super().__init__()
+        if embed_dim % 2:
+            raise ValueError(f"SelfAttention: embed_dim {embed_dim} is odd; the sin/cos position table is defined for even embed_dim only")
+        ops.text_selfattn_check(embed_dim, num_heads)
+        self.embed_dim = embed_dim
+        self.embedding = EmbeddingLayer(vocab_size, embed_dim, pretrained_embedding, freeze_embedding)
+        self.pe = PositionalEncoding(embed_dim, dropout)
+        self.mha = nn.MultiheadAttention(embed_dim, num_heads, dropout, batch_first=True)
+        self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
+
+    def forward(self, input_dict):
+        n_tok = np.shape(input_dict["text"])[-1]
+        if n_tok > self.MAX_TOKENS:                        # before any launch
+            raise ValueError(f"SelfAttention: {n_tok} tokens per phrase; the attention kernel serves at most {self.MAX_TOKENS} "
+                             "(64 positions with the cls token) and there is no eager fallback")
+        x = self.embedding(input_dict)
+        lead = tuple(x.shape[:-2])
+        L, E = x.shape[-2], x.shape[-1]
+        x = x.reshape(-1, L, E)
+        text_len = torch.as_tensor(input_dict["text_len"]).long().to(x.device).reshape(-1).contiguous()
+        mha = self.mha
+        params = [self.cls_token, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias]
+        p = float(self.pe.p) if self.training else 0.0
+        seed = ops.new_seed() if p > 0.0 else 0
+        pe = self.pe.pe[0]
+        if ops.DIRECT_GRADS:
+            out = ops.TextSelfAttnFunction.apply(x, text_len, pe, mha.num_heads, p, seed, *params)
+        else:
+            out, _ = torch.ops.tag.text_selfattn(x, text_len, pe, params, mha.num_heads, p, seed)
+        return {"token_emb": out[:, 1:].contiguous().view(*lead, L, E), "seq_emb": out[:, 0].contiguous().view(*lead, E)}

@@ -325,6 +325,64 @@ def _tgru_backward(ctx, dtok, dseq, _dsaved):
 register_autograd("tag::text_gru", _tgru_backward, setup_context=_tgru_setup)
 
 
+# ------------------------------------------------------------------------------------------------ T4 text self-attention
+@custom_op("tag::text_selfattn", mutates_args=())
+def text_selfattn(tok: Tensor, text_len: Tensor, pe: Tensor, params: List[Tensor], heads: int, drop_p: float,
+                  seed: int) -> Tuple[Tensor, List[Tensor]]:
+    """SelfAttention behind its embedding (models/text_encoder.py:263-268): tok (R, L, E) embedded tokens, text_len (R) int64,
+    pe (>= L+1, E) positions, params = [cls_token, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
+    mha.out_proj.bias] -> out (R, L+1, E) (row 0 = seq_emb, rows 1.. = token_emb) and the saved state [x, qkv, attn, ctx, klen].
+    drop_p > 0 (the caller passes 0 in eval mode): dropout behind the positions and on the attention weights, keep masks of
+    ops.text_selfattn_dropout_seeds(seed)."""
+    out, sv = ops.text_selfattn_forward(tok, text_len, pe, *params, heads, True, drop_p, seed)
+    return out, [sv["x"], sv["qkv"], sv["attn"], sv["ctx"], sv["klen"]]
+
+
+@text_selfattn.register_fake
+def _(tok, text_len, pe, params, heads, drop_p, seed):
+    R, L, E = tok.shape
+    S = L + 1
+    return (tok.new_empty(R, S, E), [tok.new_empty(R, S, E), tok.new_empty(R * S, 3 * E), tok.new_empty(R, heads, S, S),
+                                     tok.new_empty(R, S, E), text_len.new_empty(R)])
+
+
+@custom_op("tag::text_selfattn_backward", mutates_args=())
+def text_selfattn_backward(dout: Tensor, saved: List[Tensor], params: List[Tensor], heads: int, drop_p: float, seed: int,
+                           need: List[bool], need_dtok: bool) -> List[Tensor]:
+    """-> [dtok] + one gradient per parameter; an entry that is not needed (need[i] / need_dtok False) is an empty tensor."""
+    x, qkv, attn, ctx, klen = saved
+    sv = dict(x=x, qkv=qkv, attn=attn, ctx=ctx, klen=klen, w_in=params[1].contiguous(), w_out=params[3].contiguous())
+    dtok, g = ops.text_selfattn_backward(dout, sv, heads, drop_p, seed, need=list(need), need_dtok=need_dtok)
+    none = lambda: dout.new_empty(0)                                                 # noqa: E731
+    return [dtok if dtok is not None else none()] + [t.view(p.shape) if t is not None else none() for t, p in zip(g, params)]
+
+
+@text_selfattn_backward.register_fake
+def _(dout, saved, params, heads, drop_p, seed, need, need_dtok):
+    R, S, E = dout.shape
+    return [dout.new_empty(R, S - 1, E) if need_dtok else dout.new_empty(0)] + [torch.empty_like(p) if n else dout.new_empty(0)
+                                                                               for p, n in zip(params, need)]
+
+
+def _tsa_setup(ctx, inputs, output):
+    tok, text_len, pe, params, heads, drop_p, seed = inputs
+    _, saved = output
+    ctx.save_for_backward(*saved, *params)
+    ctx.meta = (heads, drop_p, seed, len(saved))
+    ctx.need = [bool(p.requires_grad) for p in params]
+    ctx.need_dtok = bool(tok.requires_grad)
+
+
+def _tsa_backward(ctx, dout, _dsaved):
+    heads, drop_p, seed, ns = ctx.meta
+    saved, params = list(ctx.saved_tensors[:ns]), list(ctx.saved_tensors[ns:])
+    g = torch.ops.tag.text_selfattn_backward(dout.contiguous(), saved, params, heads, drop_p, seed, ctx.need, ctx.need_dtok)
+    return (g[0] if ctx.need_dtok else None, None, None, [t if n else None for t, n in zip(g[1:], ctx.need)], None, None, None)
+
+
+register_autograd("tag::text_selfattn", _tsa_backward, setup_context=_tsa_setup)
+
+
 # ------------------------------------------------------------------------------------------------ M1/M2 frame x phrase heads
 @custom_op("tag::frame_match", mutates_args=())
 def frame_match(audio: Tensor, text: Tensor, kind: int, l2norm: bool, scale: bool) -> Tensor:
@@ -743,4 +801,4 @@ OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_r
             "gru_bidir", "gru_bidir_backward", "embed_mean", "embed_mean_backward", "frame_match", "frame_match_backward",
             "align_dot", "align_dot_backward", "frame_bce", "frame_bce_backward", "segments", "cnn8rnn_encoder", "crnn_encoder",
             "cross_cnn8rnn", "cross_cdur", "tagging_head", "tagging_head_backward", "masked_frame_bce",
-            "masked_frame_bce_backward", "text_gru", "text_gru_backward"]
+            "masked_frame_bce_backward", "text_gru", "text_gru_backward", "text_selfattn", "text_selfattn_backward"]
