@@ -90,6 +90,11 @@ def bn_stats(x2d, gamma, beta, running_mean, running_var, training, eps=1e-5, mo
     return st
 
 
+def _dg_db(dg_out, db_out, C, like):
+    """The (dgamma, dbeta) destinations of a BatchNorm backward: the caller's flat-gradient views, or fresh (C,) tensors."""
+    return (dg_out if dg_out is not None else _empty(C, like=like)), (db_out if db_out is not None else _empty(C, like=like))
+
+
 _X3_PRODUCTS = {"x3": 6, "x9": 9, "bf16": 1}
 BF16 = torch.bfloat16
 
@@ -265,8 +270,7 @@ def conv3x3_dgrad_bnrelu_backward(dy_in, wpack, yref, st: BNStat, gamma, dg_out=
                  ptr(st.mean), ptr(st.invstd), ptr(part), B, H, W, Cin, C)
         if after_conv is not None:
             after_conv()
-        dg = dg_out if dg_out is not None else _empty(C, like=da)
-        db = db_out if db_out is not None else _empty(C, like=da)
+        dg, db = _dg_db(dg_out, db_out, C, da)
         ws = _ws(query("tag_bn_grad_from_partials_ws_bytes", P, C), da)
         call("tag_bn_grad_from_partials", ptr(part), P, C, ptr(dg), ptr(db), ptr(ws))
         if defer_apply:
@@ -297,8 +301,7 @@ def conv3x3_dgrad_bnrelu_backward(dy_in, wpack, yref, st: BNStat, gamma, dg_out=
                  ptr(st.mean), ptr(st.invstd), ptr(part), B, H, W, Cin, C)
     if after_conv is not None:
         after_conv()
-    dg = dg_out if dg_out is not None else _empty(C, like=da)
-    db = db_out if db_out is not None else _empty(C, like=da)
+    dg, db = _dg_db(dg_out, db_out, C, da)
     ws = _ws(query("tag_bn_grad_from_partials_ws_bytes", P, C), da)
     call("tag_bn_grad_from_partials", ptr(part), P, C, ptr(dg), ptr(db), ptr(ws))
     if defer_apply:
@@ -508,8 +511,7 @@ def bnrelu_pool_backward(y, st: BNStat, gamma, dout, ph, pw, drop_p=0.0, seed=0,
     if dout.dtype != y.dtype:
         raise RuntimeError("bnrelu_pool_backward: y and dout must share their storage type")
     dy = _empty(B, H, W, C, like=y, dtype=y.dtype)
-    dg = dg_out if dg_out is not None else _empty(C, like=y)
-    db = db_out if db_out is not None else _empty(C, like=y)
+    dg, db = _dg_db(dg_out, db_out, C, y)
     if partials is not None:
         P, part = partials
         ws = _ws(query("tag_bn_grad_from_partials_ws_bytes", P, C), y)
@@ -527,8 +529,7 @@ def bnrelu_backward(y, st: BNStat, gamma, da, inplace=True, dg_out=None, db_out=
     C = y.shape[-1]
     rows = y.numel() // C
     dy = da if inplace else torch.empty_like(da)
-    dg = dg_out if dg_out is not None else _empty(C, like=y)
-    db = db_out if db_out is not None else _empty(C, like=y)
+    dg, db = _dg_db(dg_out, db_out, C, y)
     ws = _ws(query("tag_bn_backward_ws_bytes", rows, C), y)
     if da.dtype != y.dtype:
         raise RuntimeError("bnrelu_backward: y and da must share their storage type")
@@ -539,8 +540,7 @@ def bnrelu_backward(y, st: BNStat, gamma, da, inplace=True, dg_out=None, db_out=
 
 def bn_param_grad(x2d, dy2d, st: BNStat, dg_out=None, db_out=None):
     rows, C = x2d.shape
-    dg = dg_out if dg_out is not None else _empty(C, like=x2d)
-    db = db_out if db_out is not None else _empty(C, like=x2d)
+    dg, db = _dg_db(dg_out, db_out, C, x2d)
     ws = _ws(query("tag_bn_backward_ws_bytes", rows, C), x2d)
     call("tag_bn_param_grad", ptr(x2d), ptr(dy2d), rows, C, ptr(st.mean), ptr(st.invstd), ptr(dg), ptr(db), ptr(ws))
     return dg, db
@@ -720,14 +720,20 @@ def _embed_flag(like):
     return _embed_err[key]
 
 
+def _adjacent_view(a, b, shape):
+    """The view over ``a`` and ``b`` as ONE tensor when b lies right behind a in the same storage, else None."""
+    if (a is not None and b is not None and a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype
+            and a.device == b.device and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+            and b.storage_offset() == a.storage_offset() + a.numel()):
+        return torch.empty(0, device=a.device, dtype=a.dtype).set_(a.untyped_storage(), a.storage_offset(), tuple(shape))
+    return None
+
+
 def _joined(a, b, shape):
     """``torch.cat / stack([a, b])`` as a VIEW when b lies right behind a in the same storage (runner.FlatParams lays the
     two directions of an nn.GRU out that way), else a copy: no concatenation kernels per step on the flat-parameter path."""
-    if (a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype and a.device == b.device
-            and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
-            and b.storage_offset() == a.storage_offset() + a.numel()):
-        return torch.empty(0, device=a.device, dtype=a.dtype).set_(a.untyped_storage(), a.storage_offset(), tuple(shape))
-    return torch.cat([a.reshape(-1), b.reshape(-1)]).view(*shape)
+    v = _adjacent_view(a, b, shape)
+    return v if v is not None else torch.cat([a.reshape(-1), b.reshape(-1)]).view(*shape)
 
 
 def bump_bn_counters(owner, bns):
@@ -780,15 +786,6 @@ def gru_bidir_forward(x2d, rnn, B, T, need_grad):
     wsr = _gru_ws(B, T, Hh, x2d, "fwd")
     call("tag_gru_forward", ptr(gi), ptr(w_hh), ptr(b_hh), ptr(y), ptr(gates), ptr(wsr), B, T, Hh)
     return y, (dict(gates=gates, y=y, w_ih=w_ih, w_hh=w_hh, Hh=Hh) if need_grad else None)
-
-
-def _adjacent_view(a, b, shape):
-    """The view over ``a`` and ``b`` as ONE tensor when b lies right behind a in the same storage, else None."""
-    if (a is not None and b is not None and a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype
-            and a.device == b.device and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
-            and b.storage_offset() == a.storage_offset() + a.numel()):
-        return torch.empty(0, device=a.device, dtype=a.dtype).set_(a.untyped_storage(), a.storage_offset(), tuple(shape))
-    return None
 
 
 def gru_bidir_backward(dy, x2d, sv, outs=None, side=None):
@@ -1154,8 +1151,7 @@ def bn_act_backward(x, pre_op, st: BNStat, gamma, du, dg_out=None, db_out=None):
     C = x.shape[-1]
     rows = x.numel() // C
     dx = torch.empty_like(x)
-    dg = dg_out if dg_out is not None else _empty(C, like=x)
-    db = db_out if db_out is not None else _empty(C, like=x)
+    dg, db = _dg_db(dg_out, db_out, C, x)
     ws = _ws(query("tag_bn_backward_ws_bytes", rows, C), x)
     call("tag_bn_act_backward", ptr(x), pre_op, ptr(st.mean), ptr(st.invstd), ptr(gamma), ptr(du), ptr(dx), ptr(dg),
          ptr(db), rows, C, int(st.train), ptr(ws))
@@ -1365,8 +1361,7 @@ def bias_bnrelu_pool_backward(y, st: BNStat, gamma, bias, dout, ph, pw, pool=0, 
     """-> (dy, dgamma, dbeta, clip): clip (B, 2, C) fp64 = [sum dz | sum dz*xhat] of each clip (dz: gradient at bn(y) + bias)."""
     B, H, W, C = y.shape
     dy = torch.empty_like(y)
-    dg = dg_out if dg_out is not None else _empty(C, like=y)
-    db = db_out if db_out is not None else _empty(C, like=y)
+    dg, db = _dg_db(dg_out, db_out, C, y)
     ws, clip = _clip_ws(B, C, y)
     call("tag_bias_bnrelu_pool_backward", ptr(y), ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(st.invstd), ptr(gamma),
          ptr(bias), ptr(dout), ptr(dy), ptr(dg), ptr(db), ptr(clip), B, H, W, C, ph, pw, int(pool), float(drop_p), seed,
@@ -1379,8 +1374,7 @@ def bias_bnrelu_backward(y, st: BNStat, gamma, bias, da, prev=None, want_dt=True
     prev's (the clip sums bias_bnrelu_pool_backward returned for the block's other site), or None."""
     B, H, W, C = y.shape
     dy = torch.empty_like(y)
-    dg = dg_out if dg_out is not None else _empty(C, like=y)
-    db = db_out if db_out is not None else _empty(C, like=y)
+    dg, db = _dg_db(dg_out, db_out, C, y)
     dt = _empty(B, C, like=y) if want_dt else None
     ws, clip = _clip_ws(B, C, y)
     call("tag_bias_bnrelu_backward", ptr(y), ptr(st.scale), ptr(st.shift), ptr(st.mean), ptr(st.invstd), ptr(gamma), ptr(bias),
@@ -1481,8 +1475,7 @@ def bn_act_backward_clip(x, pre_op, st: BNStat, gamma, du, dg_out=None, db_out=N
     B, C = x.shape[0], x.shape[-1]
     rows = x.numel() // C
     dx, dt = torch.empty_like(x), _empty(B, C, like=x)
-    dg = dg_out if dg_out is not None else _empty(C, like=x)
-    db = db_out if db_out is not None else _empty(C, like=x)
+    dg, db = _dg_db(dg_out, db_out, C, x)
     ws = _ws(query("tag_bn_backward_ws_bytes", rows, C), x)
     wsc, clip = _clip_ws(B, C, x)
     call("tag_bn_act_backward_clip", ptr(x), pre_op, ptr(st.mean), ptr(st.invstd), ptr(gamma), ptr(du), ptr(dx), ptr(dg), ptr(db),

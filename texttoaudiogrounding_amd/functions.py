@@ -1,6 +1,15 @@
 """torch.autograd nodes of the hot path: forward() / backward() of each node are sequences of dispatch.py launches; parameter
-gradients are delivered through engine.py's direct-gradient sinks.  Cnn8RnnFunction (the whole audio encoder as one node) and its
-weight-gradient side-stream helper, CrnnFunction, the text / match / loss heads, the cross-encoder nodes.
+gradients are delivered through engine.py's direct-gradient sinks.  The four whole-encoder nodes state each launch plan once:
+
+* Cnn8 family -- Cnn8RnnFunction and the early-fusion CrossCnn8RnnFunction share the set-up, the stem (logmel, bn0, augment, the
+  Cin = 1 conv), the tail (mean over W, fc1) and the per-block epilogue (_cnn8_*); their block middles are different algorithms
+  (fused BatchNorm / pool epilogues against per-clip bias passes) and stay apart.  ConvTextBlockFunction runs
+  CrossCnn8RnnFunction's text-block forward (_text_block_forward).
+* CDur family -- CrnnFunction and the early-fusion CrossCDurFunction are thin callers of _cdur_forward / _cdur_backward, which
+  walk the five-block table CDUR_POOLS without or with the text biases; CDurTextBlockFunction shares their kernel choice
+  (_cdur_conv) and the scalar-bn0 backward (_scalar_bn_backward).
+
+Then the weight-gradient side-stream helper, the text / match / loss heads and the cross-encoder nodes.
 """
 from __future__ import annotations
 
@@ -29,7 +38,7 @@ from .dispatch import text_selfattn_backward, text_selfattn_forward
 from . import engine
 
 # ------------------------------------------------------------------------------------------------
-# Cnn8Rnn: the whole audio encoder as one autograd node (rows F1-F3, A1-A4 forward + backward)
+# Cnn8Rnn and the early-fusion CrossCnn8_Rnn: the whole audio encoder as one autograd node (rows F1-F3, A1-A4 forward + backward)
 # ------------------------------------------------------------------------------------------------
 
 CNN8_POOLS = [(2, 2), (2, 2), (1, 2), (1, 2)]
@@ -103,6 +112,79 @@ class _SideWgrad:
             self.keep = []                               # released on the main stream, ordered after the wait
 
 
+def _cnn8_begin(waveform, mod, params):
+    """What both Cnn8 nodes do before their first launch: input checks, detached parameters (bn0.w, bn0.b, 4 x (conv1.w,
+    bn1.w, bn1.b, conv2.w, bn2.w, bn2.b), fc1.w, fc1.b, 8 GRU tensors, ...), dropout probabilities and the five seeds."""
+    wave = _chk(waveform, "waveform")
+    check_pass_size(wave.shape[0], wave.shape[1] // mod.hop_length + 1)
+    training = mod.training
+    p = [_chk(t.detach(), "parameter") for t in params]
+    drop = mod.dropout_p if training else (0.0, 0.0)
+    seeds = [new_seed() for _ in range(5)] if training and (drop[0] > 0 or drop[1] > 0) else [0] * 5
+    return wave, p, training and not mod.freeze_bn, drop, seeds
+
+
+def _cnn8_stem_forward(wave, mod, p, bn_train, aug, out_dtype=F32):
+    """logmel -> bn0 statistics -> [augment] -> conv_block1.conv1.  ``aug`` (ctx.augment): bn0 is then applied by augment_forward
+    into x0 (B or B/2 clips) instead of inside the Cin = 1 convolution; bn0's statistics stay over all B clips.
+    -> (lm, st0, x0, y1, part1)."""
+    lm = logmel(wave, mod.n_fft, mod.win_length, mod.hop_length, mod.window, mod.mel_fb)   # (B,F,64)
+    B, Fr, NM = lm.shape
+    st0 = bn_stats(lm.view(B * Fr, NM), p[0], p[1], mod.bn0.running_mean, mod.bn0.running_var, bn_train, mod.bn0.eps,
+                   mod.bn0.momentum)
+    if aug is None:
+        x0 = None
+        y1, part1 = conv3x3_c1_stats(lm, p[2], st0.scale, st0.shift, want_stats=bn_train, out_dtype=out_dtype)
+    else:
+        x0 = augment_forward(lm, st0.scale, st0.shift, *aug)                                 # (B',F,64), bn0 applied
+        y1, part1 = conv3x3_c1_stats(x0, p[2], None, None, want_stats=bn_train, out_dtype=out_dtype)
+    return lm, st0, x0, y1, part1
+
+
+def _cnn8_tail_forward(x, fc_w, fc_b, drop_p, seed, act):
+    """Mean over W (with its dropout) and fc1: x (B,T',W',C) -> xm (B*T', C), fc = act(xm fc_w^T + fc_b)."""
+    Bx, Tp, Wp, C = x.shape
+    xm = _empty(Bx * Tp, C, like=x)
+    call("tag_mean_w_forward" + _sfx(x), ptr(x), Bx * Tp, Wp, C, float(drop_p), seed, ptr(xm))
+    return xm, gemm(xm, fc_w, Bx * Tp, fc_w.shape[0], C, transB=True, bias=fc_b, act=act)
+
+
+def _cnn8_tail_backward(dfc, fc_w, x_last, drop_p, seed):
+    """fc1's input gradient and the backward of the mean over W: -> dx, shaped like the last block's output x_last."""
+    M = dfc.shape[0]
+    dxm = gemm(dfc, fc_w, M, fc_w.shape[1], fc_w.shape[0])
+    Bx, Tp, Wp, C = x_last.shape
+    dx = torch.empty_like(x_last)
+    call("tag_mean_w_backward" + _sfx(dx), ptr(dxm), Bx * Tp, Wp, C, float(drop_p), seed, ptr(dx))
+    return dx
+
+
+def _cnn8_stem_backward(sv, dy1, grads, sk, bn_bwd=None):
+    """Backward of conv_block1.conv1 [and augment] and bn0's parameter gradients; delivers parameters 2, 0 and 1.
+    bn_bwd: see conv3x3_c1_backward (the deferred BatchNorm + ReLU backward of bn1)."""
+    lm, st0, x0 = sv["lm"], sv["st0"], sv["x0"]
+    if x0 is None:
+        dw0, dbn0 = conv3x3_c1_backward(lm, dy1, sv["p"][2], st0.scale, st0.shift, out=sk[2], bn_bwd=bn_bwd)   # dbn0: (B,F,64)
+    else:
+        dw0, dx0 = conv3x3_c1_backward(x0, dy1, sv["p"][2], None, None, out=sk[2], bn_bwd=bn_bwd)
+        dbn0 = augment_backward(dx0, lm.shape[0], *sv["aug"])
+        del dx0
+    _deliver(grads, sk, 2, dw0)
+    Bq, Fr, NM = lm.shape
+    dg0, db0 = bn_param_grad(lm.view(Bq * Fr, NM), dbn0.view(Bq * Fr, NM), st0, dg_out=sk[0], db_out=sk[1])
+    _deliver(grads, sk, 0, dg0)
+    _deliver(grads, sk, 1, db0)
+
+
+def _cnn8_block_done(sw, prm, i):
+    """End of block i's backward: every gradient kernel of the block is enqueued before its parameters are announced."""
+    sw.release()
+    if prm is not None:
+        o = 2 + 6 * i
+        _ready(prm[o:o + 6] + ((prm[0], prm[1]) if i == 0 else ()))
+        _flush()
+
+
 class Cnn8RnnFunction(TagFunction):
     """params order: bn0.w, bn0.b, 4 x (conv1.w, bn1.w, bn1.b, conv2.w, bn2.w, bn2.b), fc1.w, fc1.b,
     rnn (w_ih, w_hh, b_ih, b_hh) x (fwd, reverse).
@@ -114,38 +196,16 @@ class Cnn8RnnFunction(TagFunction):
 
     @staticmethod
     def forward(ctx, waveform, mod, *params):
-        wave = _chk(waveform, "waveform")
-        check_pass_size(wave.shape[0], wave.shape[1] // mod.hop_length + 1)
-        training = mod.training
-        bn_train = training and not mod.freeze_bn
-        p = [_chk(t.detach(), "parameter") for t in params]
-        bn0_w, bn0_b = p[0], p[1]
-        blocks = [p[2 + 6 * i: 8 + 6 * i] for i in range(4)]
-        fc_w, fc_b = p[26], p[27]
-        rnn = p[28:36]
-        drop = mod.dropout_p if training else (0.0, 0.0)
-        seeds = [new_seed() for _ in range(5)] if training and (drop[0] > 0 or drop[1] > 0) else [0] * 5
+        wave, p, bn_train, drop, seeds = _cnn8_begin(waveform, mod, params)
         need_grad = any(ctx.needs_input_grad[2:])
         aug = getattr(ctx, "augment", None)
-
-        lm = logmel(wave, mod.n_fft, mod.win_length, mod.hop_length, mod.window, mod.mel_fb)   # (B,F,64)
-        B, Fr, NM = lm.shape
-        st0 = bn_stats(lm.view(B * Fr, NM), bn0_w, bn0_b, mod.bn0.running_mean, mod.bn0.running_var, bn_train,
-                       mod.bn0.eps, mod.bn0.momentum)
-        x0 = augment_forward(lm, st0.scale, st0.shift, *aug) if aug is not None else None     # (B',F,64), bn0 applied
-        x = None
+        lm, st0, x0, y1, part1 = _cnn8_stem_forward(wave, mod, p, bn_train, aug, out_dtype=BF16 if act_bf16() else F32)
+        x = wd1 = None
         acts = []
-        for i, (c1w, g1, b1, c2w, g2, b2) in enumerate(blocks):
+        for i in range(4):
+            c1w, g1, b1, c2w, g2, b2 = p[2 + 6 * i: 8 + 6 * i]
             blk = getattr(mod, f"conv_block{i + 1}")
-            if i == 0:
-                if x0 is None:
-                    y1, part1 = conv3x3_c1_stats(lm, c1w, st0.scale, st0.shift, want_stats=bn_train,
-                                                 out_dtype=BF16 if act_bf16() else F32)
-                else:
-                    y1, part1 = conv3x3_c1_stats(x0, c1w, None, None, want_stats=bn_train,
-                                                 out_dtype=BF16 if act_bf16() else F32)
-                wf1 = wd1 = None
-            else:
+            if i > 0:
                 wf1, wd1 = pack_conv_weight(c1w, want_dgrad=need_grad, W=x.shape[2])
                 y1, part1 = conv3x3_stats(x, wf1, c1w.shape[0], want_stats=bn_train,
                                           inference=not need_grad and not bn_train and drop[0] == 0.0)
@@ -167,12 +227,8 @@ class Cnn8RnnFunction(TagFunction):
             if need_grad:                      # inference: intermediates die here (30 s clips x 64 are GBs per layer)
                 acts.append((x, y1, s1, y2, s2, wd1, wd2))
             x = xo
-        Bx, Tp, Wp, C = x.shape
-        xm = _empty(Bx * Tp, C, like=x)
-        call("tag_mean_w_forward" + _sfx(x), ptr(x), Bx * Tp, Wp, C, float(drop[1]), seeds[4], ptr(xm))
-        M = Bx * Tp
-        fc = gemm(xm, fc_w, M, fc_w.shape[0], C, transB=True, bias=fc_b, act=1)
-        y, gsave = gru_bidir_forward(fc, rnn, Bx, Tp, need_grad)
+        xm, fc = _cnn8_tail_forward(x, p[26], p[27], drop[1], seeds[4], act=1)
+        y, gsave = gru_bidir_forward(fc, p[28:36], x.shape[0], x.shape[1], need_grad)
         if need_grad:
             ctx.saved = dict(lm=lm, st0=st0, aug=aug, x0=x0, acts=acts, x_last=x, xm=xm, fc=fc, gsave=gsave, p=p, drop=drop,
                              seeds=seeds, sinks=_sinks(params), params=params if cfg.DIRECT_GRADS else None)
@@ -216,13 +272,8 @@ class Cnn8RnnFunction(TagFunction):
             # GRU takes a gradient and the waveform never does -- the conv stack's backward (97 % of the step) is not run
             sw.join()
             return (None, None, *grads)
-        dxm = gemm(dfc, fc_w, M, fc_w.shape[1], fc_w.shape[0])
-        x_last = sv["x_last"]
-        Bx, Tp, Wp, C = x_last.shape
-        dx = torch.empty_like(x_last)
-        call("tag_mean_w_backward" + _sfx(dx), ptr(dxm), Bx * Tp, Wp, C, float(drop[1]), seeds[4], ptr(dx))
+        dx = _cnn8_tail_backward(dfc, fc_w, sv["x_last"], drop[1], seeds[4])
         # ---- conv blocks, last to first ----
-        lm, st0 = sv["lm"], sv["st0"]
         poolpart = None                            # sums of block i's pool backward, taken by block i+1's dgrad conv
         for i in range(3, -1, -1):
             x_in, y1, s1, y2, s2, wd1, wd2 = sv["acts"][i]
@@ -258,35 +309,38 @@ class Cnn8RnnFunction(TagFunction):
                     dx = conv3x3(dy1, wd1, x_in.shape[3])
                 sw.release()
             else:
-                x0, aug = sv["x0"], sv["aug"]
-                if x0 is None:
-                    dw0, dbn0 = conv3x3_c1_backward(lm, dy1, c1w, st0.scale, st0.shift, out=sk[2],   # dbn0: (B,F,64) grad wrt bn0 output
-                                                    bn_bwd=None if applied else (y1, s1, g1, dg1, db1))
-                else:
-                    dw0, dx0 = conv3x3_c1_backward(x0, dy1, c1w, None, None, out=sk[2],
-                                                   bn_bwd=None if applied else (y1, s1, g1, dg1, db1))
-                    dbn0 = augment_backward(dx0, lm.shape[0], *aug)
-                    del dx0
-                _deliver(grads, sk, 2, dw0)
-                Bq, Fr, NM = lm.shape
-                dg0, db0 = bn_param_grad(lm.view(Bq * Fr, NM), dbn0.view(Bq * Fr, NM), st0, dg_out=sk[0], db_out=sk[1])
-                _deliver(grads, sk, 0, dg0)
-                _deliver(grads, sk, 1, db0)
+                _cnn8_stem_backward(sv, dy1, grads, sk, bn_bwd=None if applied else (y1, s1, g1, dg1, db1))
             del dy1
             sv["acts"][i] = None
-            sw.release()                           # every gradient kernel of this block is enqueued before _ready
-            if prm is not None:
-                _ready(prm[o:o + 6] + ((prm[0], prm[1]) if i == 0 else ()))
-                _flush()
+            _cnn8_block_done(sw, prm, i)
         sw.join()
         return (None, None, *grads)
 
 
+def _check_fp32_only(model):
+    if cfg.CONV_MATH != "fp32" or act_bf16() or gemm_bf16():
+        raise RuntimeError(f"{model} supports fp32 arithmetic only (CONV_MATH 'fp32', fp32 activations and GEMMs); got "
+                           f"CONV_MATH {cfg.CONV_MATH!r}, ACT_DTYPE {cfg.ACT_DTYPE!r}, GEMM_MATH {cfg.GEMM_MATH!r}")
+
+
 def check_cross_precision():
     """CrossCnn8_Rnn runs in fp32 only: its per-clip bias passes have no bf16 or split-fp32 (x3) form."""
-    if cfg.CONV_MATH != "fp32" or act_bf16() or gemm_bf16():
-        raise RuntimeError(f"CrossCnn8_Rnn supports fp32 arithmetic only (CONV_MATH 'fp32', fp32 activations and GEMMs); got "
-                           f"CONV_MATH {cfg.CONV_MATH!r}, ACT_DTYPE {cfg.ACT_DTYPE!r}, GEMM_MATH {cfg.GEMM_MATH!r}")
+    _check_fp32_only("CrossCnn8_Rnn")
+
+
+def _text_block_forward(y1, part1, prm, bns, train, t, ph, pw, pool=0, drop_p=0.0, seed=0, want_dgrad=True):
+    """A ConvTextBlock behind its first convolution (raw output y1 with the statistics partials the conv wrote):
+    pool(relu(bn2(conv2(relu(bn1(y1) + t))) + t)) [with dropout] -> (out, (s1, a1, y2, s2, wd2)).  prm = (conv1.w, bn1.w, bn1.b,
+    conv2.w, bn2.w, bn2.b), bns = (bn1, bn2) (their running statistics are updated where ``train`` says so)."""
+    _, g1, b1, c2w, g2, b2 = prm
+    (bn1, bn2), (train1, train2) = bns, train
+    C = y1.shape[3]
+    s1 = bn_stats(y1.view(-1, C), g1, b1, bn1.running_mean, bn1.running_var, train1, bn1.eps, bn1.momentum, partials=part1)
+    a1 = bias_bnrelu_forward(y1, s1, t)                              # relu(bn1(conv1(x)) + t), written out
+    wf2, wd2 = pack_conv_weight(c2w, want_dgrad=want_dgrad, W=a1.shape[2])
+    y2, part2 = conv3x3_stats(a1, wf2, C, want_stats=train2)
+    s2 = bn_stats(y2.view(-1, C), g2, b2, bn2.running_mean, bn2.running_var, train2, bn2.eps, bn2.momentum, partials=part2)
+    return bias_bnrelu_pool(y2, s2, t, ph, pw, pool=pool, drop_p=drop_p, seed=seed), (s1, a1, y2, s2, wd2)
 
 
 class CrossCnn8RnnFunction(TagFunction):
@@ -295,77 +349,48 @@ class CrossCnn8RnnFunction(TagFunction):
     (B, 512): differentiable inputs, so autograd sums their six gradients into the text embedding.
 
     params order: bn0.w, bn0.b, 4 x (conv1.w, bn1.w, bn1.b, conv2.w, bn2.w, bn2.b), fc1.w, fc1.b, rnn (w_ih, w_hh, b_ih, b_hh)
-    x (fwd, reverse), fc_output.w, fc_output.b.  The conv / BatchNorm-statistics / GRU / GEMM launches are Cnn8RnnFunction's;
-    the text bias enters through the per-clip bias passes (dispatch.bias_*), so the conv kernels' fused BatchNorm epilogues
-    (which assume a per-channel shift) are not used.  ``ctx.augment``: (stripes, n_time, None) as in Cnn8RnnFunction."""
+    x (fwd, reverse), fc_output.w, fc_output.b.  The stem, the tail and the conv / BatchNorm-statistics / GRU / GEMM launches
+    are Cnn8RnnFunction's; the text bias enters through the per-clip bias passes (dispatch.bias_*), so the conv kernels' fused
+    BatchNorm epilogues (which assume a per-channel shift) are not used.  ``ctx.augment``: (stripes, n_time, None) as in
+    Cnn8RnnFunction."""
 
     @staticmethod
     def forward(ctx, waveform, mod, t1, t2, t3, t4, u, r, *params):
         check_cross_precision()
-        wave = _chk(waveform, "waveform")
-        check_pass_size(wave.shape[0], wave.shape[1] // mod.hop_length + 1)
-        training = mod.training
-        bn_train = training and not mod.freeze_bn
-        p = [_chk(t.detach(), "parameter") for t in params]
+        wave, p, bn_train, drop, seeds = _cnn8_begin(waveform, mod, params)
         texts = [_chk(t.detach(), "text bias") for t in (t1, t2, t3, t4)]
         u_, r_ = _chk(u.detach(), "fc1_text"), _chk(r.detach(), "rnn_text")
-        bn0_w, bn0_b = p[0], p[1]
-        blocks = [p[2 + 6 * i: 8 + 6 * i] for i in range(4)]
-        fc_w, fc_b = p[26], p[27]
-        rnn = p[28:36]
-        wo, bo = p[36], p[37]
-        drop = mod.dropout_p if training else (0.0, 0.0)
-        seeds = [new_seed() for _ in range(5)] if training and (drop[0] > 0 or drop[1] > 0) else [0] * 5
         need_grad = any(ctx.needs_input_grad[2:])
         aug = getattr(ctx, "augment", None)
-
-        lm = logmel(wave, mod.n_fft, mod.win_length, mod.hop_length, mod.window, mod.mel_fb)   # (B,F,64)
-        B, Fr, NM = lm.shape
+        B = wave.shape[0]
         for i, t in enumerate(texts + [u_, r_]):
             if t.dim() != 2 or t.shape[0] != B:
                 raise RuntimeError(f"CrossCnn8_Rnn: text bias {i} has shape {tuple(t.shape)}, expected ({B}, channels)")
-        st0 = bn_stats(lm.view(B * Fr, NM), bn0_w, bn0_b, mod.bn0.running_mean, mod.bn0.running_var, bn_train,
-                       mod.bn0.eps, mod.bn0.momentum)
-        x0 = augment_forward(lm, st0.scale, st0.shift, *aug) if aug is not None else None     # (B,F,64), bn0 applied
-        x = None
+        for i, t in enumerate(texts):
+            if t.shape[1] != p[2 + 6 * i].shape[0]:
+                raise RuntimeError(f"CrossCnn8_Rnn: conv_block{i + 1} text bias has {t.shape[1]} channels, expected "
+                                   f"{p[2 + 6 * i].shape[0]}")
+        lm, st0, x0, y1, part1 = _cnn8_stem_forward(wave, mod, p, bn_train, aug)
+        x = wd1 = None
         acts = []
-        for i, (c1w, g1, b1, c2w, g2, b2) in enumerate(blocks):
+        for i in range(4):
+            prm = p[2 + 6 * i: 8 + 6 * i]
             blk = getattr(mod, f"conv_block{i + 1}")
-            t = texts[i]
-            if i == 0:
-                if x0 is None:
-                    y1, part1 = conv3x3_c1_stats(lm, c1w, st0.scale, st0.shift, want_stats=bn_train)
-                else:
-                    y1, part1 = conv3x3_c1_stats(x0, c1w, None, None, want_stats=bn_train)
-                wd1 = None
-            else:
-                wf1, wd1 = pack_conv_weight(c1w, want_dgrad=need_grad, W=x.shape[2])
-                y1, part1 = conv3x3_stats(x, wf1, c1w.shape[0], want_stats=bn_train)
-            C = y1.shape[3]
-            if t.shape[1] != C:
-                raise RuntimeError(f"CrossCnn8_Rnn: conv_block{i + 1} text bias has {t.shape[1]} channels, expected {C}")
-            s1 = bn_stats(y1.view(-1, C), g1, b1, blk.bn1.running_mean, blk.bn1.running_var, bn_train, blk.bn1.eps,
-                          blk.bn1.momentum, partials=part1)
-            a1 = bias_bnrelu_forward(y1, s1, t)                          # relu(bn1(conv1(x)) + t), written out
-            wf2, wd2 = pack_conv_weight(c2w, want_dgrad=need_grad, W=a1.shape[2])
-            y2, part2 = conv3x3_stats(a1, wf2, C, want_stats=bn_train)
-            s2 = bn_stats(y2.view(-1, C), g2, b2, blk.bn2.running_mean, blk.bn2.running_var, bn_train, blk.bn2.eps,
-                          blk.bn2.momentum, partials=part2)
-            ph, pw = CNN8_POOLS[i]
-            xo = bias_bnrelu_pool(y2, s2, t, ph, pw, pool=0, drop_p=drop[0], seed=seeds[i])
+            if i > 0:
+                wf1, wd1 = pack_conv_weight(prm[0], want_dgrad=need_grad, W=x.shape[2])
+                y1, part1 = conv3x3_stats(x, wf1, prm[0].shape[0], want_stats=bn_train)
+            xo, (s1, a1, y2, s2, wd2) = _text_block_forward(y1, part1, prm, (blk.bn1, blk.bn2), (bn_train, bn_train), texts[i],
+                                                            *CNN8_POOLS[i], drop_p=drop[0], seed=seeds[i], want_dgrad=need_grad)
             if need_grad:
                 acts.append((x, y1, s1, a1, y2, s2, wd1, wd2))
             del a1
             x = xo
-        Bx, Tp, Wp, C = x.shape
-        xm = _empty(Bx * Tp, C, like=x)
-        call("tag_mean_w_forward", ptr(x), Bx * Tp, Wp, C, float(drop[1]), seeds[4], ptr(xm))
-        M = Bx * Tp
-        fc = gemm(xm, fc_w, M, fc_w.shape[0], C, transB=True, bias=fc_b)
+        Bx, Tp = x.shape[0], x.shape[1]
+        xm, fc = _cnn8_tail_forward(x, p[26], p[27], drop[1], seeds[4], act=0)
         h = rowgroup_bias_relu(fc, u_, Tp, out=fc)                       # relu(fc1(x) + fc1_text(e)), in place
-        y, gsave = gru_bidir_forward(h, rnn, Bx, Tp, need_grad)
-        y2d = y.reshape(M, -1)
-        prob, sig = frame_head_forward(y2d, r_, wo.reshape(-1), bo, Tp)
+        y, gsave = gru_bidir_forward(h, p[28:36], Bx, Tp, need_grad)
+        y2d = y.reshape(Bx * Tp, -1)
+        prob, sig = frame_head_forward(y2d, r_, p[36].reshape(-1), p[37], Tp)
         if need_grad:
             ctx.saved = dict(lm=lm, st0=st0, aug=aug, x0=x0, acts=acts, x_last=x, xm=xm, h=h, gsave=gsave, y=y2d, sig=sig,
                              texts=texts, u=u_, r=r_, p=p, drop=drop, seeds=seeds, sinks=_sinks(params),
@@ -411,16 +436,11 @@ class CrossCnn8RnnFunction(TagFunction):
             # included -- the conv stack's backward is not run
             sw.join()
             return (None, None, *dtexts, du, dr, *grads)
-        dxm = gemm(dfc, fc_w, M, fc_w.shape[1], fc_w.shape[0])
-        x_last = sv["x_last"]
-        Bx, Tp, Wp, C = x_last.shape
-        dx = torch.empty_like(x_last)
-        call("tag_mean_w_backward", ptr(dxm), Bx * Tp, Wp, C, float(drop[1]), seeds[4], ptr(dx))
-        lm, st0 = sv["lm"], sv["st0"]
+        dx = _cnn8_tail_backward(dfc, fc_w, sv["x_last"], drop[1], seeds[4])
         texts = sv["texts"]
         for i in range(3, -1, -1):
             x_in, y1, s1, a1, y2, s2, wd1, wd2 = sv["acts"][i]
-            c1w, g1, b1, c2w, g2, b2 = p[2 + 6 * i: 8 + 6 * i]
+            g1, g2 = p[3 + 6 * i], p[6 + 6 * i]
             o = 2 + 6 * i
             ph, pw = CNN8_POOLS[i]
             t = texts[i]
@@ -442,59 +462,40 @@ class CrossCnn8RnnFunction(TagFunction):
                 dx = conv3x3(dy1, wd1, x_in.shape[3])
                 sw.release()
             else:
-                x0, aug = sv["x0"], sv["aug"]
-                if x0 is None:
-                    dw0, dbn0 = conv3x3_c1_backward(lm, dy1, c1w, st0.scale, st0.shift, out=sk[2], bn_bwd=None)
-                else:
-                    dw0, dx0 = conv3x3_c1_backward(x0, dy1, c1w, None, None, out=sk[2], bn_bwd=None)
-                    dbn0 = augment_backward(dx0, lm.shape[0], *aug)
-                    del dx0
-                _deliver(grads, sk, 2, dw0)
-                Bq, Fr, NM = lm.shape
-                dg0, db0 = bn_param_grad(lm.view(Bq * Fr, NM), dbn0.view(Bq * Fr, NM), st0, dg_out=sk[0], db_out=sk[1])
-                _deliver(grads, sk, 0, dg0)
-                _deliver(grads, sk, 1, db0)
+                _cnn8_stem_backward(sv, dy1, grads, sk)
             del dy1
             sv["acts"][i] = None
-            sw.release()
-            if prm is not None:
-                _ready(prm[o:o + 6] + ((prm[0], prm[1]) if i == 0 else ()))
-                _flush()
+            _cnn8_block_done(sw, prm, i)
         sw.join()
         return (None, None, *dtexts, du, dr, *grads)
 
 
 class ConvTextBlockFunction(TagFunction):
     """ConvTextBlock.forward on its own (models/audio_text_model.py:614-636): channels-last x (B,H,W,Cin), t = fc_text(text)
-    (B, C) -> dropout-free pool(relu(bn2(conv2(relu(bn1(conv1(x)) + t))) + t)) (B, H/ph, W/pw, C); the passes of
-    CrossCnn8RnnFunction's blocks.  ``bns`` = (bn1, bn2): their running statistics are updated in train mode."""
+    (B, C) -> dropout-free pool(relu(bn2(conv2(relu(bn1(conv1(x)) + t))) + t)) (B, H/ph, W/pw, C); the forward passes are
+    CrossCnn8RnnFunction's (_text_block_forward).  ``bns`` = (bn1, bn2): their running statistics are updated in train mode."""
 
     @staticmethod
     def forward(ctx, x, t, bns, ph, pw, pool, c1w, g1, b1, c2w, g2, b2):
         check_cross_precision()
         x, t_ = _chk(x, "x"), _chk(t.detach(), "text bias")
-        c1w, g1, b1, c2w, g2, b2 = (_chk(v.detach(), "parameter") for v in (c1w, g1, b1, c2w, g2, b2))
-        bn1, bn2 = bns
+        prm = [_chk(v.detach(), "parameter") for v in (c1w, g1, b1, c2w, g2, b2)]
+        c1w = prm[0]
+        train = (bns[0].training, bns[1].training)
         B, H, W, Cin = x.shape
         C = c1w.shape[0]
         if t_.shape != (B, C):
             raise RuntimeError(f"ConvTextBlock: text bias of shape {tuple(t_.shape)}, expected {(B, C)}")
-        train1, train2 = bn1.training, bn2.training
         if Cin == 1:
-            y1, part1 = conv3x3_c1_stats(x.view(B, H, W), c1w, want_stats=train1)
+            y1, part1 = conv3x3_c1_stats(x.view(B, H, W), c1w, want_stats=train[0])
             wd1 = None
         elif Cin % 32 == 0:
             wf1, wd1 = pack_conv_weight(c1w, want_dgrad=True, W=W)
-            y1, part1 = conv3x3_stats(x, wf1, C, want_stats=train1)
+            y1, part1 = conv3x3_stats(x, wf1, C, want_stats=train[0])
         else:
             raise RuntimeError(f"ConvTextBlock: in_channels must be 1 or a multiple of 32, got {Cin}")
-        s1 = bn_stats(y1.view(-1, C), g1, b1, bn1.running_mean, bn1.running_var, train1, bn1.eps, bn1.momentum, partials=part1)
-        a1 = bias_bnrelu_forward(y1, s1, t_)
-        wf2, wd2 = pack_conv_weight(c2w, want_dgrad=True, W=W)
-        y2, part2 = conv3x3_stats(a1, wf2, C, want_stats=train2)
-        s2 = bn_stats(y2.view(-1, C), g2, b2, bn2.running_mean, bn2.running_var, train2, bn2.eps, bn2.momentum, partials=part2)
-        out = bias_bnrelu_pool(y2, s2, t_, ph, pw, pool=pool)
-        ctx.saved = (x, t_, y1, s1, a1, y2, s2, wd1, wd2, c1w, g1, g2, ph, pw, pool)
+        out, (s1, a1, y2, s2, wd2) = _text_block_forward(y1, part1, prm, bns, train, t_, ph, pw, pool=pool)
+        ctx.saved = (x, t_, y1, s1, a1, y2, s2, wd1, wd2, c1w, prm[1], prm[4], ph, pw, pool)
         return out
 
     @staticmethod
@@ -536,126 +537,197 @@ class SpecAugmentFunction(TagFunction):
 
 
 # ------------------------------------------------------------------------------------------------
-# CrnnEncoder (row A1'): cdur_block = BN -> conv3x3 -> LeakyReLU(0.1), LPPool2d(4), Dropout(0.3), BiGRU(128)
+# CrnnEncoder (row A1') and the early-fusion CrossCDur: cdur_block = BN -> conv3x3 -> LeakyReLU(0.1), LPPool2d(4),
+# Dropout(0.3), BiGRU(128) -- one forward body and one backward body, without and with the per-clip text biases
 # ------------------------------------------------------------------------------------------------
-CRNN_POOLS = [(2, 4), (2, 4), (1, 4)]
-
-
-class CrnnFunction(TagFunction):
-    """params order: 5 x (bn.w, bn.b, conv.w) for cnn.{0,2,3,5,6}, then gru (w_ih, w_hh, b_ih, b_hh) x (fwd, reverse).
-
-    Layer plan (channels-last): lm -> [bn0 scalar | conv 1->32] -> LP(2,4) -> [bn | conv 32->128] -> [leaky,bn | conv]
-    -> LP(2,4) -> [bn | conv] -> [leaky,bn | conv] -> LP(1,4)+dropout -> GRU.  Every BatchNorm is folded into the
-    A-operand load of the conv that follows it (prologue 3 after a pool, prologue 2 after a conv)."""
-
-    @staticmethod
-    def forward(ctx, waveform, mod, *params):
-        wave = _chk(waveform, "waveform")
-        training = mod.training
-        p = [_chk(t.detach(), "parameter") for t in params]
-        blk = [p[3 * i: 3 * i + 3] for i in range(5)]
-        rnn = p[15:23]
-        bns = mod._bn_modules()
-        drop = mod.dropout_p if training else 0.0
-        seed = new_seed() if training and drop > 0 else 0
-
-        lm = logmel(wave, mod.n_fft, mod.win_length, mod.hop_length, mod.window, mod.mel_fb)   # (B,F,64)
-        B, Fr, NM = lm.shape
-
-        def stats(x2d, i, pre_op):
-            return bn_stats(x2d, blk[i][0], blk[i][1], bns[i].running_mean, bns[i].running_var, training, bns[i].eps,
-                            bns[i].momentum, pre_op)
-
-        st = [None] * 5
-        st[0] = stats(lm.view(-1, 1), 0, 0)                       # BatchNorm2d(1): one scalar affine
-        cs, ct = st[0].scale.expand(NM).contiguous(), st[0].shift.expand(NM).contiguous()
-        y0 = conv3x3_c1(lm, blk[0][2], cs, ct)                     # (B,F,64,32)
-        p1 = bnact_pool(y0, None, 2, 4, act=2, pool=1)            # leaky + LPPool -> (B,F/2,16,32)
-        st[1] = stats(p1.view(-1, p1.shape[3]), 1, 0)
-        wf1, wd1 = pack_conv_weight(blk[1][2], W=p1.shape[2])
-        y1 = conv3x3(p1, wf1, 128, prologue=3, scale=st[1].scale, shift=st[1].shift)
-        st[2] = stats(y1.view(-1, 128), 2, 1)
-        wf2, wd2 = pack_conv_weight(blk[2][2], W=y1.shape[2])
-        y2 = conv3x3(y1, wf2, 128, prologue=2, scale=st[2].scale, shift=st[2].shift)
-        p2 = bnact_pool(y2, None, 2, 4, act=2, pool=1)            # (B,F/4,4,128)
-        st[3] = stats(p2.view(-1, 128), 3, 0)
-        wf3, wd3 = pack_conv_weight(blk[3][2], W=p2.shape[2])
-        y3 = conv3x3(p2, wf3, 128, prologue=3, scale=st[3].scale, shift=st[3].shift)
-        st[4] = stats(y3.view(-1, 128), 4, 1)
-        wf4, wd4 = pack_conv_weight(blk[4][2], W=y3.shape[2])
-        y4 = conv3x3(y3, wf4, 128, prologue=2, scale=st[4].scale, shift=st[4].shift)
-        p3 = bnact_pool(y4, None, 1, 4, act=2, pool=1, drop_p=drop, seed=seed)     # (B,T',1,128)
-        Bx, Tp = p3.shape[0], p3.shape[1]
-        x2d = p3.view(Bx * Tp, -1)
-        need_grad = any(ctx.needs_input_grad[2:])
-        y, gsave = gru_bidir_forward(x2d, rnn, Bx, Tp, need_grad)
-        if need_grad:
-            ctx.saved = dict(lm=lm, cs=cs, ct=ct, st=st, y=[y0, y1, y2, y3, y4], pool=[p1, p2, p3], wd=[wd1, wd2, wd3, wd4],
-                             x2d=x2d, gsave=gsave, p=p, drop=drop, seed=seed, sinks=_sinks(params),
-                             params=params if cfg.DIRECT_GRADS else None)
-        mod._last_dropout = dict(p=drop, seeds=[seed])
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        sv = ctx.saved
-        ctx.saved = None
-        p, st, ys, pools, wd = sv["p"], sv["st"], sv["y"], sv["pool"], sv["wd"]
-        blk = [p[3 * i: 3 * i + 3] for i in range(5)]
-        grads: List[Optional[torch.Tensor]] = [None] * len(p)
-        dy = _chk(dy, "grad_output")
-        # every gradient is written straight into its flat-gradient view when the parameter has one (sk[k]; None = returned to
-        # autograd): the 23 per-parameter copies of the former form were 0.11 ms of a 5.3 ms step (tools/step_timeline.py)
-        sk = sv["sinks"]
-        dx2d, grads[15:23] = gru_bidir_backward(dy, sv["x2d"], sv["gsave"], outs=sk[15:23])
-        y0, y1, y2, y3, y4 = ys
-        p1, p2, p3 = pools
-        # block 6 (cnn.6): conv(bn(leaky(y3)))
-        dy4 = lppool_leaky_backward(y4, dx2d.view(p3.shape), 1, 4, sv["drop"], sv["seed"])
-        grads[14] = conv3x3_wgrad(y3, dy4, prologue=2, scale=st[4].scale, shift=st[4].shift, out=sk[14])
-        du = conv3x3(dy4, wd[3], 128)
-        dy3, grads[12], grads[13] = bn_act_backward(y3, 1, st[4], blk[4][0], du, dg_out=sk[12], db_out=sk[13])
-        # block 5 (cnn.5): conv(bn(p2))
-        grads[11] = conv3x3_wgrad(p2, dy3, prologue=3, scale=st[3].scale, shift=st[3].shift, out=sk[11])
-        du = conv3x3(dy3, wd[2], 128)
-        dp2, grads[9], grads[10] = bn_act_backward(p2, 0, st[3], blk[3][0], du, dg_out=sk[9], db_out=sk[10])
-        dy2 = lppool_leaky_backward(y2, dp2, 2, 4)
-        # block 3 (cnn.3)
-        grads[8] = conv3x3_wgrad(y1, dy2, prologue=2, scale=st[2].scale, shift=st[2].shift, out=sk[8])
-        du = conv3x3(dy2, wd[1], 128)
-        dy1, grads[6], grads[7] = bn_act_backward(y1, 1, st[2], blk[2][0], du, dg_out=sk[6], db_out=sk[7])
-        # block 2 (cnn.2)
-        grads[5] = conv3x3_wgrad(p1, dy1, prologue=3, scale=st[1].scale, shift=st[1].shift, out=sk[5])
-        du = conv3x3(dy1, wd[0], p1.shape[3])
-        dp1, grads[3], grads[4] = bn_act_backward(p1, 0, st[1], blk[1][0], du, dg_out=sk[3], db_out=sk[4])
-        dy0 = lppool_leaky_backward(y0, dp1, 2, 4)
-        # block 0 (cnn.0): conv(bn_scalar(lm))
-        lm = sv["lm"]
-        grads[2] = conv3x3_c1_wgrad(lm, dy0, sv["cs"], sv["ct"], out=sk[2])
-        du0 = conv3x3_c1_dgrad(dy0, blk[0][2])                                     # (B,F,64) grad wrt bn output
-        B, Fr, NM = lm.shape
-        st0c = BNStat()
-        st0c.mean, st0c.invstd = st[0].mean.expand(NM).contiguous(), st[0].invstd.expand(NM).contiguous()
-        dgc, dbc = bn_param_grad(lm.view(B * Fr, NM), du0.view(B * Fr, NM), st0c)
-        grads[0], grads[1] = dgc.sum().view(1), dbc.sum().view(1)                   # 64 columns share one channel
-        for k in range(len(grads)):
-            if grads[k] is not None:
-                _deliver(grads, sk, k, grads[k])
-        _ready(sv["params"])
-        return (None, None, *grads)
+#: the five-block plan: the LPPool2d(4) window behind block i (dropout behind the last), or None -- the next block then reads
+#: the raw conv output.  A block behind a pool takes its BatchNorm statistics over its input as it is (pre_op 0) and folds the
+#: BatchNorm into its conv's operand load as prologue 3; a block behind a conv takes them over leaky(input) (pre_op 1) and folds
+#: LeakyReLU + BatchNorm as prologue 2.  Block 0 is the Cin = 1 conv behind the scalar BatchNorm2d(1).  Block i's parameters
+#: are p[3 * i: 3 * i + 3] = (bn.w, bn.b, conv.w); its channel count is its conv weight's.
+CDUR_POOLS = [(2, 4), None, (2, 4), None, (1, 4)]
+CRNN_POOLS = [w for w in CDUR_POOLS if w is not None]
 
 
 def check_cross_cdur_precision():
     """CrossCDur runs in fp32 only: the biased conv epilogues exist for the fp32 direct kernels alone."""
-    if cfg.CONV_MATH != "fp32" or act_bf16() or gemm_bf16():
-        raise RuntimeError(f"CrossCDur supports fp32 arithmetic only (CONV_MATH 'fp32', fp32 activations and GEMMs); got "
-                           f"CONV_MATH {cfg.CONV_MATH!r}, ACT_DTYPE {cfg.ACT_DTYPE!r}, GEMM_MATH {cfg.GEMM_MATH!r}")
+    _check_fp32_only("CrossCDur")
 
 
-def _clip_sums(dz):
-    """dt[b, c] = sum over (h, w) of a channels-last gradient dz (B,H,W,C): the gradient of a per-clip bias added to z."""
-    B, H, W, C = dz.shape
-    return rowgroup_colsum(dz.view(B * H * W, C), H * W)[0]
+def _cdur_conv(x, w, cout, prologue, scale, shift, t):
+    """The kernel that writes a block's output z = conv(bn(x)) [+ t[b, c]].  x (B,H,W): the Cin = 1 conv (w its weight, scale /
+    shift per column); else w is the forward pack.  Without t, conv3x3 dispatches on CONV_MATH as everywhere."""
+    if x.dim() == 3:
+        return conv3x3_c1(x, w, scale, shift) if t is None else conv3x3_c1_bias(x, w, scale, shift, t)
+    if t is None:
+        return conv3x3(x, w, cout, prologue=prologue, scale=scale, shift=shift)
+    return conv3x3_bias(x, w, cout, prologue, scale, shift, t)
+
+
+def _cdur_pool_backward(z, g, pool, drop_p, seed, want_dt):
+    """(dz, dt) of a block's raw output z from g, the gradient of its pooled output; dt = the per-clip sums of dz from the same
+    pass when wanted (the *_clip kernel), else None."""
+    if want_dt:
+        return lppool_leaky_backward_clip(z, g, *pool, drop_p, seed)
+    return lppool_leaky_backward(z, g, *pool, drop_p, seed), None
+
+
+def _cdur_bn_backward(z, st, gamma, g, dg_out, db_out, want_dt):
+    """(dz, dgamma, dbeta, dt) of a raw output z that feeds the next block's BatchNorm (st, gamma) through LeakyReLU; g is the
+    gradient of that BatchNorm's output, dt as in _cdur_pool_backward."""
+    if want_dt:
+        return bn_act_backward_clip(z, 1, st, gamma, g, dg_out=dg_out, db_out=db_out)
+    return (*bn_act_backward(z, 1, st, gamma, g, dg_out=dg_out, db_out=db_out), None)
+
+
+def _scalar_bn_backward(x2d, dz, w, st):
+    """(dgamma, dbeta), each (1,), of a BatchNorm2d(1) in front of a Cin = 1 conv: x2d (rows, W) its input, dz the gradient of
+    the conv's output."""
+    rows, W = x2d.shape
+    du0 = conv3x3_c1_dgrad(dz, w)                                              # (B,H,W) grad wrt the BatchNorm output
+    stc = BNStat()
+    stc.mean, stc.invstd = st.mean.expand(W).contiguous(), st.invstd.expand(W).contiguous()
+    dgc, dbc = bn_param_grad(x2d, du0.view(rows, W), stc)
+    return dgc.sum().view(1), dbc.sum().view(1)                                # W columns share one channel
+
+
+def _cdur_forward(ctx, waveform, mod, params, texts=None, r=None):
+    """CrnnFunction.forward (texts None) / CrossCDurFunction.forward (texts: t1..t5, r the frame head's text term).
+    Layer plan (channels-last): lm -> [bn0 scalar | conv 1->32] -> LP(2,4) -> [bn | conv 32->128] -> [leaky,bn | conv]
+    -> LP(2,4) -> [bn | conv] -> [leaky,bn | conv] -> LP(1,4)+dropout -> GRU [-> frame head]: CDUR_POOLS."""
+    wave = _chk(waveform, "waveform")
+    check_pass_size(wave.shape[0], wave.shape[1] // mod.hop_length + 1)
+    training = mod.training
+    p = [_chk(t.detach(), "parameter") for t in params]
+    rnn = p[15:23]
+    if texts is not None:
+        texts = [_chk(t.detach(), "text bias") for t in texts]
+        r = _chk(r.detach(), "fc_text")
+    bns = mod._bn_modules()
+    drop = mod.dropout_p if training else 0.0
+    seed = new_seed() if training and drop > 0 else 0
+    drops = [(0.0, 0)] * (len(CDUR_POOLS) - 1) + [(drop, seed)]   # (probability, seed) behind block i's pool: the last one only
+
+    lm = logmel(wave, mod.n_fft, mod.win_length, mod.hop_length, mod.window, mod.mel_fb)   # (B,F,64)
+    B, Fr, NM = lm.shape
+    if texts is not None:
+        for i, t in enumerate(texts + [r]):
+            C = 2 * rnn[1].shape[1] if i == 5 else p[3 * i + 2].shape[0]
+            if t.dim() != 2 or t.shape[0] != B or t.shape[1] != C:
+                raise RuntimeError(f"CrossCDur: text bias {i + 1} has shape {tuple(t.shape)}, expected ({B}, {C})")
+    x, after_pool = lm, True
+    st, xs, zs, wd = [], [], [], []
+    for i, pool in enumerate(CDUR_POOLS):
+        g, b, cw = p[3 * i: 3 * i + 3]
+        bn = bns[i]
+        s = bn_stats(x.view(-1, 1 if i == 0 else x.shape[3]), g, b, bn.running_mean, bn.running_var, training, bn.eps,
+                     bn.momentum, 0 if after_pool else 1)
+        t = texts[i] if texts is not None else None
+        if i == 0:                                                 # BatchNorm2d(1): one scalar affine, spread over the columns
+            cs, ct = s.scale.expand(NM).contiguous(), s.shift.expand(NM).contiguous()
+            z = _cdur_conv(lm, cw, cw.shape[0], 0, cs, ct, t)      # (B,F,64,32)
+        else:
+            wf, wdi = pack_conv_weight(cw, W=x.shape[2])
+            wd.append(wdi)
+            z = _cdur_conv(x, wf, cw.shape[0], 3 if after_pool else 2, s.scale, s.shift, t)
+        st.append(s)
+        xs.append(x)
+        zs.append(z)
+        after_pool = pool is not None
+        if after_pool:                                             # leaky + LPPool; the dropout behind the last one
+            x = bnact_pool(z, None, *pool, act=2, pool=1, drop_p=drops[i][0], seed=drops[i][1])
+        else:
+            x = z
+    Bx, Tp = x.shape[0], x.shape[1]                                # x: (B,T',1,128)
+    x2d = x.view(Bx * Tp, -1)
+    need_grad = any(ctx.needs_input_grad[2:])
+    y, gsave = gru_bidir_forward(x2d, rnn, Bx, Tp, need_grad)
+    if texts is not None:
+        y2d = y.reshape(Bx * Tp, -1)
+        prob, sig = frame_head_forward(y2d, r, p[23].reshape(-1), p[24], Tp)
+        y = prob.view(Bx, Tp)
+    if need_grad:
+        ctx.saved = dict(cs=cs, ct=ct, st=st, xs=xs, zs=zs, wd=wd, x2d=x2d, gsave=gsave, p=p, drops=drops,
+                         sinks=_sinks(params), params=params if cfg.DIRECT_GRADS else None, n_texts=0)
+        if texts is not None:
+            ctx.saved.update(y=y2d, sig=sig, r=r, Tp=Tp, n_texts=len(texts) + 1)
+    mod._last_dropout = dict(p=drop, seeds=[seed])
+    return y
+
+
+def _cdur_backward(ctx, dy):
+    """CrnnFunction.backward / CrossCDurFunction.backward -> (None, None, [dt1..dt5, dr,] *parameter gradients).  A frozen
+    parameter's gradient kernels are not launched (a conv weight: its weight-gradient conv; bn0: the Cin = 1 input gradient and
+    the column reduction); dt_i = per-clip sums of dz_i, emitted by the pass that writes dz_i (dispatch.*_backward_clip; 2 % of
+    the step faster than a rowgroup_colsum pass over each dz, docs/experiments_cross_cdur.md)."""
+    sv = ctx.saved
+    ctx.saved = None
+    p, st, xs, zs, wd, nt = sv["p"], sv["st"], sv["xs"], sv["zs"], sv["wd"], sv["n_texts"]
+    need = ctx.needs_input_grad
+    need_t, need_p = (need[2:2 + nt] if nt else (False,) * 5), need[2 + nt:]
+    grads: List[Optional[torch.Tensor]] = [None] * len(p)
+    dts: List[Optional[torch.Tensor]] = [None] * 5
+    # every gradient is written straight into its flat-gradient view when the parameter has one (sk[k]; None = returned to
+    # autograd): the 23 per-parameter copies of the former form were 0.11 ms of a 5.3 ms step (tools/step_timeline.py)
+    sk = sv["sinks"]
+    dy = _chk(dy, "grad_output")
+    dr = None
+    if nt:
+        y2d, Tp, wo = sv["y"], sv["Tp"], p[23]
+        dy, dwo, dbo, dr = frame_head_backward(y2d, sv["r"], wo.reshape(-1), sv["sig"], dy.reshape(-1), Tp)
+        grads[23], grads[24] = dwo.view_as(wo), dbo
+        dy = dy.view(y2d.shape[0] // Tp, Tp, -1)
+    dx2d, grads[15:23] = gru_bidir_backward(dy, sv["x2d"], sv["gsave"], outs=sk[15:23])
+    g = dx2d.view(zs[4].shape[0], -1, 1, zs[4].shape[3])          # gradient of the last pooled output (B,T',1,128)
+    du = None
+    for i in range(4, -1, -1):
+        k = 3 * i                                                  # parameters k, k + 1, k + 2: bn.w, bn.b, conv.w of block i
+        x, z, pool = xs[i], zs[i], CDUR_POOLS[i]
+        if pool is not None:
+            dz, dts[i] = _cdur_pool_backward(z, g, pool, *sv["drops"][i], need_t[i])
+        else:                                                      # g is already dz: the BatchNorm of block i + 1 gave it
+            dz = g
+        del g
+        if i == 0:
+            break
+        after_pool = CDUR_POOLS[i - 1] is not None
+        if need_p[k + 2]:                                          # a frozen conv weight: its weight-gradient conv is not launched
+            grads[k + 2] = conv3x3_wgrad(x, dz, prologue=3 if after_pool else 2, scale=st[i].scale, shift=st[i].shift,
+                                         out=sk[k + 2])
+        du = conv3x3(dz, wd[i - 1], x.shape[3])
+        del dz
+        if after_pool:
+            g, grads[k], grads[k + 1] = bn_act_backward(x, 0, st[i], p[k], du, dg_out=sk[k], db_out=sk[k + 1])
+        else:                                                      # x is z_{i-1}: bn_i's backward gives dz_{i-1} (and dt_{i-1})
+            g, grads[k], grads[k + 1], dts[i - 1] = _cdur_bn_backward(x, st[i], p[k], du, sk[k], sk[k + 1], need_t[i - 1])
+    del du
+    lm = xs[0]
+    if need_p[2]:
+        grads[2] = conv3x3_c1_wgrad(lm, dz, sv["cs"], sv["ct"], out=sk[2])
+    if need_p[0] or need_p[1]:
+        grads[0], grads[1] = _scalar_bn_backward(lm.view(-1, lm.shape[2]), dz, p[2], st[0])
+    for k in range(len(grads)):
+        if not need_p[k]:
+            grads[k] = None
+        elif grads[k] is not None:
+            _deliver(grads, sk, k, grads[k])
+    _ready(sv["params"])
+    if nt:
+        return (None, None, *dts, dr if need_t[5] else None, *grads)
+    return (None, None, *grads)
+
+
+class CrnnFunction(TagFunction):
+    """params order: 5 x (bn.w, bn.b, conv.w) for cnn.{0,2,3,5,6}, then gru (w_ih, w_hh, b_ih, b_hh) x (fwd, reverse).
+    The bodies are _cdur_forward / _cdur_backward without texts; conv3x3 dispatches on CONV_MATH (x3, bf16 GEMMs)."""
+
+    @staticmethod
+    def forward(ctx, waveform, mod, *params):
+        return _cdur_forward(ctx, waveform, mod, params)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _cdur_backward(ctx, dy)
 
 
 class CrossCDurFunction(TagFunction):
@@ -666,152 +738,22 @@ class CrossCDurFunction(TagFunction):
     params order: 5 x (bn.w, bn.b, conv.w) for block1..5, gru (w_ih, w_hh, b_ih, b_hh) x (fwd, reverse), fc_output.w,
     fc_output.b.  CrnnFunction's layer plan with z_i = conv_i(bn_i(.)) + t_i[b, c] written by the biased conv kernels
     (dispatch.conv3x3_c1_bias / conv3x3_bias) where CrnnFunction writes y_i: the forward has no extra pass over the activations.
-    The statistics of bn_{i+1} are taken over leaky(z_i), bias included.  Backward: dt_i = per-clip sums of dz_i, emitted by
-    the pass that writes dz_i (dispatch.*_backward_clip; 2 % of the step faster than a rowgroup_colsum pass over each dz,
-    docs/experiments_cross_cdur.md)."""
+    The statistics of bn_{i+1} are taken over leaky(z_i), bias included."""
 
     @staticmethod
     def forward(ctx, waveform, mod, t1, t2, t3, t4, t5, r, *params):
         check_cross_cdur_precision()
-        wave = _chk(waveform, "waveform")
-        check_pass_size(wave.shape[0], wave.shape[1] // mod.hop_length + 1)
-        training = mod.training
-        p = [_chk(t.detach(), "parameter") for t in params]
-        texts = [_chk(t.detach(), "text bias") for t in (t1, t2, t3, t4, t5)]
-        r_ = _chk(r.detach(), "fc_text")
-        blk = [p[3 * i: 3 * i + 3] for i in range(5)]
-        rnn = p[15:23]
-        wo, bo = p[23], p[24]
-        bns = mod._bn_modules()
-        drop = mod.dropout_p if training else 0.0
-        seed = new_seed() if training and drop > 0 else 0
-
-        lm = logmel(wave, mod.n_fft, mod.win_length, mod.hop_length, mod.window, mod.mel_fb)   # (B,F,64)
-        B, Fr, NM = lm.shape
-        for i, t in enumerate(texts + [r_]):
-            C = 2 * rnn[1].shape[1] if i == 5 else blk[i][2].shape[0]
-            if t.dim() != 2 or t.shape[0] != B or t.shape[1] != C:
-                raise RuntimeError(f"CrossCDur: text bias {i + 1} has shape {tuple(t.shape)}, expected ({B}, {C})")
-
-        def stats(x2d, i, pre_op):
-            return bn_stats(x2d, blk[i][0], blk[i][1], bns[i].running_mean, bns[i].running_var, training, bns[i].eps,
-                            bns[i].momentum, pre_op)
-
-        st = [None] * 5
-        st[0] = stats(lm.view(-1, 1), 0, 0)                       # BatchNorm2d(1): one scalar affine
-        cs, ct = st[0].scale.expand(NM).contiguous(), st[0].shift.expand(NM).contiguous()
-        z1 = conv3x3_c1_bias(lm, blk[0][2], cs, ct, texts[0])      # (B,F,64,32)
-        a1 = bnact_pool(z1, None, 2, 4, act=2, pool=1)            # leaky + LPPool -> (B,F/2,16,32)
-        st[1] = stats(a1.view(-1, a1.shape[3]), 1, 0)
-        wf1, wd1 = pack_conv_weight(blk[1][2], W=a1.shape[2])
-        z2 = conv3x3_bias(a1, wf1, 128, 3, st[1].scale, st[1].shift, texts[1])
-        st[2] = stats(z2.view(-1, 128), 2, 1)                     # over leaky(z2)
-        wf2, wd2 = pack_conv_weight(blk[2][2], W=z2.shape[2])
-        z3 = conv3x3_bias(z2, wf2, 128, 2, st[2].scale, st[2].shift, texts[2])
-        a3 = bnact_pool(z3, None, 2, 4, act=2, pool=1)            # (B,F/4,4,128)
-        st[3] = stats(a3.view(-1, 128), 3, 0)
-        wf3, wd3 = pack_conv_weight(blk[3][2], W=a3.shape[2])
-        z4 = conv3x3_bias(a3, wf3, 128, 3, st[3].scale, st[3].shift, texts[3])
-        st[4] = stats(z4.view(-1, 128), 4, 1)
-        wf4, wd4 = pack_conv_weight(blk[4][2], W=z4.shape[2])
-        z5 = conv3x3_bias(z4, wf4, 128, 2, st[4].scale, st[4].shift, texts[4])
-        a5 = bnact_pool(z5, None, 1, 4, act=2, pool=1, drop_p=drop, seed=seed)     # (B,T',1,128)
-        Bx, Tp = a5.shape[0], a5.shape[1]
-        x2d = a5.view(Bx * Tp, -1)
-        need_grad = any(ctx.needs_input_grad[2:])
-        y, gsave = gru_bidir_forward(x2d, rnn, Bx, Tp, need_grad)
-        y2d = y.reshape(Bx * Tp, -1)
-        prob, sig = frame_head_forward(y2d, r_, wo.reshape(-1), bo, Tp)
-        if need_grad:
-            ctx.saved = dict(lm=lm, cs=cs, ct=ct, st=st, z=[z1, z2, z3, z4, z5], pool=[a1, a3, a5], wd=[wd1, wd2, wd3, wd4],
-                             x2d=x2d, gsave=gsave, y=y2d, sig=sig, r=r_, p=p, drop=drop, seed=seed, sinks=_sinks(params),
-                             params=params if cfg.DIRECT_GRADS else None)
-        mod._last_dropout = dict(p=drop, seeds=[seed])
-        return prob.view(Bx, Tp)
+        return _cdur_forward(ctx, waveform, mod, params, (t1, t2, t3, t4, t5), r)
 
     @staticmethod
-    def backward(ctx, dprob):
-        sv = ctx.saved
-        ctx.saved = None
-        p, st, zs, pools, wd = sv["p"], sv["st"], sv["z"], sv["pool"], sv["wd"]
-        blk = [p[3 * i: 3 * i + 3] for i in range(5)]
-        need = ctx.needs_input_grad
-        need_t, need_p = need[2:8], need[8:]
-        grads: List[Optional[torch.Tensor]] = [None] * len(p)
-        dts: List[Optional[torch.Tensor]] = [None] * 5
-        sk = sv["sinks"]
-        dprob = _chk(dprob, "grad_output")
-        y2d = sv["y"]
-        Tp = pools[2].shape[1]
-        wo = p[23]
-        dyh, dwo, dbo, dr = frame_head_backward(y2d, sv["r"], wo.reshape(-1), sv["sig"], dprob.reshape(-1), Tp)
-        grads[23], grads[24] = dwo.view_as(wo), dbo
-        dx2d, grads[15:23] = gru_bidir_backward(dyh.view(y2d.shape[0] // Tp, Tp, -1), sv["x2d"], sv["gsave"], outs=sk[15:23])
-        z1, z2, z3, z4, z5 = zs
-        a1, a3, a5 = pools
+    def backward(ctx, dy):
+        return _cdur_backward(ctx, dy)
 
-        def wgrad(k, x, dz, prologue, s):
-            if need_p[k]:                                      # a frozen conv weight: its weight-gradient conv is not launched
-                grads[k] = conv3x3_wgrad(x, dz, prologue=prologue, scale=s.scale, shift=s.shift, out=sk[k])
 
-        def pool_bwd(i, z, dout, ph, pw, drop_p=0.0, seed=0):
-            """dz_i of a pooled block and, when t_i takes a gradient, dt_i from the same pass."""
-            if need_t[i]:
-                dz, dts[i] = lppool_leaky_backward_clip(z, dout, ph, pw, drop_p, seed)
-                return dz
-            return lppool_leaky_backward(z, dout, ph, pw, drop_p, seed)
-
-        def bn_bwd(i, k, z, s, du):
-            """dz_i of a block whose output feeds a BatchNorm directly (leaky in the next conv's prologue), and dt_i."""
-            if need_t[i]:
-                dz, grads[k], grads[k + 1], dts[i] = bn_act_backward_clip(z, 1, s, blk[i + 1][0], du, dg_out=sk[k], db_out=sk[k + 1])
-            else:
-                dz, grads[k], grads[k + 1] = bn_act_backward(z, 1, s, blk[i + 1][0], du, dg_out=sk[k], db_out=sk[k + 1])
-            return dz
-
-        # block5: conv(bn(leaky(z4))) + t5
-        dz5 = pool_bwd(4, z5, dx2d.view(a5.shape), 1, 4, sv["drop"], sv["seed"])
-        wgrad(14, z4, dz5, 2, st[4])
-        du = conv3x3(dz5, wd[3], 128)
-        del dz5
-        dz4 = bn_bwd(3, 12, z4, st[4], du)
-        # block4: conv(bn(a3)) + t4
-        wgrad(11, a3, dz4, 3, st[3])
-        du = conv3x3(dz4, wd[2], 128)
-        del dz4
-        da3, grads[9], grads[10] = bn_act_backward(a3, 0, st[3], blk[3][0], du, dg_out=sk[9], db_out=sk[10])
-        dz3 = pool_bwd(2, z3, da3, 2, 4)
-        del da3
-        # block3
-        wgrad(8, z2, dz3, 2, st[2])
-        du = conv3x3(dz3, wd[1], 128)
-        del dz3
-        dz2 = bn_bwd(1, 6, z2, st[2], du)
-        # block2
-        wgrad(5, a1, dz2, 3, st[1])
-        du = conv3x3(dz2, wd[0], a1.shape[3])
-        del dz2
-        da1, grads[3], grads[4] = bn_act_backward(a1, 0, st[1], blk[1][0], du, dg_out=sk[3], db_out=sk[4])
-        dz1 = pool_bwd(0, z1, da1, 2, 4)
-        del da1, du
-        # block1: conv(bn_scalar(lm)) + t1
-        lm = sv["lm"]
-        if need_p[2]:
-            grads[2] = conv3x3_c1_wgrad(lm, dz1, sv["cs"], sv["ct"], out=sk[2])
-        if need_p[0] or need_p[1]:
-            du0 = conv3x3_c1_dgrad(dz1, blk[0][2])                                 # (B,F,64) grad wrt bn output
-            B, Fr, NM = lm.shape
-            st0c = BNStat()
-            st0c.mean, st0c.invstd = st[0].mean.expand(NM).contiguous(), st[0].invstd.expand(NM).contiguous()
-            dgc, dbc = bn_param_grad(lm.view(B * Fr, NM), du0.view(B * Fr, NM), st0c)
-            grads[0], grads[1] = dgc.sum().view(1), dbc.sum().view(1)               # 64 columns share one channel
-        for k in range(len(grads)):
-            if not need_p[k]:
-                grads[k] = None
-            elif grads[k] is not None:
-                _deliver(grads, sk, k, grads[k])
-        _ready(sv["params"])
-        return (None, None, *dts, dr if need_t[5] else None, *grads)
+def _clip_sums(dz):
+    """dt[b, c] = sum over (h, w) of a channels-last gradient dz (B,H,W,C): the gradient of a per-clip bias added to z."""
+    B, H, W, C = dz.shape
+    return rowgroup_colsum(dz.view(B * H * W, C), H * W)[0]
 
 
 class CDurTextBlockFunction(TagFunction):
@@ -832,12 +774,12 @@ class CDurTextBlockFunction(TagFunction):
         st = bn_stats(x.view(-1, Cin), g, b, bn.running_mean, bn.running_var, bn.training, bn.eps, bn.momentum)
         if Cin == 1:
             cs, ct = st.scale.expand(W).contiguous(), st.shift.expand(W).contiguous()
-            z = conv3x3_c1_bias(x.view(B, H, W), cw, cs, ct, t_)
+            z = _cdur_conv(x.view(B, H, W), cw, Cout, 0, cs, ct, t_)
             wd = None
         else:
             cs = ct = None
             wf, wd = pack_conv_weight(cw, W=W)
-            z = conv3x3_bias(x, wf, Cout, 3, st.scale, st.shift, t_)
+            z = _cdur_conv(x, wf, Cout, 3, st.scale, st.shift, t_)
         ctx.saved = (x, z, st, cs, ct, wd, g, cw)
         return leaky_forward(z)
 
@@ -850,11 +792,8 @@ class CDurTextBlockFunction(TagFunction):
         dt = _clip_sums(dz)
         if Cin == 1:
             dcw = conv3x3_c1_wgrad(x.view(B, H, W), dz, cs, ct)
-            du0 = conv3x3_c1_dgrad(dz, cw)
-            stc = BNStat()
-            stc.mean, stc.invstd = st.mean.expand(W).contiguous(), st.invstd.expand(W).contiguous()
-            dgc, dbc = bn_param_grad(x.view(B * H, W), du0.view(B * H, W), stc)
-            return None, dt, None, dgc.sum().view(1), dbc.sum().view(1), dcw
+            dg, db = _scalar_bn_backward(x.view(B * H, W), dz, cw, st)
+            return None, dt, None, dg, db, dcw
         dcw = conv3x3_wgrad(x, dz, prologue=3, scale=st.scale, shift=st.shift)
         du = conv3x3(dz, wd, Cin)
         dx, dg, db = bn_act_backward(x, 0, st, g, du)

@@ -584,7 +584,9 @@ register_autograd("tag::masked_frame_bce", _mbce_backward, setup_context=_mbce_s
 # same forward / backward bodies, called with a plain context object): that engine keeps per-step state no functional
 # operator could return cheaply (GBs of raw conv outputs saved for backward, dropout seeds, the direct-gradient sinks of the
 # flat buffer, the weight-gradient side stream), so the saved state travels from the forward kernel to ``setup_context`` through
-# a one-slot hand-over and the module (eps / momentum / dropout probabilities / frozen flags) is named by a token.
+# a one-slot hand-over and the module (eps / momentum / dropout probabilities / frozen flags) is named by a token.  All four
+# encoder operators go through _enc_forward / _enc_setup / _enc_backward; the early-fusion ones (``tag::cross_cnn8rnn`` /
+# ``tag::cross_cdur``) pass their text terms ahead of the parameters and cut the gradient list apart again (_cross_backward).
 # EAGER-ONLY: the fake kernels serve shape inference (opcheck, meta tensors); a backward traced by torch.compile / AOTAutograd has
 # no saved state and raises a clear error (_enc_backward).  A second backward through one forward (retain_graph) raises its own.
 import weakref
@@ -609,10 +611,11 @@ class _EncCtx:
         self.augment = augment
 
 
-def _enc_forward(engine, waveform, params, module_token, need_grad, augment=None):
+def _enc_forward(engine, waveform, params, module_token, need_grad, augment=None, texts=()):
+    """``texts``: the differentiable per-clip text terms of an early-fusion node, passed ahead of its parameters."""
     mod = _ENC_MODULES[module_token]
-    ctx = _EncCtx((False, False) + tuple(bool(need_grad and p.requires_grad) for p in params), augment)
-    y = engine.forward(ctx, waveform, mod, *params)
+    ctx = _EncCtx((False, False) + tuple(bool(need_grad and t.requires_grad) for t in (*texts, *params)), augment)
+    y = engine.forward(ctx, waveform, mod, *texts, *params)
     _ENC_HANDOVER[0] = (engine, ctx) if need_grad else None
     return y
 
@@ -641,6 +644,13 @@ def _enc_backward(ctx, dy):
     ctx.enc_consumed = True
     grads = engine.backward(ectx, dy.contiguous())            # (None, None, *parameter gradients)
     return (None, list(grads[2:])) + (None,) * (ctx.n_args - 2)
+
+
+def _cross_backward(ctx, dy):
+    """_enc_backward of an early-fusion operator (waveform, texts, params, ...): the node's flat gradient list is cut into the
+    six text terms and the parameters."""
+    flat = _enc_backward(ctx, dy)[1]
+    return (None, flat[:6], flat[6:]) + (None,) * (ctx.n_args - 3)
 
 
 def _enc_fake_frames(mod, waveform):
@@ -698,14 +708,10 @@ def cross_cnn8rnn(waveform: Tensor, texts: List[Tensor], params: List[Tensor], m
     (B, T', 1) before the optional x4 upsampling.  texts = [conv_block1..4.fc_text(e), fc1_text(e), rnn_text(e)] (B, C);
     params in CrossCnn8_Rnn._flat_params() order.  BatchNorm running statistics: module state, as tag::cnn8rnn_encoder.
     specaug_stripes: as tag::cnn8rnn_encoder (no mixup: the reference's cannot run, see CrossCnn8_Rnn)."""
-    mod = _ENC_MODULES[module_token]
     augment = None
     if specaug_stripes is not None:
-        augment = (specaug_stripes, mod.spec_augmenter.time_dropper.stripes_num, None)
-    ctx = _EncCtx((False, False) + tuple(bool(need_grad and t.requires_grad) for t in list(texts) + list(params)), augment)
-    y = ops.CrossCnn8RnnFunction.forward(ctx, waveform, mod, *texts, *params)
-    _ENC_HANDOVER[0] = (ops.CrossCnn8RnnFunction, ctx) if need_grad else None
-    return y
+        augment = (specaug_stripes, _ENC_MODULES[module_token].spec_augmenter.time_dropper.stripes_num, None)
+    return _enc_forward(ops.CrossCnn8RnnFunction, waveform, params, module_token, need_grad, augment, texts)
 
 
 @cross_cnn8rnn.register_fake
@@ -714,18 +720,7 @@ def _(waveform, texts, params, module_token, need_grad, specaug_stripes=None):
     return waveform.new_empty(waveform.shape[0], _enc_fake_frames(mod, waveform), 1)
 
 
-def _cross_setup(ctx, inputs, output):
-    _enc_setup(ctx, inputs, output)
-    ctx.n_args = 6 if inputs[5] is not None else 5
-
-
-def _cross_backward(ctx, dy):
-    g = _enc_backward(ctx, dy)                # (None, [texts..., params...], None, ...)
-    flat = g[1]
-    return (None, flat[:6], flat[6:]) + (None,) * (ctx.n_args - 3)
-
-
-register_autograd("tag::cross_cnn8rnn", _cross_backward, setup_context=_cross_setup)
+register_autograd("tag::cross_cnn8rnn", _cross_backward, setup_context=_enc_setup)
 
 
 @custom_op("tag::cross_cdur", mutates_args=())
@@ -733,11 +728,7 @@ def cross_cdur(waveform: Tensor, texts: List[Tensor], params: List[Tensor], modu
     """CrossCDur.forward of models/audio_text_model.py:539-568 below its text encoder: waveform (B,S) -> frame_sim (B, T')
     before the optional x4 upsampling.  texts = [block1..5.fc_text(e), fc_text(e)] (B, C); params in
     CrossCDur._flat_params() order.  BatchNorm running statistics: module state, as tag::crnn_encoder."""
-    mod = _ENC_MODULES[module_token]
-    ctx = _EncCtx((False, False) + tuple(bool(need_grad and t.requires_grad) for t in list(texts) + list(params)))
-    y = ops.CrossCDurFunction.forward(ctx, waveform, mod, *texts, *params)
-    _ENC_HANDOVER[0] = (ops.CrossCDurFunction, ctx) if need_grad else None
-    return y
+    return _enc_forward(ops.CrossCDurFunction, waveform, params, module_token, need_grad, texts=texts)
 
 
 @cross_cdur.register_fake
@@ -746,13 +737,7 @@ def _(waveform, texts, params, module_token, need_grad):
     return waveform.new_empty(waveform.shape[0], (waveform.shape[1] // mod.hop_length + 1) // mod.interpolate_ratio)
 
 
-def _cdur_backward(ctx, dy):
-    g = _enc_backward(ctx, dy)                # (None, [texts..., params...], None, ...)
-    flat = g[1]
-    return (None, flat[:6], flat[6:], None, None)
-
-
-register_autograd("tag::cross_cdur", _cdur_backward, setup_context=_enc_setup)
+register_autograd("tag::cross_cdur", _cross_backward, setup_context=_enc_setup)
 
 
 def stage_to_device(t, device, dtype):
