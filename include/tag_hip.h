@@ -89,7 +89,12 @@ int tag_bn_stats(const float* x, long rows, int C, int pre_op, const float* gamm
                  float eps, float momentum, float* running_mean, float* running_var, float* mean,
                  float* invstd, float* scale, float* shift, void* ws, void* stream);
 /* the same outputs from the partial statistics a conv kernel wrote in its epilogue (P rows; layout: see
- * tag_conv3x3_forward) */
+ * tag_conv3x3_forward).  A row's pivot is any value near its pixels (the tile mean rounded to fp32 in conv.hip / conv_x3.hip,
+ * the first output of the row in conv_wino.hip and the Cin = 1 conv); the rows are merged in fp64 (Chan et al.) about the pivot of
+ * ROW 0, whatever its count, so row 0 must not be empty.  Every conv epilogue keeps that: its row 0 belongs to the first tile, strip or M group of clip 0, which starts at
+ * pixel (0, 0) of that clip and so holds at least one pixel (conv.hip, conv_x3.hip, conv_rows.hip: h0 = 0 < H; conv_wino.hip,
+ * conv_wino_fused.hip: tile 0, output (0, 0)).  Rows with count 0 occur only further down (tile halves past H, padding rows
+ * of a tile block); they are skipped and their contents are never read.  ws: tag_bn_stats_from_partials_ws_bytes(P, C) bytes. */
 size_t tag_bn_stats_from_partials_ws_bytes(int P, int C);
 int tag_bn_stats_from_partials(const float* partials, int P, int C, const float* gamma, const float* beta, float eps,
                                float momentum, float* running_mean, float* running_var, float* mean,
@@ -740,7 +745,8 @@ int tag_mean_w_backward_bf16(const float* dout, long rows, int W, int C, float d
  * bias between BatchNorm and ReLU, relu(bn(y) + bias[b, c]), and again at fc1 and after the GRU.  fp32, channels-last.
  * A reducing entry writes clip (B, 2, C) doubles, [b][sum a | sum b] of its two quantities over clip b, folded in a fixed order
  * from fp64 partial rows that never straddle two clips; the channel totals are folded from those (no atomics).
- * ws: tag_clip_reduce_ws_bytes(B, C) bytes.
+ * ws: tag_clip_reduce_ws_bytes(B, C) bytes.  The clips are the y dimension of the launch grid: every entry of this group but
+ * tag_rowgroup_bias_relu and tag_frame_head_forward refuses B > 65535 with TAG_EINVAL before it launches anything.
  *   tag_bias_bnrelu_forward       out = relu(y*scale + shift + bias[b]) over (B, HW, C)
  *   tag_bias_bnrelu_pool_forward  tag_bnact_pool_forward (act 1; pool 0 avg+max | 2 avg | 3 max) with the bias
  *   tag_bias_bnrelu_pool_backward its backward: clip = [sum dz | sum dz*xhat], dbeta / dgamma their totals, dy

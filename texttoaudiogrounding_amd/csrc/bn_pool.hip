@@ -6,7 +6,9 @@
 // All tensors channels-last (rows, C); every kernel is HBM-bound: one float4 per lane, channels
 // innermost so a wave reads 1 KiB contiguous.  Per-channel reductions accumulate in fp64 per
 // thread, are combined per block through LDS and written as per-block partials; a one-block
-// finalize kernel sums the partials in a fixed order (deterministic, no atomics).
+// finalize kernel sums the partials in a fixed order (deterministic, no atomics).  The statistics
+// are one-pass, var = E[v^2] - E[v]^2, from fp32 squares summed in fp64: the rounding of the squares
+// (6e-8 of E[v^2]) stays in the variance, which matters where |mean| >> sigma over few rows.
 #include "tag_common.h"
 
 // bf16 tensors: 8 channels per thread in the pool BACKWARD passes too (1) or only in the forward pass (0)
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(FOLD_T) void bn_stats_finalize_kernel(const double*
     if (part != 0 || c >= C) return;
     const double m = s1 / (double)rows;
     double var = s2 / (double)rows - m * m;
-    if (var < 0) var = 0;
+    if (var < 0 || rows == 1) var = 0;          // one row: fl(v^2) - v^2 is the square's rounding, the variance is zero
     const double is = 1.0 / sqrt(var + (double)eps);
     if (mean) mean[c] = (float)m;
     if (invstd) invstd[c] = (float)is;
@@ -1399,7 +1401,7 @@ static int clip_fold_and_total(const double* partials, int nblk, int B, int C, d
 // out = relu(y * scale[c] + shift[c] + bias[b, c]) over (B, HW, C)
 extern "C" int tag_bias_bnrelu_forward(const float* y, const float* scale, const float* shift, const float* bias, float* out,
                                        int B, long HW, int C, void* stream) {
-    TAG_CHECK_ARG(y && scale && shift && bias && out && B > 0 && HW > 0 && vec_ok(C));
+    TAG_CHECK_ARG(y && scale && shift && bias && out && B > 0 && B <= 65535 && HW > 0 && vec_ok(C));   // one clip per blockIdx.y
     const long n4 = HW * C / 4;
     hipLaunchKernelGGL(affine_kernel<true>, dim3(ew_blocks(n4 * B) / B + 1, B), dim3(256), 0, as_stream(stream), y, n4, C, scale,
                        shift, out, bias);
@@ -1412,7 +1414,7 @@ extern "C" int tag_bias_bnrelu_pool_forward(const float* y, const float* scale, 
                                             float* out, int B, int H, int W, int C, int ph, int pw, int pool, float drop_p,
                                             uint64_t seed, void* stream) {
     TAG_CHECK_ARG(y && scale && shift && bias && out && (pool == 0 || pool == 2 || pool == 3));
-    TAG_CHECK_ARG(H / ph > 0 && W / pw > 0 && vec_ok(C));
+    TAG_CHECK_ARG(H / ph > 0 && W / pw > 0 && vec_ok(C) && B > 0 && B <= 65535);   // the clip count its backward puts in gridDim.y
     TAG_CHECK_ARG((long)B * H * W < (1L << 31));
     bool launched = false;
     const int nb = apply_blocks((long)B * (H / ph) * (W / pw), C);
@@ -1437,7 +1439,7 @@ extern "C" int tag_bias_bnrelu_pool_backward(const float* y, const float* scale,
                                              void* stream) {
     TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && bias && dout && dy && dgamma && dbeta && clip && ws);
     TAG_CHECK_ARG(pool == 0 || pool == 2 || pool == 3);
-    TAG_CHECK_ARG(vec_ok(C) && H / ph > 0 && W / pw > 0);
+    TAG_CHECK_ARG(vec_ok(C) && H / ph > 0 && W / pw > 0 && B > 0 && B <= 65535);   // one clip per blockIdx.y
     TAG_CHECK_ARG((long)B * H * W < (1L << 31));
     const float wavg = pool == 3 ? 0.0f : 1.0f / (float)(ph * pw), wmax = pool == 2 ? 0.0f : 1.0f;
     double* partials = static_cast<double*>(ws);
@@ -1473,7 +1475,7 @@ extern "C" int tag_bias_bnrelu_backward(const float* y, const float* scale, cons
                                         float* dgamma, float* dbeta, double* clip, const double* prev, float* dt, int B,
                                         long HW, int C, int bn_train, void* ws, void* stream) {
     TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && bias && da && dy && dgamma && dbeta && clip && ws);
-    TAG_CHECK_ARG(vec_ok(C) && B > 0 && HW > 0 && (long)B * HW < (1L << 31));
+    TAG_CHECK_ARG(vec_ok(C) && B > 0 && B <= 65535 && HW > 0 && (long)B * HW < (1L << 31));   // one clip per blockIdx.y
     double* partials = static_cast<double*>(ws);
     hipStream_t st = as_stream(stream);
     const int nblk = clip_red_blocks(HW, C, B);
@@ -1492,7 +1494,7 @@ extern "C" int tag_bias_bnrelu_backward(const float* y, const float* scale, cons
 // per-group column sums of x (B*T, N): dgroup (B, N) = sum over the T rows of each group, dtotal (N) = their sum over groups
 extern "C" int tag_rowgroup_colsum(const float* x, int B, int T, int N, float* dgroup, float* dtotal, double* clip, void* ws,
                                    void* stream) {
-    TAG_CHECK_ARG(x && dgroup && dtotal && clip && ws && B > 0 && T > 0 && vec_ok(N));
+    TAG_CHECK_ARG(x && dgroup && dtotal && clip && ws && B > 0 && B <= 65535 && T > 0 && vec_ok(N));   // one group per blockIdx.y
     double* partials = static_cast<double*>(ws);
     hipStream_t st = as_stream(stream);
     const int nblk = clip_red_blocks(T, N, B);
@@ -1508,7 +1510,7 @@ extern "C" int tag_rowgroup_colsum(const float* x, int B, int T, int N, float* d
 extern "C" int tag_frame_head_backward(const float* y, const float* rb, const float* w, const float* sig, const float* dprob,
                                        float* dy, float* dw, float* dsum, float* drb, double* clip, int B, int T, int N,
                                        void* ws, void* stream) {
-    TAG_CHECK_ARG(y && rb && w && sig && dprob && dy && dw && dsum && drb && clip && ws && B > 0 && T > 0 && vec_ok(N));
+    TAG_CHECK_ARG(y && rb && w && sig && dprob && dy && dw && dsum && drb && clip && ws && B > 0 && B <= 65535 && T > 0 && vec_ok(N));
     double* partials = static_cast<double*>(ws);
     hipStream_t st = as_stream(stream);
     const int nblk = clip_red_blocks(T, N, B);
