@@ -174,7 +174,9 @@ __global__ __launch_bounds__(512) void wino_fused_kernel(const float* __restrict
     const int un = (tid & 127) >> 1, uslot = tid & 1;
     const unsigned uo0 = (unsigned)((((tid >> 7) * 64 + un) * 8 + ((uslot ^ ((un >> 3) & 1)) << 2)) * sizeof(float));   // + i * 4 planes
     const int uw0 = (tid >> 7) * FPL + un * 8 + (uslot << 2);                                                            // + i * 4 FPL
-    const unsigned ublk = (unsigned)nt * (unsigned)nch;                     // block index of chunk 0
+    // (explicitly wave-uniform: nt comes out of a division, and without this the prologue's chunk-1 U loads, whose scalar offset
+    // is (ublk + c1) * block bytes, were compiled into four readfirstlane / saveexec waterfall loops instead of four plain loads)
+    const unsigned ublk = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)nt * (unsigned)nch));   // block index of chunk 0
 
     // ---- MFMA role
     const int hh = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
@@ -356,6 +358,57 @@ __global__ __launch_bounds__(512) void wino_fused_kernel(const float* __restrict
 #if TAG_WF_ABL & 32
     if (acc[0][0] != 12345.678f) return;               // ablation: no epilogue at all (prologue + K loop only)
 #endif
+    // ---- role of the last phase, thread = (pixel, cout quad) of tiles slot and slot + 32.  EPI 1 works it out in front of the
+    // output transform, because it requests what that phase reads from global memory HERE: with one workgroup per CU nothing
+    // covers a latency outside the K loop, and the yref reads used to sit one per iteration behind the last loop's `continue`,
+    // eight dependent round trips per thread.  (The other forms: behind the park barrier, as before.  EPI 2 keeps its reads in the
+    // loop: batched, its launches measured level -- its iterations are ~300 instructions each; docs/experiments_wino_epilogue.md.)
+    const int cq = tid & 15, slot = tid >> 4;
+    const int co = n0 + 4 * cq;
+    int tb[2], ti[2], tj[2];
+    bool tok[2];
+    bool pok[8];                                       // EPI 1: iteration it = (pixel ae = it >> 1, tile u = it & 1) is inside the image
+    auto last_phase_role = [&]() {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const unsigned t = (unsigned)m0 + (unsigned)(slot + 32 * u);
+            tok[u] = t < (unsigned)T;
+            const unsigned t2 = tok[u] ? t : 0u;
+            const unsigned bi = t2 / (unsigned)tw;
+            tj[u] = (int)(t2 - bi * (unsigned)tw);
+            tb[u] = (int)(bi / (unsigned)th);
+            ti[u] = (int)(bi - (unsigned)tb[u] * (unsigned)th);
+        }
+        if (EPI == 1) {
+#pragma unroll
+            for (int it = 0; it < 8; ++it) {
+                const int u = it & 1;
+                pok[it] = tok[u] && 2 * ti[u] + (it >> 2) < H && 2 * tj[u] + ((it >> 1) & 1) < W;
+            }
+        }
+    };
+    if (EPI == 1) last_phase_role();
+    f32x4 bsc = {0, 0, 0, 0}, bsh = {0, 0, 0, 0}, bmu = {0, 0, 0, 0}, bis = {0, 0, 0, 0};
+    f32x4 yrv[EPI == 1 ? 8 : 1];
+    if (EPI == 1) {
+        // (the per-channel constants travel with the batch)
+        bsc = *reinterpret_cast<const f32x4*>(epi.scale + co); bsh = *reinterpret_cast<const f32x4*>(epi.shift + co);
+        bmu = *reinterpret_cast<const f32x4*>(epi.mean + co); bis = *reinterpret_cast<const f32x4*>(epi.invstd + co);
+        // EPI 1: all eight yref reads of the thread in ONE batch, requested before the park phase so that the single round trip runs
+        // under the output transform and the park writes (8 x 16 B = 32 registers beside the accumulators).
+        // A batched read must NEVER address memory outside yref: the reads go through a buffer descriptor over the tensor's exact
+        // byte size (B H W Cout floats, < 2^31 bytes: tag_conv3x3_wino_ok), and a (tile, pixel) outside the image -- tile beyond T,
+        // row >= H, column >= W -- gets an offset beyond the descriptor's range, as the K loop's padding rows do: the hardware
+        // touches no memory for it and returns zeros, which the loop below discards exactly where its `continue` always did.
+        const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(epi.yref), 0, (int)((size_t)B * H * W * Cout * 4), 0x00020000);
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int u = it & 1, a = it >> 2, e = (it >> 1) & 1;
+            const unsigned ob = pok[it] ? (((((unsigned)tb[u] * (unsigned)H + 2u * (unsigned)ti[u] + (unsigned)a) * (unsigned)W
+                                               + 2u * (unsigned)tj[u] + (unsigned)e) * (unsigned)Cout + (unsigned)co) << 2) : 0x80000000u;
+            yrv[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(yrs, ob, 0, 0));
+        }
+    }
     // ---- output transform: each wave parks its share of the 2 x 2 outputs  [half][pixel 2a+e][tile][cout]
     {
         float* park = smem + hh * (4 * 64 * FPARK_LD) + (wn * 32 + ml) * FPARK_LD + wm * 32 + 4 * kl;
@@ -373,22 +426,9 @@ __global__ __launch_bounds__(512) void wino_fused_kernel(const float* __restrict
     const unsigned long long pt4 = __builtin_readcyclecounter();
 #endif
     // ---- thread = (pixel, cout quad): add the halves, store, epilogue sums
-    const int cq = tid & 15, slot = tid >> 4;
+    if (EPI != 1) last_phase_role();
     const float* pk = smem + 4 * cq;
     constexpr int HALF = 4 * 64 * FPARK_LD;
-    int tb[2], ti[2], tj[2];
-    bool tok[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const unsigned t = (unsigned)m0 + (unsigned)(slot + 32 * u);
-        tok[u] = t < (unsigned)T;
-        const unsigned t2 = tok[u] ? t : 0u;
-        const unsigned bi = t2 / (unsigned)tw;
-        tj[u] = (int)(t2 - bi * (unsigned)tw);
-        tb[u] = (int)(bi / (unsigned)th);
-        ti[u] = (int)(bi - (unsigned)tb[u] * (unsigned)th);
-    }
-    const int co = n0 + 4 * cq;
 
     if (EPI == 3) {
         // inference: out (B, H/ph, W/2, C) = avg/max pool(relu(y * scale + shift)) of the tile's own 2 x 2 outputs (the expression and
@@ -439,8 +479,7 @@ __global__ __launch_bounds__(512) void wino_fused_kernel(const float* __restrict
 #else
     const bool want = (EPI == 0) ? (stats != nullptr) : true;
 #endif
-    f32x4 bsc = {0, 0, 0, 0}, bsh = {0, 0, 0, 0}, bmu = {0, 0, 0, 0}, bis = {0, 0, 0, 0};
-    if (EPI == 1 || EPI == 2) {
+    if (EPI == 2) {
         bsc = *reinterpret_cast<const f32x4*>(epi.scale + co); bsh = *reinterpret_cast<const f32x4*>(epi.shift + co);
         bmu = *reinterpret_cast<const f32x4*>(epi.mean + co); bis = *reinterpret_cast<const f32x4*>(epi.invstd + co);
     }
@@ -450,6 +489,14 @@ __global__ __launch_bounds__(512) void wino_fused_kernel(const float* __restrict
     size_t tbase[2];                                   // offset of the tile's first output pixel (the 64-bit products once per tile)
 #pragma unroll
     for (int u = 0; u < 2; ++u) tbase[u] = (((size_t)tb[u] * H + 2 * ti[u]) * W + 2 * tj[u]) * Cout + co;
+    if (EPI == 1) {
+        // the batch is consumed as a whole: ONE wait, in front of the first y store.  Left to itself the compiler waits per iteration
+        // with a count that assumes no store was issued on the way, and an iteration here is ~30 instructions: on the path where
+        // the stores were issued those counts wait for the STORES of the iterations before (nothing waits for them now, up to the end
+        // of the kernel: the fold barrier orders LDS only)
+#pragma unroll
+        for (int it = 0; it < 8; ++it) asm volatile("" : "+v"(yrv[it]));
+    }
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
         const int ae = it >> 1, u = it & 1, a = ae >> 1, e = ae & 1;
@@ -457,7 +504,7 @@ __global__ __launch_bounds__(512) void wino_fused_kernel(const float* __restrict
         const float* p = pk + (ae * 64 + tile) * FPARK_LD;
         const f32x4 o = *reinterpret_cast<const f32x4*>(p) + *reinterpret_cast<const f32x4*>(p + HALF);
         const int h = 2 * ti[u] + a, w = 2 * tj[u] + e;
-        if (!tok[u] || h >= H || w >= W) continue;
+        if (EPI == 1 ? !pok[it] : (!tok[u] || h >= H || w >= W)) continue;     // (EPI 1: what the batched read of this iteration returned is dropped here)
         const size_t off = tbase[u] + (size_t)((a * W + e) * Cout);
 #if TAG_WF_ABL & 128
         if (o[0] == 12345.678f)                        // ablation: no output stores
@@ -469,7 +516,7 @@ __global__ __launch_bounds__(512) void wino_fused_kernel(const float* __restrict
             cnt += 1.0f;
         }
         if (EPI == 1) {
-            const f32x4 yr = *reinterpret_cast<const f32x4*>(epi.yref + off);
+            const f32x4 yr = yrv[it];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float g = fmaf(yr[k], bsc[k], bsh[k]) > 0.0f ? o[k] : 0.0f;
