@@ -566,7 +566,9 @@ int tag_roberta_embed_ln(const long* ids /*(B,L)*/, const float* word, const flo
 int tag_add_layernorm(const float* x, const float* res, const float* gamma, const float* beta, float eps,
                       float* out, long rows, int D, void* stream);
 /* softmax(q k^T / sqrt(dh) + key mask) v per (sequence, head); qkv (B*L, 3*heads*dh) = [q|k|v]; L <= 64;
- * dh in {16,32,64}; mask (B,L) int64 (0 = padded key) */
+ * dh in {16,32,64}; mask (B,L) int64 (0 = padded key; a key is valid wherever the mask is non-zero, holes included).
+ * A sequence whose mask is all zero is a softmax over no key: every output of THAT sequence is NaN (0 * 1/0), the other
+ * sequences of the batch are untouched. */
 int tag_mha_small(const float* qkv, const long* mask, float* out /*(B*L, heads*dh)*/, int B, int L, int heads,
                   int dh, void* stream);
 
@@ -576,7 +578,9 @@ int tag_mha_small(const float* qkv, const long* mask, float* out /*(B*L, heads*d
  * (aq = query Wq^T (B,T,Da), ak = kv Wk^T + b (B,L,Da)); these entries do the rest.  L <= 32 tokens.
  * ------------------------------------------------------------------------------------------- */
 /* score = v . tanh(aq[b,q] + ak[b,k]); rows q >= qlen[b] and columns k >= klen[b] filled with -1e10; attn = softmax_k;
- * ctx = attn @ kv (B,T,Dk) */
+ * ctx = attn @ kv (B,T,Dk).  qlen[b] > T / klen[b] > L fill nothing.  A fully filled row (q >= qlen[b], or klen[b] = 0) is the
+ * uniform 1/L over ALL L tokens, padding included (the reference's masked_fill, not -inf), and passes no score gradient.
+ * Forward takes any Da, Dk > 0; backward holds a row in registers and refuses Da or Dk > 1024. */
 int tag_addattn_forward(const float* aq, const float* ak, const float* v, const float* kv /*(B,L,Dk)*/,
                         const long* qlen, const long* klen, float* attn /*(B,T,L)*/, float* ctx, int B, int T, int L,
                         int Da, int Dk, void* stream);
@@ -590,7 +594,8 @@ int tag_addattn_backward(const float* aq, const float* ak, const float* v, const
 int tag_mul(const float* a, const float* b, float* out, long n, void* stream);
 int tag_gate_backward(const float* dout, const float* x, const float* g, float* dx, int accumulate, float* dz, long n,
                       void* stream);
-/* DotProduct with text_level="token" after a cross-encoder: sim[r] = sigmoid(a[r].b[r] [/sqrt(D)]).clamp(1e-7, 1) */
+/* DotProduct with text_level="token" after a cross-encoder: sim[r] = sigmoid(a[r].b[r] [/sqrt(D)]).clamp(1e-7, 1).
+ * Same arithmetic in the same order as tag_rowpair_* with kind 0 and no l2norm: the two agree bit for bit. */
 int tag_rowdot_sigmoid_forward(const float* a, const float* b, float* sim, long rows, int D, int scale, void* stream);
 int tag_rowdot_sigmoid_backward(const float* a, const float* b, const float* dsim, float* da, float* db, long rows,
                                 int D, int scale, void* stream);
@@ -675,6 +680,10 @@ int tag_sim_pool_backward(const float* sim, const long* alen, const long* tlen, 
  *   attn (B,T,H,L) softmax weights BEFORE dropout (saved for backward); ctx (B,T,E).  head_dim = E/H in {16, 32} or a
  *   multiple of 64, E <= 1024.  drop_p / seed: dropout on the attention weights (train), counter-based like A2.
  * backward: dq (B,T,E), dk, dv (B,L,E) (sums over frames folded from per-tile partials in a fixed order).
+ *   klen[b] > L (up to INT_MAX) means L (nothing is masked), on the MFMA and on the VALU path alike.  klen[b] = 0 is a softmax over no token:
+ *   forward writes NaN to attn of THAT clip and to its ctx (as nn.MultiheadAttention does; loud, not a silent 0; with dropout, a
+ *   (frame, head) all of whose weights were dropped reads 0) and leaves the other clips untouched; backward reads no weight of
+ *   such a clip and returns exact zeros for its dq, dk and dv.
  * tag_resln_head_*: x = audio, r = out_proj(ctx); sim (rows) = sigmoid(LayerNorm(x + dropout(r)) . w + b); mu / rstd (rows)
  * saved.  backward: dx, dr (rows,E) and the per-row terms gw = d logit * n, gg = dn * xhat, gb = dn, ds = d logit, whose
  * column sums (tag_colsum) are the gradients of linear.weight, norm.weight, norm.bias and linear.bias.

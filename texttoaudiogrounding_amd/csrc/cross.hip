@@ -5,7 +5,7 @@
 // materialises the (B, T*L, 2D) concatenation; here W = [Wq | Wk] is applied as two GEMMs (tag_gemm: aq = query Wq^T,
 // ak = kv Wk^T + b) and these kernels do the rest per frame: broadcast-add + tanh + dot with v, the two -1e10 mask fills,
 // softmax over the tokens and attn @ kv -- one wave per (clip, frame), the D axis spread over the lanes.
-// Backward recomputes tanh; a wave owns a tile of 16 frames so that the token-side gradients (d ak, d kv, d v), which
+// Backward recomputes tanh; a wave owns a tile of 8 frames (QT) so that the token-side gradients (d ak, d kv, d v), which
 // are sums over frames, leave as per-tile partials that a second kernel folds in a fixed order (no atomics).
 #include "tag_common.h"
 

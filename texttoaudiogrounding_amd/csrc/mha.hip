@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) void mha_cross_fwd_mfma_kernel(const float* __
     const int f = tile * 32 + n;                                   // this lane's frame (result column)
     const bool fok = f < T;
     const long row = (long)b * T + (fok ? f : T - 1);
-    const int kl = (int)klen[b];
+    const int kl = (int)min(klen[b], (long)L);                     // klen > L masks nothing, as the VALU loop `t < L && t < kl`
     // S^T = K_h Q_h^T: A = K (row = token n), B = Q^T (column = frame n); k-slot `half` of step j = column half * HD + j
     float ka[HD], qb[HD];
     load_half_row<HD>(ka, k + ((long)b * L + (n < L ? n : 0)) * E + h * DH + half * HD, n < L);
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256) void mha_cross_bwd_mfma_kernel(const float* __
     const int f0 = tile * 32, f = f0 + n;
     const bool fok = f < T;
     const long row = (long)b * T + (fok ? f : T - 1);
-    const int kl = (int)klen[b];
+    const int kl = (int)min(klen[b], (long)L);
     const float keep_scale = drop_p > 0.0f ? 1.0f / (1.0f - drop_p) : 1.0f;
     float* X = xs[wv];
     // d(dropped weights)^T[token][frame] = V_h dctx_h^T: same operand shapes as the forward scores
@@ -452,7 +452,8 @@ __global__ __launch_bounds__(256) void mha_cross_bwd_mfma_kernel(const float* __
     for (int r = 0; r < 16; ++r) {
         const int t = d_row(r, half);
         const long ai = (row * H + h) * L + t;
-        const float a = (fok && t < L) ? attn[ai] : 0.0f;
+        // a masked token weighs 0; klen 0: the forward's NaN row is not read and the clip's gradients are 0, as in the VALU kernel
+        const float a = (fok && t < kl) ? attn[ai] : 0.0f;
         float g = s[r];
         ad[r] = a;
         if (drop_p > 0.0f) {
