@@ -10,6 +10,7 @@
 // are one-pass, var = E[v^2] - E[v]^2, from fp32 squares summed in fp64: the rounding of the squares
 // (6e-8 of E[v^2]) stays in the variance, which matters where |mean| >> sigma over few rows.
 #include "tag_common.h"
+#include <type_traits>
 
 // bf16 tensors: 8 channels per thread in the pool BACKWARD passes too (1) or only in the forward pass (0)
 #ifndef TAG_POOL_BWD_NC8
@@ -22,6 +23,41 @@ constexpr int RED_MAX_BLOCKS = 1024;
 
 __device__ __forceinline__ float leaky01(float v) { return v > 0.0f ? v : 0.1f * v; }
 
+// The block-level end of every per-channel reduction here: each thread parks its NQ x NC fp64 sums in LDS (sred: [256][NQ][NC]),
+// the rsub == 0 threads add the block's other rpi - 1 rows to their own in ascending q (a fixed order) and write ONE partial row
+// [2][C] (slot 1 = zeros where NQ == 1): row blockIdx.x, or with clip row blockIdx.x of clip blockIdx.y.  tpr = C / NC threads per
+// row, c = the thread's first channel.
+// The two reducers hand over a COPY of their sums.  An array whose address leaves the kernel body is split into registers only
+// after inlining, and the loop that accumulates into it is then scheduled differently: 3-9 more VGPRs and one wave per SIMD less in
+// reduce2_kernel<BnReluBwdFnT> and pool_bwd_reduce_kernel<2, 2, bf16, 4>.
+template <int NC, int NQ>
+__device__ __forceinline__ void block_fold(double* sred, double (&s)[NQ][NC], int tpr, int rpi, int rsub, int c, int C,
+                                           double* __restrict__ partials, bool clip) {
+    double* mine = sred + threadIdx.x * NQ * NC;
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) mine[k * NC + j] = s[k][j];
+    __syncthreads();
+    if (rsub == 0) {
+        for (int q = 1; q < rpi; ++q) {
+            const double* o = sred + (threadIdx.x + q * tpr) * NQ * NC;
+#pragma unroll
+            for (int j = 0; j < NC; ++j)
+#pragma unroll
+                for (int k = 0; k < NQ; ++k) s[k][j] += o[k * NC + j];
+        }
+        const size_t blk = clip ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
+        double* row = partials + blk * 2 * C;
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {
+            row[c + j] = s[0][j];
+            if constexpr (NQ == 2) row[C + c + j] = s[1][j];
+            else row[C + c + j] = 0.0;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // generic two-quantity per-channel reduction over (rows, C), C % 4 == 0, (C/4) | 256
 // Functor: void operator()(long row, int c, float4& a, float4& b)   (c multiple of 4)
@@ -31,7 +67,7 @@ __device__ __forceinline__ float leaky01(float v) { return v > 0.0f ? v : 0.1f *
 // ------------------------------------------------------------------------------------------
 template <class Fn, bool CLIP = false>
 __global__ __launch_bounds__(256) void reduce2_kernel(Fn fn, long rows, int C, double* __restrict__ partials) {
-    extern __shared__ double sred[];   // [256][8]
+    extern __shared__ double sred[];   // [256][2][4]
     const int tpr = C >> 2;                 // threads per row
     const int rpi = 256 / tpr;              // rows per iteration
     const int c = (threadIdx.x % tpr) << 2;
@@ -46,21 +82,10 @@ __global__ __launch_bounds__(256) void reduce2_kernel(Fn fn, long rows, int C, d
         s1[0] += a.x; s1[1] += a.y; s1[2] += a.z; s1[3] += a.w;
         s2[0] += b.x; s2[1] += b.y; s2[2] += b.z; s2[3] += b.w;
     }
-    double* mine = sred + threadIdx.x * 8;
+    double s[2][4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { mine[j] = s1[j]; mine[4 + j] = s2[j]; }
-    __syncthreads();
-    if (rsub == 0) {
-        for (int q = 1; q < rpi; ++q) {
-            const double* o = sred + (threadIdx.x + q * tpr) * 8;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { s1[j] += o[j]; s2[j] += o[4 + j]; }
-        }
-        const size_t blk = CLIP ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
-        double* p = partials + blk * 2 * C;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { p[c + j] = s1[j]; p[C + c + j] = s2[j]; }
-    }
+    for (int j = 0; j < 4; ++j) { s[0][j] = s1[j]; s[1][j] = s2[j]; }
+    block_fold(sred, s, tpr, rpi, rsub, c, C, partials, CLIP);
 }
 
 // scalar fallback for C % 4 != 0 or C < 4 (CrnnEncoder's 1-channel BatchNorm): thread t owns
@@ -621,21 +646,10 @@ __global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(PoolBwdCtx<PH, PW,
             for (; r < slots; r += stride) { load(ia, ra); finish(ia, ra); ia = ia.plus(dstep, Ho, Wo); }
         }
     }
-    double* mine = sred + threadIdx.x * 2 * NC;
+    double s[2][NC];
 #pragma unroll
-    for (int j = 0; j < NC; ++j) { mine[j] = s1[j]; mine[NC + j] = s2[j]; }
-    __syncthreads();
-    if (rsub == 0) {
-        for (int q = 1; q < rpi; ++q) {
-            const double* o = sred + (threadIdx.x + q * tpr) * 2 * NC;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) { s1[j] += o[j]; s2[j] += o[NC + j]; }
-        }
-        const size_t blk = BIAS ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
-        double* p = partials + blk * 2 * C;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) { p[c + j] = s1[j]; p[C + c + j] = s2[j]; }
-    }
+    for (int j = 0; j < NC; ++j) { s[0][j] = s1[j]; s[1][j] = s2[j]; }
+    block_fold(sred, s, tpr, rpi, rsub, c, C, partials, BIAS);
 }
 
 template <int PH, int PW, class TS = float, int NC = 4, bool BIAS = false>
@@ -808,13 +822,26 @@ struct BnActBwdFn {
     }
 };
 
+// ------------------------------------------------------------------------------------------
+// CLIP forms of the two kernels below, for the backward passes of CrossCDur that also emit the per-clip sums of what they write:
+// the text enters as a per-clip bias on the raw conv output z, so d bias[b, c] = sum over (h, w) of dz[b, h, w, c], and dz is the
+// output of lppool_leaky_bwd_kernel (blocks 1, 3, 5) or bn_act_bwd_apply_kernel (blocks 2, 4).  CLIP: one clip per blockIdx.y,
+// the same statements per element (ONE body: dz is bit-identical to the plain instance's), every thread adds what it stores to fp64
+// sums of its channel quad, folded through LDS (block_fold) into partial rows [clip][blk][2][C] (slot 1 unused, zero) that never
+// straddle two clips; clip_fold_kernel folds them in a fixed order (no atomics) -- the protocol of the per-clip bias passes.  They
+// replace a tag_rowgroup_colsum pass over dz.  partials: CLIP only.
+// ------------------------------------------------------------------------------------------
+// CLIP: rows = rows of ONE clip, the BatchNorm count is that of all clips
+template <bool CLIP = false>
 __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(BnActBwdFn fn, const float* __restrict__ gamma,
                                                                const float* __restrict__ dgamma,
                                                                const float* __restrict__ dbeta, int bn_train,
-                                                               long rows, float* __restrict__ dx) {
+                                                               long rows, float* __restrict__ dx,
+                                                               double* __restrict__ partials) {
     const int C = fn.C, tpr = C >> 2, rpi = 256 / tpr;
     const int c = (threadIdx.x % tpr) << 2, rsub = threadIdx.x / tpr;
-    const float invN = 1.0f / (float)rows;
+    const float invN = 1.0f / (float)(CLIP ? rows * gridDim.y : rows);
+    const long r0 = CLIP ? (long)blockIdx.y * rows : 0;
     fn.prep(c);
     float k0[4], k1[4], k2[4];
 #pragma unroll
@@ -824,9 +851,10 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(BnActBwdFn fn, co
         k2[j] = bn_train ? dgamma[c + j] * invN : 0.0f;
     }
     const float mv[4] = {fn.m.x, fn.m.y, fn.m.z, fn.m.w}, iv[4] = {fn.is.x, fn.is.y, fn.is.z, fn.is.w};
+    double acc[1][4] = {{0, 0, 0, 0}};
     for (long r = (long)blockIdx.x * rpi + rsub; r < rows; r += (long)gridDim.x * rpi) {
-        const float4 xv = *reinterpret_cast<const float4*>(fn.x + (size_t)r * C + c);
-        const float4 g = *reinterpret_cast<const float4*>(fn.du + (size_t)r * C + c);
+        const float4 xv = *reinterpret_cast<const float4*>(fn.x + (size_t)(r0 + r) * C + c);
+        const float4 g = *reinterpret_cast<const float4*>(fn.du + (size_t)(r0 + r) * C + c);
         const float xx[4] = {xv.x, xv.y, xv.z, xv.w}, gg[4] = {g.x, g.y, g.z, g.w};
         float o[4];
 #pragma unroll
@@ -834,24 +862,34 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(BnActBwdFn fn, co
             const float v = fn.pre == 1 ? leaky01(xx[j]) : xx[j];
             const float dv = k0[j] * (gg[j] - k1[j] - (v - mv[j]) * iv[j] * k2[j]);
             o[j] = (fn.pre == 1 && xx[j] <= 0.0f) ? 0.1f * dv : dv;
+            if constexpr (CLIP) acc[0][j] += o[j];
         }
-        *reinterpret_cast<float4*>(dx + (size_t)r * C + c) = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<float4*>(dx + (size_t)(r0 + r) * C + c) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+    if constexpr (CLIP) {
+        __shared__ double sred[256 * 4];
+        block_fold(sred, acc, tpr, rpi, rsub, c, C, partials, true);
     }
 }
 
 // backward of  out = dropout( LPPool4( leaky_relu(y, 0.1) ) ):  dy = dout * a^3 / out^3 * leaky'(y)
-template <int PH, int PW>
+// plain: a 1-D grid over the B * Hs * Ws slots; CLIP: the Hs * Ws slots of clip blockIdx.y (32-bit slot index, B unused)
+template <int PH, int PW, bool CLIP = false>
 __global__ __launch_bounds__(256) void lppool_leaky_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dout,
                                                                float* __restrict__ dy, int B, int H, int W, int C,
-                                                               float drop_p, uint64_t seed) {
+                                                               float drop_p, uint64_t seed, double* __restrict__ partials) {
     const int Ho = H / PH, Wo = W / PW, C4 = C >> 2, rpi = 256 / C4;
     const int c = (threadIdx.x % C4) << 2, rsub = threadIdx.x / C4;
     const int Hs = (H + PH - 1) / PH, Ws = (W + PW - 1) / PW;
-    const long slots = (long)B * Hs * Ws;
     const float keep_scale = drop_p > 0.0f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    for (long r = (long)blockIdx.x * rpi + rsub; r < slots; r += (long)gridDim.x * rpi) {
-        const int ws = (int)(r % Ws); long q = r / Ws;
-        const int hs = (int)(q % Hs); const int b = (int)(q / Hs);
+    // plain: the slots of all clips, 64-bit; CLIP: the slots of clip blockIdx.y, 32-bit
+    using slot_t = std::conditional_t<CLIP, int, long>;
+    const slot_t slots = CLIP ? (slot_t)(Hs * Ws) : (slot_t)B * Hs * Ws;
+    double acc[1][4] = {{0, 0, 0, 0}};
+    for (slot_t r = (slot_t)blockIdx.x * rpi + rsub; r < slots; r += (slot_t)gridDim.x * rpi) {
+        const int ws = (int)(r % Ws);
+        const slot_t q = r / Ws;
+        const int hs = CLIP ? (int)q : (int)(q % Hs), b = CLIP ? (int)blockIdx.y : (int)(q / Hs);
         const bool full = hs < Ho && ws < Wo;
         float a[PH][PW][4], yv[PH][PW][4], sum[4] = {0, 0, 0, 0};
         bool ex[PH][PW];
@@ -896,10 +934,15 @@ __global__ __launch_bounds__(256) void lppool_leaky_bwd_kernel(const float* __re
                     const float aa = a[dh][dw][j];
                     const float da = k[j] * aa * aa * aa;
                     o[j] = yv[dh][dw][j] > 0.0f ? da : 0.1f * da;
+                    if constexpr (CLIP) acc[0][j] += o[j];
                 }
                 const int h = hs * PH + dh, w = ws * PW + dw;
                 *reinterpret_cast<float4*>(dy + (((size_t)b * H + h) * W + w) * C + c) = make_float4(o[0], o[1], o[2], o[3]);
             }
+    }
+    if constexpr (CLIP) {
+        __shared__ double sred[256 * 4];
+        block_fold(sred, acc, C4, rpi, rsub, c, C, partials, true);
     }
 }
 
@@ -957,11 +1000,54 @@ int clip_red_blocks(long rows_per_clip, int C, int B) {
     const int nb = red_blocks(rows_per_clip, C), cap = B >= 2048 ? 1 : 2048 / B;
     return nb < cap ? nb : cap;
 }
+// workgroups per clip of the CLIP forms of lppool_leaky_bwd_kernel and bn_act_bwd_apply_kernel: ~4 iterations per thread, at most
+// 2048 partial rows over all clips (tag_clip_reduce_ws_bytes)
+int clip_apply_blocks(long rows_per_clip, int C, int B) {
+    const int rpi = 256 / (C >> 2);
+    long nb = (rows_per_clip + (long)rpi * 4 - 1) / ((long)rpi * 4);
+    const int cap = B >= 2048 ? 1 : (2048 / B < RED_MAX_BLOCKS ? 2048 / B : RED_MAX_BLOCKS);
+    if (nb > cap) nb = cap;
+    return (int)(nb < 1 ? 1 : nb);
+}
+// clip[b] = the fold of clip b's partial rows (and dt, see clip_fold_kernel), then dsum1 / dsum2 = the channel totals of slots 0 / 1
+int clip_fold_and_total(const double* partials, int nblk, int B, int C, double* clip, const double* prev, const float* wcol,
+                        float* dt, float* dsum1, float* dsum2, hipStream_t st) {
+    hipLaunchKernelGGL(clip_fold_kernel, dim3(cdiv(C, 16), B), dim3(FOLD_T), 0, st, partials, nblk, C, clip, prev, wcol, dt);
+    TAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, st, clip, B, C, dsum2, dsum1);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
 bool vec_ok(int C) { return C % 4 == 0 && C >= 4 && (C >> 2) <= 256 && 256 % (C >> 2) == 0; }
 // channels per thread of the pool passes: 8 for bf16 tensors when the channel count allows (16-byte accesses), else 4
 template <class TS>
 constexpr bool pool_nc8_type() { return Act<TS>::is_bf16; }
 bool pool_nc8_ok(int C) { return C % 8 == 0 && (C >> 3) <= 256 && 256 % (C >> 3) == 0; }
+// The pooling windows an entry serves, as types: dispatch_window calls f(integral_constant<int, PH>, integral_constant<int, PW>)
+// for the listed window that equals (ph, pw) and returns whether there was one (any other window is refused by the caller), so
+// every entry instantiates its kernels for its own windows only.  The constants convert to int in a constant expression.
+template <int PH, int PW> struct Window {};
+template <class... Ws> struct Windows {};
+using PoolFwdWindows = Windows<Window<2, 2>, Window<1, 2>, Window<2, 4>, Window<1, 4>, Window<1, 1>, Window<2, 1>>;
+using PoolBwdWindows = Windows<Window<2, 2>, Window<1, 2>, Window<1, 1>, Window<2, 1>>;   // and both bias pool entries
+using LpBwdWindows = Windows<Window<2, 4>, Window<1, 4>, Window<2, 2>>;
+template <int... PH, int... PW, class F>
+bool dispatch_window(Windows<Window<PH, PW>...>, int ph, int pw, F&& f) {
+    return ((ph == PH && pw == PW && (f(std::integral_constant<int, PH>{}, std::integral_constant<int, PW>{}), true)) || ...);
+}
+// f(integral_constant<int, NC>): NC = 8 only exists for the storage types that take it (pool_nc8_type), else 4
+template <class TS, class F>
+void dispatch_nc(bool nc8, F&& f) {
+    if constexpr (pool_nc8_type<TS>()) {
+        if (nc8) return f(std::integral_constant<int, 8>{});
+    }
+    f(std::integral_constant<int, 4>{});
+}
+// both: f(PH, PW, NC)
+template <class TS, class Ws, class F>
+bool dispatch_window_nc(Ws windows, int ph, int pw, bool nc8, F&& f) {
+    return dispatch_window(windows, ph, pw, [&](auto ph_, auto pw_) { dispatch_nc<TS>(nc8, [&](auto nc_) { f(ph_, pw_, nc_); }); });
+}
 int ew_blocks(long n) {
     long nb = (n + 255) / 256;
     if (nb > 4096) nb = 4096;
@@ -1063,40 +1149,23 @@ extern "C" int tag_bn_param_grad(const float* x, const float* dy, long rows, int
     return 0;
 }
 
-#define DISPATCH_POOL(PH_, PW_, ...)                       \
-    if (ph == PH_ && pw == PW_) { constexpr int PH = PH_, PW = PW_; __VA_ARGS__; launched = true; }
-
-template <class TS>
-static int bnact_pool_forward_impl(const TS* y, const float* scale, const float* shift, TS* out, int B, int H, int W, int C,
-                                   int ph, int pw, int act, int pool, float drop_p, uint64_t seed, void* stream) {
+// BIAS: relu(bn(y) + bias[b, c]) (act 1), fp32, the backward's windows
+template <class TS, bool BIAS = false>
+static int bnact_pool_forward_impl(const TS* y, const float* scale, const float* shift, const float* bias, TS* out, int B, int H,
+                                   int W, int C, int ph, int pw, int act, int pool, float drop_p, uint64_t seed, void* stream) {
     TAG_CHECK_ARG(y && out && C % 4 == 0 && (act == 1 || act == 2) && pool >= 0 && pool <= 3);
     TAG_CHECK_ARG((scale == nullptr) == (shift == nullptr));
     TAG_CHECK_ARG(H / ph > 0 && W / pw > 0);
     TAG_CHECK_ARG(vec_ok(C));
     TAG_CHECK_ARG((long)B * H * W < (1L << 31));          // 32-bit pixel indices in the kernel
-    bool launched = false;
     const bool nc8 = pool_nc8_type<TS>() && pool_nc8_ok(C);
     const int nb = apply_blocks((long)B * (H / ph) * (W / pw), C, nc8 ? 8 : 4);
-#define POOL_FWD_BODY                                                                                              \
-    if constexpr (pool_nc8_type<TS>()) {                                                                            \
-        if (nc8) {                                                                                                  \
-            hipLaunchKernelGGL((bnact_pool_fwd_kernel<PH, PW, TS, 8>), dim3(nb), dim3(256), 0, as_stream(stream), y, scale, \
-                               shift, out, B, H, W, C, act, pool, drop_p, seed, nullptr);                                    \
-        } else {                                                                                                    \
-            hipLaunchKernelGGL((bnact_pool_fwd_kernel<PH, PW, TS, 4>), dim3(nb), dim3(256), 0, as_stream(stream), y, scale, \
-                               shift, out, B, H, W, C, act, pool, drop_p, seed, nullptr);                                    \
-        }                                                                                                           \
-    } else {                                                                                                        \
-        hipLaunchKernelGGL((bnact_pool_fwd_kernel<PH, PW, TS, 4>), dim3(nb), dim3(256), 0, as_stream(stream), y, scale, shift, \
-                           out, B, H, W, C, act, pool, drop_p, seed, nullptr);                                               \
-    }
-    DISPATCH_POOL(2, 2, POOL_FWD_BODY)
-    DISPATCH_POOL(1, 2, POOL_FWD_BODY)
-    DISPATCH_POOL(2, 4, POOL_FWD_BODY)
-    DISPATCH_POOL(1, 4, POOL_FWD_BODY)
-    DISPATCH_POOL(1, 1, POOL_FWD_BODY)
-    DISPATCH_POOL(2, 1, POOL_FWD_BODY)
-#undef POOL_FWD_BODY
+    using Ws = std::conditional_t<BIAS, PoolBwdWindows, PoolFwdWindows>;
+    const bool launched = dispatch_window_nc<TS>(Ws{}, ph, pw, nc8, [&](auto ph_, auto pw_, auto nc_) {
+        constexpr int PH = ph_, PW = pw_, NC = nc_;
+        hipLaunchKernelGGL((bnact_pool_fwd_kernel<PH, PW, TS, NC, BIAS>), dim3(nb), dim3(256), 0, as_stream(stream), y, scale, shift,
+                           out, B, H, W, C, act, pool, drop_p, seed, bias);
+    });
     TAG_CHECK_ARG(launched);
     TAG_LAUNCH_CHECK();
     return 0;
@@ -1104,102 +1173,46 @@ static int bnact_pool_forward_impl(const TS* y, const float* scale, const float*
 extern "C" int tag_bnact_pool_forward(const float* y, const float* scale, const float* shift, float* out, int B,
                                       int H, int W, int C, int ph, int pw, int act, int pool, float drop_p,
                                       uint64_t seed, void* stream) {
-    return bnact_pool_forward_impl<float>(y, scale, shift, out, B, H, W, C, ph, pw, act, pool, drop_p, seed, stream);
+    return bnact_pool_forward_impl<float>(y, scale, shift, nullptr, out, B, H, W, C, ph, pw, act, pool, drop_p, seed, stream);
 }
 extern "C" int tag_bnact_pool_forward_bf16(const void* y, const float* scale, const float* shift, void* out, int B,
                                            int H, int W, int C, int ph, int pw, int act, int pool, float drop_p,
                                            uint64_t seed, void* stream) {
-    return bnact_pool_forward_impl<bf16_t>(static_cast<const bf16_t*>(y), scale, shift, static_cast<bf16_t*>(out), B, H, W, C,
-                                           ph, pw, act, pool, drop_p, seed, stream);
+    return bnact_pool_forward_impl<bf16_t>(static_cast<const bf16_t*>(y), scale, shift, nullptr, static_cast<bf16_t*>(out), B, H,
+                                           W, C, ph, pw, act, pool, drop_p, seed, stream);
 }
 
-template <class TS>
-static int bnrelu_pool_backward_impl(const TS* y, const float* scale, const float* shift, const float* mean,
-                                     const float* invstd, const float* gamma, const TS* dout, TS* dy, float* dgamma,
-                                     float* dbeta, int B, int H, int W, int C, int ph, int pw, int pool, float drop_p,
-                                     uint64_t seed, int bn_train, void* ws, void* stream) {
-    TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && dout && dy && dgamma && dbeta && ws);
-    TAG_CHECK_ARG(pool == 0 || pool == 2 || pool == 3);
-    const float wavg = pool == 3 ? 0.0f : 1.0f / (float)(ph * pw), wmax = pool == 2 ? 0.0f : 1.0f;
-    TAG_CHECK_ARG(vec_ok(C) && H / ph > 0 && W / pw > 0);
-    TAG_CHECK_ARG((long)B * H * W < (1L << 31));          // 32-bit pixel indices in the kernels
-    double* partials = static_cast<double*>(ws);
-    const long slots = (long)B * (H / ph) * (W / pw);
-    const bool nc8 = pool_nc8_type<TS>() && pool_nc8_ok(C) && TAG_POOL_BWD_NC8;
-    const int nblk = red_blocks(slots, C, nc8 ? 8 : 4);
-    const int nb = apply_blocks((long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw), C, nc8 ? 8 : 4);
-    bool launched = false;
-#define POOL_BWD_NC(NC_)                                                                                           \
-    {                                                                                                              \
-        PoolBwdCtx<PH, PW, TS, NC_> ctx{y, scale, shift, mean, invstd, dout, B, H, W, C, drop_p, seed, wavg, wmax}; \
-        hipLaunchKernelGGL((pool_bwd_reduce_kernel<PH, PW, TS, NC_>), dim3(nblk), dim3(256), 256 * 2 * NC_ * sizeof(double), \
-                           as_stream(stream), ctx, partials);                                                      \
-        hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, as_stream(stream), partials, nblk, \
-                           C, dgamma, dbeta);                                                                      \
-        hipLaunchKernelGGL((pool_bwd_apply_kernel<PH, PW, TS, NC_>), dim3(nb), dim3(256), 0, as_stream(stream), ctx, gamma, \
-                           dgamma, dbeta, bn_train, dy);                                                           \
-    }
-#define POOL_BWD_BODY                                                                                              \
-    if constexpr (pool_nc8_type<TS>()) {                                                                           \
-        if (nc8) POOL_BWD_NC(8) else POOL_BWD_NC(4)                                                                \
-    } else POOL_BWD_NC(4)
-    DISPATCH_POOL(2, 2, POOL_BWD_BODY)
-    DISPATCH_POOL(1, 2, POOL_BWD_BODY)
-    DISPATCH_POOL(1, 1, POOL_BWD_BODY)
-    DISPATCH_POOL(2, 1, POOL_BWD_BODY)
-#undef POOL_BWD_BODY
-#undef POOL_BWD_NC
-    TAG_CHECK_ARG(launched);
-    TAG_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int tag_bnrelu_pool_backward(const float* y, const float* scale, const float* shift, const float* mean,
-                                        const float* invstd, const float* gamma, const float* dout, float* dy,
-                                        float* dgamma, float* dbeta, int B, int H, int W, int C, int ph, int pw,
-                                        int pool, float drop_p, uint64_t seed, int bn_train, void* ws, void* stream) {
-    return bnrelu_pool_backward_impl<float>(y, scale, shift, mean, invstd, gamma, dout, dy, dgamma, dbeta, B, H, W, C, ph, pw,
-                                            pool, drop_p, seed, bn_train, ws, stream);
-}
-extern "C" int tag_bnrelu_pool_backward_bf16(const void* y, const float* scale, const float* shift, const float* mean,
-                                             const float* invstd, const float* gamma, const void* dout, void* dy,
-                                             float* dgamma, float* dbeta, int B, int H, int W, int C, int ph, int pw,
-                                             int pool, float drop_p, uint64_t seed, int bn_train, void* ws, void* stream) {
-    return bnrelu_pool_backward_impl<bf16_t>(static_cast<const bf16_t*>(y), scale, shift, mean, invstd, gamma,
-                                             static_cast<const bf16_t*>(dout), static_cast<bf16_t*>(dy), dgamma, dbeta, B, H, W,
-                                             C, ph, pw, pool, drop_p, seed, bn_train, ws, stream);
+template <int PH, int PW, class TS, int NC, bool BIAS>
+static PoolBwdCtx<PH, PW, TS, NC, BIAS> pool_bwd_ctx(const TS* y, const float* scale, const float* shift, const float* mean,
+                                                     const float* invstd, const float* bias, const TS* dout, int B, int H, int W,
+                                                     int C, int pool, float drop_p, uint64_t seed) {
+    const float wavg = pool == 3 ? 0.0f : 1.0f / (float)(PH * PW), wmax = pool == 2 ? 0.0f : 1.0f;
+    PoolBwdCtx<PH, PW, TS, NC, BIAS> ctx{y, scale, shift, mean, invstd, dout, B, H, W, C, drop_p, seed, wavg, wmax};
+    ctx.bias = bias;
+    return ctx;
 }
 
 // the APPLY half of tag_bnrelu_pool_backward alone: dgamma / dbeta already hold sum(dz * xhat) / sum(dz) (folded from the partial
 // rows the dgrad conv that PRODUCED dout wrote in its epilogue: tag_conv3x3_dgrad_poolsums + tag_bn_grad_from_partials)
-template <class TS>
+// BIAS: the pool input is relu(bn(y) + bias[b, c]), fp32
+template <class TS, bool BIAS = false>
 static int bnrelu_pool_backward_apply_impl(const TS* y, const float* scale, const float* shift, const float* mean,
-                                           const float* invstd, const float* gamma, const TS* dout, TS* dy,
+                                           const float* invstd, const float* gamma, const float* bias, const TS* dout, TS* dy,
                                            const float* dgamma, const float* dbeta, int B, int H, int W, int C, int ph, int pw,
                                            int pool, float drop_p, uint64_t seed, int bn_train, void* stream) {
     TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && dout && dy && dgamma && dbeta);
     TAG_CHECK_ARG(pool == 0 || pool == 2 || pool == 3);
-    const float wavg = pool == 3 ? 0.0f : 1.0f / (float)(ph * pw), wmax = pool == 2 ? 0.0f : 1.0f;
     TAG_CHECK_ARG(vec_ok(C) && H / ph > 0 && W / pw > 0);
-    TAG_CHECK_ARG((long)B * H * W < (1L << 31));
+    TAG_CHECK_ARG((long)B * H * W < (1L << 31));          // 32-bit pixel indices in the kernels
     const bool nc8 = pool_nc8_type<TS>() && pool_nc8_ok(C) && TAG_POOL_BWD_NC8;
     const int nb = apply_blocks((long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw), C, nc8 ? 8 : 4);
-    bool launched = false;
-#define POOL_APPLY_NC(NC_)                                                                                         \
-    {                                                                                                              \
-        PoolBwdCtx<PH, PW, TS, NC_> ctx{y, scale, shift, mean, invstd, dout, B, H, W, C, drop_p, seed, wavg, wmax}; \
-        hipLaunchKernelGGL((pool_bwd_apply_kernel<PH, PW, TS, NC_>), dim3(nb), dim3(256), 0, as_stream(stream), ctx, gamma, \
-                           dgamma, dbeta, bn_train, dy);                                                           \
-    }
-#define POOL_APPLY_BODY                                                                                            \
-    if constexpr (pool_nc8_type<TS>()) {                                                                           \
-        if (nc8) POOL_APPLY_NC(8) else POOL_APPLY_NC(4)                                                            \
-    } else POOL_APPLY_NC(4)
-    DISPATCH_POOL(2, 2, POOL_APPLY_BODY)
-    DISPATCH_POOL(1, 2, POOL_APPLY_BODY)
-    DISPATCH_POOL(1, 1, POOL_APPLY_BODY)
-    DISPATCH_POOL(2, 1, POOL_APPLY_BODY)
-#undef POOL_APPLY_BODY
-#undef POOL_APPLY_NC
+    const bool launched = dispatch_window_nc<TS>(PoolBwdWindows{}, ph, pw, nc8, [&](auto ph_, auto pw_, auto nc_) {
+        constexpr int PH = ph_, PW = pw_, NC = nc_;
+        hipLaunchKernelGGL((pool_bwd_apply_kernel<PH, PW, TS, NC, BIAS>), dim3(nb), dim3(256), 0, as_stream(stream),
+                           pool_bwd_ctx<PH, PW, TS, NC, BIAS>(y, scale, shift, mean, invstd, bias, dout, B, H, W, C, pool, drop_p,
+                                                              seed),
+                           gamma, dgamma, dbeta, bn_train, dy);
+    });
     TAG_CHECK_ARG(launched);
     TAG_LAUNCH_CHECK();
     return 0;
@@ -1208,18 +1221,81 @@ extern "C" int tag_bnrelu_pool_backward_apply(const float* y, const float* scale
                                               const float* invstd, const float* gamma, const float* dout, float* dy,
                                               const float* dgamma, const float* dbeta, int B, int H, int W, int C, int ph,
                                               int pw, int pool, float drop_p, uint64_t seed, int bn_train, void* stream) {
-    return bnrelu_pool_backward_apply_impl<float>(y, scale, shift, mean, invstd, gamma, dout, dy, dgamma, dbeta, B, H, W, C, ph,
-                                                  pw, pool, drop_p, seed, bn_train, stream);
+    return bnrelu_pool_backward_apply_impl<float>(y, scale, shift, mean, invstd, gamma, nullptr, dout, dy, dgamma, dbeta, B, H, W,
+                                                  C, ph, pw, pool, drop_p, seed, bn_train, stream);
 }
 extern "C" int tag_bnrelu_pool_backward_apply_bf16(const void* y, const float* scale, const float* shift, const float* mean,
                                                    const float* invstd, const float* gamma, const void* dout, void* dy,
                                                    const float* dgamma, const float* dbeta, int B, int H, int W, int C, int ph,
                                                    int pw, int pool, float drop_p, uint64_t seed, int bn_train, void* stream) {
-    return bnrelu_pool_backward_apply_impl<bf16_t>(static_cast<const bf16_t*>(y), scale, shift, mean, invstd, gamma,
+    return bnrelu_pool_backward_apply_impl<bf16_t>(static_cast<const bf16_t*>(y), scale, shift, mean, invstd, gamma, nullptr,
                                                    static_cast<const bf16_t*>(dout), static_cast<bf16_t*>(dy), dgamma, dbeta, B, H,
                                                    W, C, ph, pw, pool, drop_p, seed, bn_train, stream);
 }
 
+// reduce (sum dz, sum dz*xhat), fold into dbeta / dgamma, apply.  BIAS (fp32): the reduction runs clip by clip (one clip per
+// blockIdx.y) and clip[b] keeps clip b's sums, the channel totals come from the same fold (clip_fold_and_total)
+template <class TS, bool BIAS = false>
+static int bnrelu_pool_backward_impl(const TS* y, const float* scale, const float* shift, const float* mean,
+                                     const float* invstd, const float* gamma, const float* bias, const TS* dout, TS* dy,
+                                     float* dgamma, float* dbeta, double* clip, int B, int H, int W, int C, int ph, int pw,
+                                     int pool, float drop_p, uint64_t seed, int bn_train, void* ws, void* stream) {
+    TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && dout && dy && dgamma && dbeta && ws);
+    TAG_CHECK_ARG(pool == 0 || pool == 2 || pool == 3);
+    TAG_CHECK_ARG(vec_ok(C) && H / ph > 0 && W / pw > 0);
+    TAG_CHECK_ARG((long)B * H * W < (1L << 31));          // 32-bit pixel indices in the kernels
+    double* partials = static_cast<double*>(ws);
+    const bool nc8 = pool_nc8_type<TS>() && pool_nc8_ok(C) && TAG_POOL_BWD_NC8;
+    const int nblk = BIAS ? clip_red_blocks((long)(H / ph) * (W / pw), C, B)
+                          : red_blocks((long)B * (H / ph) * (W / pw), C, nc8 ? 8 : 4);
+    const bool launched = dispatch_window_nc<TS>(PoolBwdWindows{}, ph, pw, nc8, [&](auto ph_, auto pw_, auto nc_) {
+        constexpr int PH = ph_, PW = pw_, NC = nc_;
+        hipLaunchKernelGGL((pool_bwd_reduce_kernel<PH, PW, TS, NC, BIAS>), BIAS ? dim3(nblk, B) : dim3(nblk), dim3(256),
+                           256 * 2 * NC * sizeof(double), as_stream(stream),
+                           pool_bwd_ctx<PH, PW, TS, NC, BIAS>(y, scale, shift, mean, invstd, bias, dout, B, H, W, C, pool, drop_p,
+                                                              seed),
+                           partials);
+    });
+    TAG_CHECK_ARG(launched);
+    TAG_LAUNCH_CHECK();
+    if constexpr (BIAS) {
+        if (int e = clip_fold_and_total(partials, nblk, B, C, clip, nullptr, nullptr, nullptr, dbeta, dgamma, as_stream(stream)))
+            return e;
+    } else {
+        hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, as_stream(stream), partials, nblk, C,
+                           dgamma, dbeta);
+    }
+    return bnrelu_pool_backward_apply_impl<TS, BIAS>(y, scale, shift, mean, invstd, gamma, bias, dout, dy, dgamma, dbeta, B, H, W, C,
+                                                     ph, pw, pool, drop_p, seed, bn_train, stream);
+}
+extern "C" int tag_bnrelu_pool_backward(const float* y, const float* scale, const float* shift, const float* mean,
+                                        const float* invstd, const float* gamma, const float* dout, float* dy,
+                                        float* dgamma, float* dbeta, int B, int H, int W, int C, int ph, int pw,
+                                        int pool, float drop_p, uint64_t seed, int bn_train, void* ws, void* stream) {
+    return bnrelu_pool_backward_impl<float>(y, scale, shift, mean, invstd, gamma, nullptr, dout, dy, dgamma, dbeta, nullptr, B, H,
+                                            W, C, ph, pw, pool, drop_p, seed, bn_train, ws, stream);
+}
+extern "C" int tag_bnrelu_pool_backward_bf16(const void* y, const float* scale, const float* shift, const float* mean,
+                                             const float* invstd, const float* gamma, const void* dout, void* dy,
+                                             float* dgamma, float* dbeta, int B, int H, int W, int C, int ph, int pw,
+                                             int pool, float drop_p, uint64_t seed, int bn_train, void* ws, void* stream) {
+    return bnrelu_pool_backward_impl<bf16_t>(static_cast<const bf16_t*>(y), scale, shift, mean, invstd, gamma, nullptr,
+                                             static_cast<const bf16_t*>(dout), static_cast<bf16_t*>(dy), dgamma, dbeta, nullptr, B,
+                                             H, W, C, ph, pw, pool, drop_p, seed, bn_train, ws, stream);
+}
+
+// the APPLY half of tag_bnrelu_backward alone: dgamma / dbeta already hold sum(g*xhat) / sum(g)
+template <class TS>
+static int bnrelu_backward_apply_impl(const TS* y, const float* scale, const float* shift, const float* mean,
+                                      const float* invstd, const float* gamma, const TS* da, TS* dy, const float* dgamma,
+                                      const float* dbeta, long rows, int C, int bn_train, void* stream) {
+    TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && da && dy && dgamma && dbeta && vec_ok(C));
+    BnReluBwdFnT<TS> fn{y, scale, shift, mean, invstd, da, C};
+    hipLaunchKernelGGL(bnrelu_bwd_apply_kernel<TS>, dim3(apply_blocks(rows, C)), dim3(256), 0, as_stream(stream), fn, gamma,
+                       dgamma, dbeta, bn_train, rows, dy);
+    TAG_LAUNCH_CHECK();
+    return 0;
+}
 template <class TS>
 static int bnrelu_backward_impl(const TS* y, const float* scale, const float* shift, const float* mean,
                                 const float* invstd, const float* gamma, const TS* da, TS* dy, float* dgamma,
@@ -1227,16 +1303,12 @@ static int bnrelu_backward_impl(const TS* y, const float* scale, const float* sh
     TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && da && dy && dgamma && dbeta && ws && vec_ok(C));
     double* partials = static_cast<double*>(ws);
     const int nblk = red_blocks(rows, C);
-    BnReluBwdFnT<TS> fn{y, scale, shift, mean, invstd, da, C};
     hipLaunchKernelGGL(reduce2_kernel<BnReluBwdFnT<TS>>, dim3(nblk), dim3(256), 256 * 8 * sizeof(double),
-                       as_stream(stream), fn, rows, C, partials);
+                       as_stream(stream), BnReluBwdFnT<TS>{y, scale, shift, mean, invstd, da, C}, rows, C, partials);
     TAG_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, as_stream(stream), partials, nblk, C,
                        dgamma, dbeta);
-    hipLaunchKernelGGL(bnrelu_bwd_apply_kernel<TS>, dim3(apply_blocks(rows, C)), dim3(256), 0, as_stream(stream), fn,
-                       gamma, dgamma, dbeta, bn_train, rows, dy);
-    TAG_LAUNCH_CHECK();
-    return 0;
+    return bnrelu_backward_apply_impl<TS>(y, scale, shift, mean, invstd, gamma, da, dy, dgamma, dbeta, rows, C, bn_train, stream);
 }
 extern "C" int tag_bnrelu_backward(const float* y, const float* scale, const float* shift, const float* mean,
                                    const float* invstd, const float* gamma, const float* da, float* dy,
@@ -1272,29 +1344,20 @@ extern "C" int tag_bn_grad_from_partials(const float* bnpart, int P, int C, floa
     TAG_LAUNCH_CHECK();
     return 0;
 }
-// the APPLY half of tag_bnrelu_backward alone: dgamma / dbeta already hold sum(g*xhat) / sum(g)
 extern "C" int tag_bnrelu_backward_apply(const float* y, const float* scale, const float* shift, const float* mean,
                                          const float* invstd, const float* gamma, const float* da, float* dy,
                                          const float* dgamma, const float* dbeta, long rows, int C, int bn_train,
                                          void* stream) {
-    TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && da && dy && dgamma && dbeta && vec_ok(C));
-    BnReluBwdFn fn{y, scale, shift, mean, invstd, da, C};
-    hipLaunchKernelGGL(bnrelu_bwd_apply_kernel<float>, dim3(apply_blocks(rows, C)), dim3(256), 0, as_stream(stream), fn, gamma,
-                       dgamma, dbeta, bn_train, rows, dy);
-    TAG_LAUNCH_CHECK();
-    return 0;
+    return bnrelu_backward_apply_impl<float>(y, scale, shift, mean, invstd, gamma, da, dy, dgamma, dbeta, rows, C, bn_train,
+                                             stream);
 }
-
 extern "C" int tag_bnrelu_backward_apply_bf16(const void* y, const float* scale, const float* shift, const float* mean,
                                               const float* invstd, const float* gamma, const void* da, void* dy,
                                               const float* dgamma, const float* dbeta, long rows, int C, int bn_train,
                                               void* stream) {
-    TAG_CHECK_ARG(y && scale && shift && mean && invstd && gamma && da && dy && dgamma && dbeta && vec_ok(C));
-    BnReluBwdFnT<bf16_t> fn{static_cast<const bf16_t*>(y), scale, shift, mean, invstd, static_cast<const bf16_t*>(da), C};
-    hipLaunchKernelGGL(bnrelu_bwd_apply_kernel<bf16_t>, dim3(apply_blocks(rows, C)), dim3(256), 0, as_stream(stream), fn,
-                       gamma, dgamma, dbeta, bn_train, rows, static_cast<bf16_t*>(dy));
-    TAG_LAUNCH_CHECK();
-    return 0;
+    return bnrelu_backward_apply_impl<bf16_t>(static_cast<const bf16_t*>(y), scale, shift, mean, invstd, gamma,
+                                              static_cast<const bf16_t*>(da), static_cast<bf16_t*>(dy), dgamma, dbeta, rows, C,
+                                              bn_train, stream);
 }
 
 extern "C" int tag_dropout_mask(uint64_t seed, long n, float p, uint8_t* mask, void* stream) {
@@ -1343,38 +1406,79 @@ extern "C" int tag_mean_w_backward_bf16(const float* dout, long rows, int W, int
     return 0;
 }
 
+// tag_bn_act_backward over x (B, HW, C).  CLIP: the apply pass runs clip by clip and also leaves dt (B, C) = the per-clip sums of dx
+// (cpart: its partial rows, clip (B, 2, C): slot 0 = the sums); dx, dgamma, dbeta are bit-identical to the plain form's
+template <bool CLIP>
+static int bn_act_backward_impl(const float* x, int pre_op, const float* mean, const float* invstd, const float* gamma,
+                                const float* du, float* dx, float* dgamma, float* dbeta, float* dt, double* clip, int B, long HW,
+                                int C, int bn_train, double* partials, double* cpart, hipStream_t st) {
+    const long rows = (long)B * HW;
+    const int nblk = red_blocks(rows, C);
+    BnActBwdFn fn{x, mean, invstd, du, C, pre_op};
+    hipLaunchKernelGGL(reduce2_kernel<BnActBwdFn>, dim3(nblk), dim3(256), 256 * 8 * sizeof(double), st, fn, rows, C, partials);
+    TAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, st, partials, nblk, C, dgamma, dbeta);
+    const int nb = CLIP ? clip_apply_blocks(HW, C, B) : apply_blocks(rows, C);
+    hipLaunchKernelGGL(bn_act_bwd_apply_kernel<CLIP>, CLIP ? dim3(nb, B) : dim3(nb), dim3(256), 0, st, fn, gamma, dgamma, dbeta,
+                       bn_train, HW, dx, cpart);
+    TAG_LAUNCH_CHECK();
+    if constexpr (CLIP) {
+        hipLaunchKernelGGL(clip_fold_kernel, dim3(cdiv(C, 16), B), dim3(FOLD_T), 0, st, cpart, nb, C, clip, nullptr, nullptr, dt);
+        TAG_LAUNCH_CHECK();
+    }
+    return 0;
+}
 extern "C" int tag_bn_act_backward(const float* x, int pre_op, const float* mean, const float* invstd,
                                    const float* gamma, const float* du, float* dx, float* dgamma, float* dbeta,
                                    long rows, int C, int bn_train, void* ws, void* stream) {
     TAG_CHECK_ARG(x && mean && invstd && du && dx && dgamma && dbeta && ws && vec_ok(C) && (pre_op == 0 || pre_op == 1));
-    double* partials = static_cast<double*>(ws);
-    const int nblk = red_blocks(rows, C);
-    BnActBwdFn fn{x, mean, invstd, du, C, pre_op};
-    hipLaunchKernelGGL(reduce2_kernel<BnActBwdFn>, dim3(nblk), dim3(256), 256 * 8 * sizeof(double), as_stream(stream),
-                       fn, rows, C, partials);
-    TAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, as_stream(stream), partials, nblk, C,
-                       dgamma, dbeta);
-    hipLaunchKernelGGL(bn_act_bwd_apply_kernel, dim3(apply_blocks(rows, C)), dim3(256), 0, as_stream(stream), fn, gamma,
-                       dgamma, dbeta, bn_train, rows, dx);
-    TAG_LAUNCH_CHECK();
-    return 0;
+    return bn_act_backward_impl<false>(x, pre_op, mean, invstd, gamma, du, dx, dgamma, dbeta, nullptr, nullptr, 1, rows, C,
+                                       bn_train, static_cast<double*>(ws), nullptr, as_stream(stream));
+}
+// ws: tag_bn_backward_ws_bytes(B*HW, C) bytes, ws_clip: tag_clip_reduce_ws_bytes(B, C) bytes
+extern "C" int tag_bn_act_backward_clip(const float* x, int pre_op, const float* mean, const float* invstd, const float* gamma,
+                                        const float* du, float* dx, float* dgamma, float* dbeta, float* dt, double* clip, int B,
+                                        long HW, int C, int bn_train, void* ws, void* ws_clip, void* stream) {
+    TAG_CHECK_ARG(x && mean && invstd && du && dx && dgamma && dbeta && dt && clip && ws && ws_clip && vec_ok(C));
+    TAG_CHECK_ARG((pre_op == 0 || pre_op == 1) && B > 0 && B <= 65535 && HW > 0);
+    return bn_act_backward_impl<true>(x, pre_op, mean, invstd, gamma, du, dx, dgamma, dbeta, dt, clip, B, HW, C, bn_train,
+                                      static_cast<double*>(ws), static_cast<double*>(ws_clip), as_stream(stream));
 }
 
+// CLIP: one clip per blockIdx.y, and also dt (B, C) = the per-clip sums of dy (partials: tag_clip_reduce_ws_bytes(B, C) bytes,
+// clip (B, 2, C): slot 0 = the sums); dy is bit-identical to the plain form's
+template <bool CLIP>
+static int lppool_leaky_backward_impl(const float* y, const float* dout, float* dy, float* dt, double* clip, int B, int H, int W,
+                                      int C, int ph, int pw, float drop_p, uint64_t seed, double* partials, hipStream_t st) {
+    const long slots = (long)((H + ph - 1) / ph) * ((W + pw - 1) / pw);   // of one clip
+    const int nb = CLIP ? clip_apply_blocks(slots, C, B) : apply_blocks(B * slots, C);
+    const bool launched = dispatch_window(LpBwdWindows{}, ph, pw, [&](auto ph_, auto pw_) {
+        constexpr int PH = ph_, PW = pw_;
+        hipLaunchKernelGGL((lppool_leaky_bwd_kernel<PH, PW, CLIP>), CLIP ? dim3(nb, B) : dim3(nb), dim3(256), 0, st, y, dout, dy, B,
+                           H, W, C, drop_p, seed, partials);
+    });
+    TAG_CHECK_ARG(launched);
+    TAG_LAUNCH_CHECK();
+    if constexpr (CLIP) {
+        hipLaunchKernelGGL(clip_fold_kernel, dim3(cdiv(C, 16), B), dim3(FOLD_T), 0, st, partials, nb, C, clip, nullptr, nullptr, dt);
+        TAG_LAUNCH_CHECK();
+    }
+    return 0;
+}
 extern "C" int tag_lppool_leaky_backward(const float* y, const float* dout, float* dy, int B, int H, int W, int C,
                                          int ph, int pw, float drop_p, uint64_t seed, void* stream) {
     TAG_CHECK_ARG(y && dout && dy && vec_ok(C) && H / ph > 0 && W / pw > 0);
-    const int nb = apply_blocks((long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw), C);
-    bool launched = false;
-    DISPATCH_POOL(2, 4, hipLaunchKernelGGL((lppool_leaky_bwd_kernel<PH, PW>), dim3(nb), dim3(256), 0, as_stream(stream),
-                                           y, dout, dy, B, H, W, C, drop_p, seed))
-    DISPATCH_POOL(1, 4, hipLaunchKernelGGL((lppool_leaky_bwd_kernel<PH, PW>), dim3(nb), dim3(256), 0, as_stream(stream),
-                                           y, dout, dy, B, H, W, C, drop_p, seed))
-    DISPATCH_POOL(2, 2, hipLaunchKernelGGL((lppool_leaky_bwd_kernel<PH, PW>), dim3(nb), dim3(256), 0, as_stream(stream),
-                                           y, dout, dy, B, H, W, C, drop_p, seed))
-    TAG_CHECK_ARG(launched);
-    TAG_LAUNCH_CHECK();
-    return 0;
+    return lppool_leaky_backward_impl<false>(y, dout, dy, nullptr, nullptr, B, H, W, C, ph, pw, drop_p, seed, nullptr,
+                                             as_stream(stream));
+}
+// ws: tag_clip_reduce_ws_bytes(B, C) bytes
+extern "C" int tag_lppool_leaky_backward_clip(const float* y, const float* dout, float* dy, float* dt, double* clip, int B,
+                                              int H, int W, int C, int ph, int pw, float drop_p, uint64_t seed, void* ws,
+                                              void* stream) {
+    TAG_CHECK_ARG(y && dout && dy && dt && clip && ws && B > 0 && B <= 65535 && vec_ok(C) && H / ph > 0 && W / pw > 0);
+    TAG_CHECK_ARG((long)((H + ph - 1) / ph) * ((W + pw - 1) / pw) < (1L << 31));
+    return lppool_leaky_backward_impl<true>(y, dout, dy, dt, clip, B, H, W, C, ph, pw, drop_p, seed, static_cast<double*>(ws),
+                                            as_stream(stream));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1387,15 +1491,6 @@ extern "C" int tag_lppool_leaky_backward(const float* y, const float* dout, floa
 extern "C" size_t tag_clip_reduce_ws_bytes(int B, int C) {
     const long rows = B >= 2048 ? (long)B : 2048;
     return (size_t)(rows < (long)B * RED_MAX_BLOCKS ? rows : (long)B * RED_MAX_BLOCKS) * 2 * (size_t)C * sizeof(double);
-}
-
-static int clip_fold_and_total(const double* partials, int nblk, int B, int C, double* clip, const double* prev,
-                               const float* wcol, float* dt, float* dsum1, float* dsum2, hipStream_t st) {
-    hipLaunchKernelGGL(clip_fold_kernel, dim3(cdiv(C, 16), B), dim3(FOLD_T), 0, st, partials, nblk, C, clip, prev, wcol, dt);
-    TAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, st, clip, B, C, dsum2, dsum1);
-    TAG_LAUNCH_CHECK();
-    return 0;
 }
 
 // out = relu(y * scale[c] + shift[c] + bias[b, c]) over (B, HW, C)
@@ -1416,18 +1511,7 @@ extern "C" int tag_bias_bnrelu_pool_forward(const float* y, const float* scale, 
     TAG_CHECK_ARG(y && scale && shift && bias && out && (pool == 0 || pool == 2 || pool == 3));
     TAG_CHECK_ARG(H / ph > 0 && W / pw > 0 && vec_ok(C) && B > 0 && B <= 65535);   // the clip count its backward puts in gridDim.y
     TAG_CHECK_ARG((long)B * H * W < (1L << 31));
-    bool launched = false;
-    const int nb = apply_blocks((long)B * (H / ph) * (W / pw), C);
-#define BIAS_POOL_FWD hipLaunchKernelGGL((bnact_pool_fwd_kernel<PH, PW, float, 4, true>), dim3(nb), dim3(256), 0, \
-                                         as_stream(stream), y, scale, shift, out, B, H, W, C, 1, pool, drop_p, seed, bias)
-    DISPATCH_POOL(2, 2, BIAS_POOL_FWD)
-    DISPATCH_POOL(1, 2, BIAS_POOL_FWD)
-    DISPATCH_POOL(1, 1, BIAS_POOL_FWD)
-    DISPATCH_POOL(2, 1, BIAS_POOL_FWD)
-#undef BIAS_POOL_FWD
-    TAG_CHECK_ARG(launched);
-    TAG_LAUNCH_CHECK();
-    return 0;
+    return bnact_pool_forward_impl<float, true>(y, scale, shift, bias, out, B, H, W, C, ph, pw, 1, pool, drop_p, seed, stream);
 }
 
 // backward of tag_bias_bnrelu_pool_forward: dz = d(bn(y) + bias) per position; clip[b] = [sum dz | sum dz*xhat] over clip b,
@@ -1441,31 +1525,8 @@ extern "C" int tag_bias_bnrelu_pool_backward(const float* y, const float* scale,
     TAG_CHECK_ARG(pool == 0 || pool == 2 || pool == 3);
     TAG_CHECK_ARG(vec_ok(C) && H / ph > 0 && W / pw > 0 && B > 0 && B <= 65535);   // one clip per blockIdx.y
     TAG_CHECK_ARG((long)B * H * W < (1L << 31));
-    const float wavg = pool == 3 ? 0.0f : 1.0f / (float)(ph * pw), wmax = pool == 2 ? 0.0f : 1.0f;
-    double* partials = static_cast<double*>(ws);
-    const int nblk = clip_red_blocks((long)(H / ph) * (W / pw), C, B);
-    const int nb = apply_blocks((long)B * ((H + ph - 1) / ph) * ((W + pw - 1) / pw), C);
-    hipStream_t st = as_stream(stream);
-    bool launched = false;
-#define BIAS_POOL_BWD                                                                                                \
-    {                                                                                                                \
-        PoolBwdCtx<PH, PW, float, 4, true> ctx{y, scale, shift, mean, invstd, dout, B, H, W, C, drop_p, seed, wavg, wmax}; \
-        ctx.bias = bias;                                                                                             \
-        hipLaunchKernelGGL((pool_bwd_reduce_kernel<PH, PW, float, 4, true>), dim3(nblk, B), dim3(256),               \
-                           256 * 2 * 4 * sizeof(double), st, ctx, partials);                                         \
-        TAG_LAUNCH_CHECK();                                                                                          \
-        if (int e = clip_fold_and_total(partials, nblk, B, C, clip, nullptr, nullptr, nullptr, dbeta, dgamma, st)) return e; \
-        hipLaunchKernelGGL((pool_bwd_apply_kernel<PH, PW, float, 4, true>), dim3(nb), dim3(256), 0, st, ctx, gamma, dgamma, \
-                           dbeta, bn_train, dy);                                                                     \
-    }
-    DISPATCH_POOL(2, 2, BIAS_POOL_BWD)
-    DISPATCH_POOL(1, 2, BIAS_POOL_BWD)
-    DISPATCH_POOL(1, 1, BIAS_POOL_BWD)
-    DISPATCH_POOL(2, 1, BIAS_POOL_BWD)
-#undef BIAS_POOL_BWD
-    TAG_CHECK_ARG(launched);
-    TAG_LAUNCH_CHECK();
-    return 0;
+    return bnrelu_pool_backward_impl<float, true>(y, scale, shift, mean, invstd, gamma, bias, dout, dy, dgamma, dbeta, clip, B, H, W,
+                                                  C, ph, pw, pool, drop_p, seed, bn_train, ws, stream);
 }
 
 // backward of tag_bias_bnrelu_forward given da = d out: same sums and apply as tag_bnrelu_backward, clip by clip; dt (B, C),
@@ -1551,193 +1612,6 @@ extern "C" int tag_leaky_backward(const float* z, const float* dout, float* dz, 
     hipLaunchKernelGGL(leaky_bwd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, as_stream(stream),
                        reinterpret_cast<const float4*>(z), reinterpret_cast<const float4*>(dout), reinterpret_cast<float4*>(dz),
                        n / 4);
-    TAG_LAUNCH_CHECK();
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// Backward passes of CrossCDur that also emit the per-clip sums of what they write: the text enters as a per-clip bias on the raw
-// conv output z, so d bias[b, c] = sum over (h, w) of dz[b, h, w, c], and dz is the output of lppool_leaky_bwd_kernel (blocks 1,
-// 3, 5) or bn_act_bwd_apply_kernel (blocks 2, 4).  CLIP forms of those two kernels: one clip per blockIdx.y, the same arithmetic
-// per element (dz is bit-identical to the plain kernels'), every thread adds what it stores to fp64 sums of its channel quad,
-// folded through LDS into partial rows [clip][blk][2][C] (slot 1 unused, zero) that never straddle two clips;
-// clip_fold_kernel folds them in a fixed order (no atomics) -- the protocol of the per-clip bias passes above.  They replace a
-// tag_rowgroup_colsum pass over dz.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void clip_block_fold(double s[4], int tpr, int rpi, int rsub, int c, int C,
-                                                double* __restrict__ partials) {
-    __shared__ double sred[256][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sred[threadIdx.x][j] = s[j];
-    __syncthreads();
-    if (rsub == 0) {
-        for (int q = 1; q < rpi; ++q)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s[j] += sred[threadIdx.x + q * tpr][j];
-        double* p = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * C;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { p[c + j] = s[j]; p[C + c + j] = 0.0; }
-    }
-}
-
-template <int PH, int PW>
-__global__ __launch_bounds__(256) void lppool_leaky_bwd_clip_kernel(const float* __restrict__ y, const float* __restrict__ dout,
-                                                                    float* __restrict__ dy, int H, int W, int C, float drop_p,
-                                                                    uint64_t seed, double* __restrict__ partials) {
-    const int Ho = H / PH, Wo = W / PW, C4 = C >> 2, rpi = 256 / C4;
-    const int c = (threadIdx.x % C4) << 2, rsub = threadIdx.x / C4;
-    const int Hs = (H + PH - 1) / PH, Ws = (W + PW - 1) / PW;
-    const int slots = Hs * Ws;                                  // of ONE clip
-    const int b = blockIdx.y;
-    const float keep_scale = drop_p > 0.0f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    double acc[4] = {0, 0, 0, 0};
-    for (int r = blockIdx.x * rpi + rsub; r < slots; r += gridDim.x * rpi) {
-        const int ws = r % Ws, hs = r / Ws;
-        const bool full = hs < Ho && ws < Wo;
-        float a[PH][PW][4], yv[PH][PW][4], sum[4] = {0, 0, 0, 0};
-        bool ex[PH][PW];
-#pragma unroll
-        for (int dh = 0; dh < PH; ++dh)
-#pragma unroll
-            for (int dw = 0; dw < PW; ++dw) {
-                const int h = hs * PH + dh, w = ws * PW + dw;
-                ex[dh][dw] = h < H && w < W;
-                float4 v = make_float4(0, 0, 0, 0);
-                if (ex[dh][dw]) v = *reinterpret_cast<const float4*>(y + (((size_t)b * H + h) * W + w) * C + c);
-                const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    yv[dh][dw][j] = vv[j];
-                    a[dh][dw][j] = leaky01(vv[j]);
-                    const float a2 = a[dh][dw][j] * a[dh][dw][j];
-                    sum[j] += a2 * a2;
-                }
-            }
-        float k[4] = {0, 0, 0, 0};
-        if (full) {
-            const size_t oi = (((size_t)b * Ho + hs) * Wo + ws) * C + c;
-            const float4 g4 = *reinterpret_cast<const float4*>(dout + oi);
-            float g[4] = {g4.x, g4.y, g4.z, g4.w};
-            const uint64_t bits = drop_p > 0.0f ? tag_keep4_bits(seed, (uint64_t)(oi >> 2)) : 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (drop_p > 0.0f) g[j] = tag_keep4(bits, j, tag_keep4_threshold(drop_p)) ? g[j] * keep_scale : 0.0f;
-                const float out = sqrtf(sqrtf(sum[j]));
-                k[j] = out > 0.0f ? g[j] / (out * out * out) : 0.0f;
-            }
-        }
-#pragma unroll
-        for (int dh = 0; dh < PH; ++dh)
-#pragma unroll
-            for (int dw = 0; dw < PW; ++dw) {
-                if (!ex[dh][dw]) continue;
-                float o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float aa = a[dh][dw][j];
-                    const float da = k[j] * aa * aa * aa;
-                    o[j] = yv[dh][dw][j] > 0.0f ? da : 0.1f * da;
-                    acc[j] += o[j];
-                }
-                const int h = hs * PH + dh, w = ws * PW + dw;
-                *reinterpret_cast<float4*>(dy + (((size_t)b * H + h) * W + w) * C + c) = make_float4(o[0], o[1], o[2], o[3]);
-            }
-    }
-    clip_block_fold(acc, C4, rpi, rsub, c, C, partials);
-}
-
-// bn_act_bwd_apply_kernel clip by clip: rows = rows of ONE clip, the BatchNorm count is that of all clips
-__global__ __launch_bounds__(256) void bn_act_bwd_apply_clip_kernel(BnActBwdFn fn, const float* __restrict__ gamma,
-                                                                    const float* __restrict__ dgamma,
-                                                                    const float* __restrict__ dbeta, int bn_train,
-                                                                    long rows, float* __restrict__ dx,
-                                                                    double* __restrict__ partials) {
-    const int C = fn.C, tpr = C >> 2, rpi = 256 / tpr;
-    const int c = (threadIdx.x % tpr) << 2, rsub = threadIdx.x / tpr;
-    const float invN = 1.0f / (float)(rows * gridDim.y);
-    const long r0 = (long)blockIdx.y * rows;
-    fn.prep(c);
-    float k0[4], k1[4], k2[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        k0[j] = (gamma ? gamma[c + j] : 1.0f) * fn.invstd[c + j];
-        k1[j] = bn_train ? dbeta[c + j] * invN : 0.0f;
-        k2[j] = bn_train ? dgamma[c + j] * invN : 0.0f;
-    }
-    const float mv[4] = {fn.m.x, fn.m.y, fn.m.z, fn.m.w}, iv[4] = {fn.is.x, fn.is.y, fn.is.z, fn.is.w};
-    double acc[4] = {0, 0, 0, 0};
-    for (long r = (long)blockIdx.x * rpi + rsub; r < rows; r += (long)gridDim.x * rpi) {
-        const float4 xv = *reinterpret_cast<const float4*>(fn.x + (size_t)(r0 + r) * C + c);
-        const float4 g = *reinterpret_cast<const float4*>(fn.du + (size_t)(r0 + r) * C + c);
-        const float xx[4] = {xv.x, xv.y, xv.z, xv.w}, gg[4] = {g.x, g.y, g.z, g.w};
-        float o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float v = fn.pre == 1 ? leaky01(xx[j]) : xx[j];
-            const float dv = k0[j] * (gg[j] - k1[j] - (v - mv[j]) * iv[j] * k2[j]);
-            o[j] = (fn.pre == 1 && xx[j] <= 0.0f) ? 0.1f * dv : dv;
-            acc[j] += o[j];
-        }
-        *reinterpret_cast<float4*>(dx + (size_t)(r0 + r) * C + c) = make_float4(o[0], o[1], o[2], o[3]);
-    }
-    clip_block_fold(acc, tpr, rpi, rsub, c, C, partials);
-}
-
-// workgroups per clip of the two kernels above: ~4 iterations per thread, at most 2048 partial rows over all clips
-// (tag_clip_reduce_ws_bytes)
-static int clip_apply_blocks(long rows_per_clip, int C, int B) {
-    const int rpi = 256 / (C >> 2);
-    long nb = (rows_per_clip + (long)rpi * 4 - 1) / ((long)rpi * 4);
-    const int cap = B >= 2048 ? 1 : (2048 / B < RED_MAX_BLOCKS ? 2048 / B : RED_MAX_BLOCKS);
-    if (nb > cap) nb = cap;
-    return (int)(nb < 1 ? 1 : nb);
-}
-
-// tag_lppool_leaky_backward that also writes dt (B, C) = per-clip sums of dy; clip (B, 2, C) doubles (slot 0 = the sums),
-// ws: tag_clip_reduce_ws_bytes(B, C) bytes.  dy is bit-identical to tag_lppool_leaky_backward's.
-extern "C" int tag_lppool_leaky_backward_clip(const float* y, const float* dout, float* dy, float* dt, double* clip, int B,
-                                              int H, int W, int C, int ph, int pw, float drop_p, uint64_t seed, void* ws,
-                                              void* stream) {
-    TAG_CHECK_ARG(y && dout && dy && dt && clip && ws && B > 0 && B <= 65535 && vec_ok(C) && H / ph > 0 && W / pw > 0);
-    TAG_CHECK_ARG((long)((H + ph - 1) / ph) * ((W + pw - 1) / pw) < (1L << 31));
-    double* partials = static_cast<double*>(ws);
-    hipStream_t st = as_stream(stream);
-    const int nb = clip_apply_blocks((long)((H + ph - 1) / ph) * ((W + pw - 1) / pw), C, B);
-    bool launched = false;
-#define LP_CLIP hipLaunchKernelGGL((lppool_leaky_bwd_clip_kernel<PH, PW>), dim3(nb, B), dim3(256), 0, st, y, dout, dy, H, W, C, \
-                                   drop_p, seed, partials)
-    DISPATCH_POOL(2, 4, LP_CLIP)
-    DISPATCH_POOL(1, 4, LP_CLIP)
-    DISPATCH_POOL(2, 2, LP_CLIP)
-#undef LP_CLIP
-    TAG_CHECK_ARG(launched);
-    TAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(clip_fold_kernel, dim3(cdiv(C, 16), B), dim3(FOLD_T), 0, st, partials, nb, C, clip, nullptr, nullptr, dt);
-    TAG_LAUNCH_CHECK();
-    return 0;
-}
-
-// tag_bn_act_backward over x (B, HW, C) that also writes dt (B, C) = per-clip sums of dx; ws: tag_bn_backward_ws_bytes(B*HW, C)
-// bytes, ws_clip: tag_clip_reduce_ws_bytes(B, C) bytes.  dx, dgamma, dbeta are bit-identical to tag_bn_act_backward's.
-extern "C" int tag_bn_act_backward_clip(const float* x, int pre_op, const float* mean, const float* invstd, const float* gamma,
-                                        const float* du, float* dx, float* dgamma, float* dbeta, float* dt, double* clip, int B,
-                                        long HW, int C, int bn_train, void* ws, void* ws_clip, void* stream) {
-    TAG_CHECK_ARG(x && mean && invstd && du && dx && dgamma && dbeta && dt && clip && ws && ws_clip && vec_ok(C));
-    TAG_CHECK_ARG((pre_op == 0 || pre_op == 1) && B > 0 && B <= 65535 && HW > 0);
-    const long rows = (long)B * HW;
-    double* partials = static_cast<double*>(ws);
-    double* cpart = static_cast<double*>(ws_clip);
-    hipStream_t st = as_stream(stream);
-    const int nblk = red_blocks(rows, C);
-    BnActBwdFn fn{x, mean, invstd, du, C, pre_op};
-    hipLaunchKernelGGL(reduce2_kernel<BnActBwdFn>, dim3(nblk), dim3(256), 256 * 8 * sizeof(double), st, fn, rows, C, partials);
-    TAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3(cdiv(C, 16)), dim3(FOLD_T), 0, st, partials, nblk, C, dgamma, dbeta);
-    const int nb = clip_apply_blocks(HW, C, B);
-    hipLaunchKernelGGL(bn_act_bwd_apply_clip_kernel, dim3(nb, B), dim3(256), 0, st, fn, gamma, dgamma, dbeta, bn_train, HW, dx,
-                       cpart);
-    TAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(clip_fold_kernel, dim3(cdiv(C, 16), B), dim3(FOLD_T), 0, st, cpart, nb, C, clip, nullptr, nullptr, dt);
     TAG_LAUNCH_CHECK();
     return 0;
 }
