@@ -562,7 +562,10 @@ extern "C" int tag_conv3x3_wino_wgrad(const float* x, int prologue, const float*
     TAG_CHECK_ARG(prologue >= 0 && prologue <= 3 && (prologue == 0 || (in_scale && in_shift)));
     hipStream_t st = as_stream(stream);
     if (wino_fused_wgrad_ok(Cin, Cout) && x) {
-        wino_fused_wgrad_run(x, prologue, in_scale, in_shift, dy, dw, B, H, W, Cin, Cout, static_cast<float*>(ws), st);
+        if (wino_fused_wgrad_run(x, prologue, in_scale, in_shift, dy, dw, B, H, W, Cin, Cout, static_cast<float*>(ws), st) != 0) {
+            tag_set_error("%s:%d: the weight-gradient kernel's LDS limit could not be set on this device", __FILE__, __LINE__);
+            return TAG_EINVAL;
+        }
         TAG_LAUNCH_CHECK();
         return 0;
     }

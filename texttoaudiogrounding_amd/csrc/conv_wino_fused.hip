@@ -34,7 +34,10 @@
 //
 // wino_fused_wgrad_kernel: dw = G^T [ sum_t (A dY A^T) (.) (B^T d B) ] G with BOTH transforms formed at staging: 64 ci x 64 co x
 // 16 xi accumulators per workgroup, K = tiles in chunks of 8, split over S slices of the tile axis; partial 3 x 3 filters per
-// (slice, xi half) are folded in a fixed order by wino_fused_wgrad_finish_kernel.
+// (slice, xi half) are folded in a fixed order by wino_fused_wgrad_finish_kernel.  wino_fused_wgrad_rows_kernel: the same sums
+// with ONE transform row x 128 ci x 128 co per workgroup (channel counts that are multiples of 128): a third of the fragment
+// reads, half of the LDS stores and of the transform VALU, the same bits.
+#include <atomic>
 #include <type_traits>
 #include "conv_wino.h"
 
@@ -927,6 +930,344 @@ __global__ __launch_bounds__(256) void wino_fused_wgrad_finish_kernel(const floa
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Weight gradient, ROW SPLIT (Cin and Cout multiples of 128).  wino_fused_wgrad_kernel forms B^T d B of a (tile, ci) in every co
+// block and A dY A^T of a (tile, co) in every ci block.  The xi axis costs nothing to split -- the partial products go to the
+// share workspace anyway -- so here a workgroup owns ONE transform row r0 (xi = 4 r0 + s, s = 0..3) x 128 ci x 128 co: the same
+// 128 accumulator registers, the same 32 MFMAs per wave and chunk, the same grid (4 Cin/128 Cout/128 S), and of each transform
+// only row r0: two of the four window rows (r0 = 0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3) and g0, g0 + g1, g0 - g1 or g1.
+//   * staging: tile = wave as above (uniform geometry on the scalar unit); a lane = (channel quad q, window column s) stages the
+//     items of quads q and q + 16: 2 x 2 loads + 4 + 4 VALU + one ds_write_b128 for V, 2 x (1 or 2) loads + (0 or 4) + 4 VALU + one
+//     ds_write_b128 for D.  Same element-wise expressions and sign conventions as above: every staged value has the same bits.
+//   * LDS images k-major, [s 4][tile 8][channel 128], planes 4128 B apart (the 8 lanes of a ds_write_b128 group -- 2 quads x 4 s --
+//     cover 128 contiguous bytes mod 128); two stages [V0 | V1 | D0 | D1] = 66 KB, every stage / block / k offset an immediate
+//     of ONE base register per operand.
+//   * wave = (s, ci half): 2 ci blocks x 4 co blocks of xi = (r0, s); per k-step 2 A + 4 B fragment reads feed 8 MFMAs (the
+//     fragments of k-step e + 1 are requested behind the first four MFMAs of k-step e).  k order per set as above: chunk after
+//     chunk, e = 0..3 in a chunk -- every per-xi, per-slice sum is bit-identical to wino_fused_wgrad_kernel's.
+//   * epilogue: no fold; raw sums to part[slice][xi 16][co][ci], 16-byte stores of the 4 consecutive ci of a register quad.
+//     wino_fused_wgrad_rows_finish_kernel<Q> forms the two half-shares of every slice with the expressions of the epilogue above
+//     and adds them in the order of wino_fused_wgrad_finish_kernel<Q> (p = 2 slice + half, Q runs): dw has the same bits.
+constexpr int RPL = 8 * 128 + 8;              // floats per s plane of an operand buffer (4128 B: planes rotate by 32 B mod 128)
+constexpr int RBUF = 4 * RPL;                 // one operand buffer (V or D) of one pipeline stage
+
+// Dispatch rule: every layer whose channel counts are multiples of 128 on both sides.  ms per launch at B = 64 (prologue 1; the
+// medians of three fresh processes per kernel, alternating; the spread of the 64 x 64 x 16 kernel's three is 0.001-0.018 ms;
+// docs/experiments_wgrad_rows.md):
+//     layer               64 x 64 x 16   row split
+//     250x8   512 -> 512      2.737        2.413
+//     250x8   256 -> 512      1.319        1.145
+//     250x16  256 -> 256      1.314        1.155
+//     250x16  128 -> 256      0.676        0.587
+//     500x32  128 -> 128      1.304        1.153
+// (64 -> 128, 64 -> 64 and counts such as 192 have no 128-channel blocks on both sides and keep the 64 x 64 x 16 kernel.)
+inline bool wg_rows_ok(int Cin, int Cout) { return Cin % 128 == 0 && Cout % 128 == 0; }
+
+template <int PRO, int R0>
+__device__ __forceinline__ void wgrad_rows_body(float* smem, const float* __restrict__ x, const float* __restrict__ in_scale,
+                                                const float* __restrict__ in_shift, const float* __restrict__ dy,
+                                                float* __restrict__ part, int B, int H, int W, int Cin, int Cout, int th, int tw,
+                                                int sl, int cib, int cob, int cps) {
+    constexpr int RA = R0 == 0 ? 0 : (R0 == 2 ? 2 : 1);           // row r0 of B^T d = d[RA] - d[RB]  (r0 = 1: d[RA] + d[RB])
+    constexpr int RB = R0 == 0 ? 2 : (R0 == 1 ? 2 : (R0 == 2 ? 1 : 3));
+    constexpr int NG = (R0 == 1 || R0 == 2) ? 2 : 1;              // gradient rows loaded: g0, g0 (+|-) g1, g1
+    constexpr int GA = R0 == 3 ? 1 : 0;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // ---- staging role: tile = wave (8 tiles per chunk), lane = (channel quad, window column s), items = quads q and q + 16
+    const int s = lane & 3, quad = lane >> 2;
+    const float fb = s == 1 ? 1.0f : -1.0f;                       // V[r][s] = tt[r][s] + fb tt[r][{2,2,1,1}[s]]  (column 3 negated)
+    const float cb = s == 1 ? 1.0f : (s == 2 ? -1.0f : 0.0f);     // D[r][s] = R[r][s & 1] + cb R[r][{0,0,3,3}[s] & 1] (column 3 negated)
+    const int xbytes = (int)(((size_t)B * H * W + 1) * Cin * 4), dbytes = (int)((size_t)B * H * W * Cout * 4);
+    const unsigned xvo = (unsigned)((s * Cin + cib * 128 + 4 * quad) * 4);          // (item 1: + 256 B, an immediate)
+    const unsigned dvo = (unsigned)(((s & 1) * Cout + cob * 128 + 4 * quad) * 4);
+    const int vw0 = s * RPL + wave * 128 + 4 * quad;              // + 64 i  (V image; the D image is 2 RBUF further)
+    int tb, ti, tj;
+    {
+        const unsigned t = (unsigned)sl * (unsigned)cps * 8u + (unsigned)wave;
+        const unsigned bi = t / (unsigned)tw;
+        tj = (int)(t - bi * (unsigned)tw);
+        tb = (int)(bi / (unsigned)th);
+        ti = (int)(bi - (unsigned)tb * (unsigned)th);
+        tb = __builtin_amdgcn_readfirstlane(tb); ti = __builtin_amdgcn_readfirstlane(ti); tj = __builtin_amdgcn_readfirstlane(tj);
+    }
+    auto advance = [&]() {                            // + 8 tiles
+        tj += 8;
+        while (tj >= tw) { tj -= tw; ++ti; }
+        while (ti >= th) { ti -= th; ++tb; }
+    };
+    f32x4 psc[2], psh[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        psc[i] = (f32x4){1.0f, 1.0f, 1.0f, 1.0f}; psh[i] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        if (PRO != 0) {
+            psc[i] = *reinterpret_cast<const f32x4*>(in_scale + cib * 128 + 64 * i + 4 * quad);
+            psh[i] = *reinterpret_cast<const f32x4*>(in_shift + cib * 128 + 64 * i + 4 * quad);
+        }
+    }
+
+    // ---- MFMA role: wave = (s plane, ci half)
+    const int sp = wave & 3, cih = wave >> 2;
+    const int kl = lane >> 5, ml = lane & 31;
+    int ab = sp * RPL + kl * 128 + cih * 64 + ml;                 // V fragment (A operand: rows = ci); + 32 ci block + 256 e
+    int bb = 2 * RBUF + sp * RPL + kl * 128 + ml;                 // D fragment (B operand: columns = co); + 32 co block + 256 e
+    asm volatile("" : "+v"(ab), "+v"(bb));
+
+    f32x16 acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
+
+    f32x4 xr[2][2], gr[2][NG];                         // [item][row]
+    float okn[2] = {0.0f, 0.0f}, okc[2];               // PRO != 0: upper clamp (+inf | 0) of the rows in flight / being transformed
+    unsigned xcol = 0x80000000u, gcol = 0x80000000u;   // vector offsets of the chunk being loaded (out of range = column outside the image)
+    float xclamp = 0.0f;
+    auto col_offsets = [&]() {                         // once per chunk, before its loads
+        const bool cx = (unsigned)(2 * tj - 1 + s) < (unsigned)W;
+        xcol = cx ? xvo : 0x80000000u;
+        gcol = (2 * tj + (s & 1)) < W ? dvo : 0x80000000u;
+        if (PRO != 0) xclamp = cx ? INFINITY : 0.0f;
+    };
+    auto load_x = [&](int j) {                         // window row RA (j = 0) / RB (j = 1) of the tile (tb, ti, tj), both items
+        const int h = 2 * ti - 1 + (j == 0 ? RA : RB);
+        const bool rv = tb < B && (unsigned)h < (unsigned)H;
+        const int so = (int)(((unsigned)(tb * H + h) * (unsigned)W + 2u * (unsigned)tj) * (unsigned)(Cin * 4));     // (unused when !rv)
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x) - Cin, 0, rv ? xbytes : 0, 0x00020000);
+        xr[0][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, xcol, so, 0));
+        xr[1][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, xcol + 256u, so, 0));
+        if (PRO != 0) okn[j] = rv ? xclamp : 0.0f;
+    };
+    auto load_g = [&](int j) {                         // gradient row 2 ti + GA + j, column 2 tj + (s & 1), both items
+        const int h = 2 * ti + GA + j;
+        const bool rv = tb < B && h < H;
+        const int so = (int)(((unsigned)(tb * H + h) * (unsigned)W + 2u * (unsigned)tj) * (unsigned)(Cout * 4));
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy), 0, rv ? dbytes : 0, 0x00020000);
+        gr[0][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, gcol, so, 0));
+        gr[1][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, gcol + 256u, so, 0));
+    };
+    f32x4 d[2][2], vv;
+    float tt[2][4], R[2][4];
+    auto x_row = [&](int i, int j) {
+        if (PRO == 0) {
+            d[i][j] = xr[i][j];
+        } else if (PRO == 1) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d[i][j][k] = __builtin_amdgcn_fmed3f(fmaf(xr[i][j][k], psc[i][k], psh[i][k]), 0.0f, okc[j]);
+        } else {
+            const f32x4 v = fused_prologue<PRO>(xr[i][j], psc[i], psh[i]);
+            d[i][j] = okc[j] > 0.0f ? v : (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        }
+    };
+    auto x_col = [&](int i) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tt[i][k] = R0 == 1 ? d[i][0][k] + d[i][1][k] : d[i][0][k] - d[i][1][k];
+    };
+    auto v_write = [&](float* Vb, int i) {
+        quad_fmac_2211(tt[i], fb, vv);
+        *reinterpret_cast<f32x4*>(Vb + vw0 + 64 * i) = vv;
+    };
+    auto g_rows = [&](int i) {                         // row r0 of A g (row 3 of D is stored NEGATED, as above)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (NG == 1) R[i][k] = gr[i][0][k];
+            else R[i][k] = R0 == 1 ? gr[i][0][k] + gr[i][NG - 1][k] : gr[i][0][k] - gr[i][NG - 1][k];
+        }
+    };
+    auto d_write = [&](float* Db, int i) {
+        quad_fmac_0033(R[i], cb, vv);
+        *reinterpret_cast<f32x4*>(Db + vw0 + 64 * i) = vv;
+    };
+    auto rotate_ok = [&]() {
+        if (PRO != 0) { okc[0] = okn[0]; okc[1] = okn[1]; }
+    };
+    auto load_chunk = [&]() {
+        col_offsets();
+        load_x(0); load_x(1);
+#pragma unroll
+        for (int j = 0; j < NG; ++j) load_g(j);
+        advance();
+    };
+
+    // ---- pipeline prologue: chunk 0 into buffer 0, chunk 1 into the registers (both requested before anything waits)
+    {
+        f32x4 x0[2][2], g0[2][NG], x1[2][2], g1[2][NG];
+        float ok0[2], ok1[2];
+        load_chunk();
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) x0[i][j] = xr[i][j];
+#pragma unroll
+            for (int j = 0; j < NG; ++j) g0[i][j] = gr[i][j];
+        }
+        ok0[0] = okn[0]; ok0[1] = okn[1];
+        load_chunk();                                  // chunk 1 (stays in xr / gr / okn for the first iteration)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) { x1[i][j] = xr[i][j]; xr[i][j] = x0[i][j]; }
+#pragma unroll
+            for (int j = 0; j < NG; ++j) { g1[i][j] = gr[i][j]; gr[i][j] = g0[i][j]; }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { ok1[j] = okn[j]; okc[j] = ok0[j]; }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            x_row(i, 0); x_row(i, 1); x_col(i); g_rows(i);
+            v_write(smem, i); d_write(smem + 2 * RBUF, i);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) xr[i][j] = x1[i][j];
+#pragma unroll
+            for (int j = 0; j < NG; ++j) gr[i][j] = g1[i][j];
+        }
+        okn[0] = ok1[0]; okn[1] = ok1[1];
+    }
+    __syncthreads();
+
+    float fA[2][2], fB[2][4];                          // fragments of two k-steps: [e & 1][block]
+#define WR_FRAG(E)                                                                                            \
+    do {                                                                                                      \
+        fA[(E) & 1][0] = cur[ab + 256 * (E)]; fA[(E) & 1][1] = cur[ab + 32 + 256 * (E)];                      \
+        _Pragma("unroll") for (int b = 0; b < 4; ++b) fB[(E) & 1][b] = cur[bb + 32 * b + 256 * (E)];          \
+    } while (0)
+#define WR_M4(E, A_)                                                                                          \
+    _Pragma("unroll") for (int b = 0; b < 4; ++b)                                                             \
+        acc[4 * (A_) + b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fA[(E) & 1][A_], fB[(E) & 1][b], acc[4 * (A_) + b], 0, 0, 0)
+#define WR_SB __builtin_amdgcn_sched_barrier(0)
+    // (two copies of the chunk body, one per pipeline stage: stage offsets as LDS-instruction immediates)
+    auto chunk = [&](auto stage) {
+        constexpr int ST = decltype(stage)::value;
+        const float* cur = smem + ST * RBUF;
+        float* nxt = smem + (1 - ST) * RBUF;
+        WR_SB;
+        WR_FRAG(0); WR_SB;
+        WR_M4(0, 0); WR_SB; rotate_ok(); x_row(0, 0); x_row(0, 1); x_row(1, 0); x_row(1, 1); x_col(0); x_col(1); WR_SB;
+        WR_FRAG(1); WR_M4(0, 1); WR_SB; v_write(nxt, 0); v_write(nxt, 1); WR_SB;
+        WR_M4(1, 0); WR_SB; col_offsets(); load_x(0); load_x(1); WR_SB;
+        WR_FRAG(2); WR_M4(1, 1); WR_SB; g_rows(0); g_rows(1); d_write(nxt + 2 * RBUF, 0); WR_SB;
+        WR_M4(2, 0); WR_SB; d_write(nxt + 2 * RBUF, 1);
+        _Pragma("unroll") for (int j = 0; j < NG; ++j) load_g(j);
+        advance(); WR_SB;
+        WR_FRAG(3); WR_M4(2, 1); WR_SB;
+        WR_M4(3, 0); WR_SB;
+        WR_M4(3, 1); WR_SB;
+        __syncthreads();
+    };
+    {
+        int c = 0;
+        for (; c + 1 < cps; c += 2) {
+            chunk(std::integral_constant<int, 0>{});
+            chunk(std::integral_constant<int, 1>{});
+        }
+        if (c < cps) chunk(std::integral_constant<int, 0>{});
+    }
+#undef WR_FRAG
+#undef WR_M4
+#undef WR_SB
+
+    // ---- raw sums of xi = 4 r0 + s: part[slice][xi][co][ci], the lane's register quad = 4 consecutive ci of one co
+    float* pb = part + (((size_t)sl * 16 + 4 * R0 + sp) * Cout + cob * 128 + ml) * Cin + cib * 128 + cih * 64 + 4 * kl;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int rq = 0; rq < 4; ++rq)
+                *reinterpret_cast<f32x4*>(pb + (size_t)(32 * b) * Cin + 32 * a + 8 * rq) =
+                    (f32x4){acc[4 * a + b][4 * rq], acc[4 * a + b][4 * rq + 1], acc[4 * a + b][4 * rq + 2], acc[4 * a + b][4 * rq + 3]};
+}
+
+template <int PRO>
+__global__ __launch_bounds__(512) void wino_fused_wgrad_rows_kernel(const float* __restrict__ x, const float* __restrict__ in_scale,
+                                                                    const float* __restrict__ in_shift, const float* __restrict__ dy,
+                                                                    float* __restrict__ part, int B, int H, int W, int Cin, int Cout,
+                                                                    int th, int tw, int nci, int nco, int S, int cps) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    // workgroup = (slice, ci block of 128, co block of 128, r0), r0 fastest: the four rows of a block read the same x and dy rows
+    const int per = nci * nco * 4;
+    const int L = xcd_remap(blockIdx.x, per * S);
+    const int sl = L / per;
+    const int rem = L - sl * per;
+    const int r0 = rem & 3, blk = rem >> 2;
+    const int cib = blk / nco, cob = blk - cib * nco;
+#define WR_CASE(R_) wgrad_rows_body<PRO, R_>(smem, x, in_scale, in_shift, dy, part, B, H, W, Cin, Cout, th, tw, sl, cib, cob, cps)
+    switch (r0) {
+        case 0: WR_CASE(0); break;
+        case 1: WR_CASE(1); break;
+        case 2: WR_CASE(2); break;
+        default: WR_CASE(3); break;
+    }
+#undef WR_CASE
+}
+
+// dw (Cout,Cin,3,3) from part[slice][xi][co][ci]: thread = (co, ci) x run q of the share axis.  Share p = 2 slice + hh is the
+// epilogue of wino_fused_wgrad_kernel for xi half hh, line by line; the runs and their order are wino_fused_wgrad_finish_kernel<Q>'s.
+template <int Q>
+__global__ __launch_bounds__(256) void wino_fused_wgrad_rows_finish_kernel(const float* __restrict__ part, int nshare, long n,
+                                                                           float* __restrict__ dw) {
+    constexpr int E = 256 / Q;
+    __shared__ float run[Q > 1 ? 256 * 9 : 1];
+    const int el = threadIdx.x % E, q = threadIdx.x / E;
+    const int per = (nshare + Q - 1) / Q;
+    const int p0 = q * per, p1 = (p0 + per < nshare) ? p0 + per : nshare;
+    for (long e0 = (long)blockIdx.x * E; e0 < n; e0 += (long)gridDim.x * E) {
+        const long e = e0 + el;
+        float a[9];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) a[j] = 0.0f;
+        if (e < n)
+            for (int p = p0; p < p1; ++p) {
+                const int hh = p & 1;
+                const float* m = part + (size_t)((p >> 1) * 16 + 8 * hh) * n + e;     // xi = 4 (2 hh + {0, 1}) + sx
+                float P[3][4];
+#pragma unroll
+                for (int sx = 0; sx < 4; ++sx) {
+                    const float m0 = m[(size_t)sx * n], m1 = m[(size_t)(4 + sx) * n];
+                    if (hh == 0) { P[0][sx] = m0 + 0.5f * m1; P[1][sx] = 0.5f * m1; P[2][sx] = 0.5f * m1; }      // transform rows r = 0, 1
+                    else { P[0][sx] = 0.5f * m0; P[1][sx] = -0.5f * m0; P[2][sx] = 0.5f * m0 - m1; }              // rows r = 2, 3 (m1 = -dU of row 3)
+                }
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    const float hs = 0.5f * (P[t][1] + P[t][2]), hd = 0.5f * (P[t][1] - P[t][2]);
+                    a[3 * t + 0] += P[t][0] + hs;
+                    a[3 * t + 1] += hd;
+                    a[3 * t + 2] += hs + P[t][3];
+                }
+            }
+        if (Q > 1) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) run[j * 256 + threadIdx.x] = a[j];
+            __syncthreads();
+            if (q == 0) {
+#pragma unroll
+                for (int k = 1; k < Q; ++k)
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) a[j] += run[j * 256 + k * E + el];
+            }
+            __syncthreads();
+        }
+        if (q == 0 && e < n) {
+#pragma unroll
+            for (int j = 0; j < 9; ++j) dw[e * 9 + j] = a[j];
+        }
+    }
+}
+
+// The dynamic-LDS limit is an attribute of the function PER DEVICE: set once on each device, and a failure fails the launch.
+inline int wg_set_lds(const void* fn, size_t bytes, std::atomic<unsigned long long>& done) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    if (!(done.load(std::memory_order_acquire) >> dev & 1ull)) {
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -1;
+        done.fetch_or(1ull << dev, std::memory_order_release);
+    }
+    return 0;
+}
+
 }  // namespace
 
 bool wino_fused_ok(int Cin, int Cout) { return Cin >= 8 && Cin % 8 == 0 && Cin <= 1024 && Cout >= 64 && Cout % 64 == 0; }
@@ -965,17 +1306,20 @@ int wino_fused_wgrad_run(const float* x, int pro, const float* s, const float* t
                          int Cin, int Cout, float* ws, hipStream_t st) {
     const WgGeom g = wg_geom(B, H, W, Cin, Cout);
     const int grid = g.nci * g.nco * g.S;
-    const size_t lds = (size_t)4 * FBUF * sizeof(float);
+    const bool rows = wg_rows_ok(Cin, Cout);
+    const size_t lds = (size_t)4 * (rows ? RBUF : FBUF) * sizeof(float);
 #define WG_CASE(P_)                                                                                                          \
     {                                                                                                                        \
-        static bool attr_set = false;                                                                                        \
-        if (!attr_set) {                                                                                                     \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_fused_wgrad_kernel<P_>),                           \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-            attr_set = true;                                                                                                 \
+        static std::atomic<unsigned long long> set_full{0}, set_rows{0};                                                     \
+        if (rows) {                                                                                                          \
+            if (wg_set_lds(reinterpret_cast<const void*>(&wino_fused_wgrad_rows_kernel<P_>), lds, set_rows) != 0) return -1; \
+            hipLaunchKernelGGL((wino_fused_wgrad_rows_kernel<P_>), dim3(grid), dim3(512), lds, st, x, s, t, dy, ws, B, H, W, Cin,   \
+                               Cout, g.th, g.tw, g.nci / 2, g.nco / 2, g.S, g.cps);                                          \
+        } else {                                                                                                             \
+            if (wg_set_lds(reinterpret_cast<const void*>(&wino_fused_wgrad_kernel<P_>), lds, set_full) != 0) return -1;      \
+            hipLaunchKernelGGL((wino_fused_wgrad_kernel<P_>), dim3(grid), dim3(512), lds, st, x, s, t, dy, ws, B, H, W, Cin, Cout,  \
+                               g.th, g.tw, g.nci, g.nco, g.S, g.cps);                                                        \
         }                                                                                                                    \
-        hipLaunchKernelGGL((wino_fused_wgrad_kernel<P_>), dim3(grid), dim3(512), lds, st, x, s, t, dy, ws, B, H, W, Cin, Cout, g.th,  \
-                           g.tw, g.nci, g.nco, g.S, g.cps);                                                                  \
     }
     switch (pro) {
         case 0: WG_CASE(0) break;
@@ -984,10 +1328,16 @@ int wino_fused_wgrad_run(const float* x, int pro, const float* s, const float* t
         default: WG_CASE(3) break;
     }
 #undef WG_CASE
+    // (one rule for the run split Q of both finish kernels: dw is the same sum in the same order whichever kernel formed the shares)
     const long n4 = (long)Cin * Cout * 9 / 4;
-    const auto blocks = [&](int e) { const long b = cdiv(n4, (long)e); return dim3((unsigned)(b > 4096 ? 4096 : b)); };
-    if (n4 >= 131072 || g.S < 8) hipLaunchKernelGGL(wino_fused_wgrad_finish_kernel<1>, blocks(256), dim3(256), 0, st, ws, 2 * g.S, n4, dw);
-    else if (n4 >= 32768 || g.S < 32) hipLaunchKernelGGL(wino_fused_wgrad_finish_kernel<4>, blocks(64), dim3(256), 0, st, ws, 2 * g.S, n4, dw);
-    else hipLaunchKernelGGL(wino_fused_wgrad_finish_kernel<16>, blocks(16), dim3(256), 0, st, ws, 2 * g.S, n4, dw);
+    const int Q = (n4 >= 131072 || g.S < 8) ? 1 : ((n4 >= 32768 || g.S < 32) ? 4 : 16);
+    const auto blocks = [&](long n, int e) { const long b = cdiv(n, (long)e); return dim3((unsigned)(b > 4096 ? 4096 : b)); };
+    if (rows) {                                       // (Q = 16 needs n4 < 32768: not with 128 x 128 channels or more)
+        const long n = (long)Cin * Cout;
+        if (Q == 1) hipLaunchKernelGGL(wino_fused_wgrad_rows_finish_kernel<1>, blocks(n, 256), dim3(256), 0, st, ws, 2 * g.S, n, dw);
+        else hipLaunchKernelGGL(wino_fused_wgrad_rows_finish_kernel<4>, blocks(n, 64), dim3(256), 0, st, ws, 2 * g.S, n, dw);
+    } else if (Q == 1) hipLaunchKernelGGL(wino_fused_wgrad_finish_kernel<1>, blocks(n4, 256), dim3(256), 0, st, ws, 2 * g.S, n4, dw);
+    else if (Q == 4) hipLaunchKernelGGL(wino_fused_wgrad_finish_kernel<4>, blocks(n4, 64), dim3(256), 0, st, ws, 2 * g.S, n4, dw);
+    else hipLaunchKernelGGL(wino_fused_wgrad_finish_kernel<16>, blocks(n4, 16), dim3(256), 0, st, ws, 2 * g.S, n4, dw);
     return 0;
 }
