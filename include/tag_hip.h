@@ -859,6 +859,37 @@ int tag_masked_frame_bce_backward(const float* prob, int ld_t, const float* labe
                                   const float* cls_mask, int B, int Tt, int C, const float* dloss, float* dprob, void* ws,
                                   void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sentence-level contrastive objectives (contrastive.hip): fp32 in, fp32 out, cross-thread sums in fp64 in a fixed order,
+ * no atomics (two runs give the same bits).  x (n,n) contiguous = the clip-versus-caption matrix "sim"; any n >= 1 (n = 1:
+ * loss 0, gradient 0).  One forward and one backward launch for n <= 128; above that the forward is two launches.
+ * ws: tag_contrastive_ws_bytes(n) bytes (n = B for MilNce), written by the forward and READ by the backward of the same
+ * input -- the backward is one elementwise pass with no reduction of its own.
+ *   tag_infonce_*   InfoNceLoss (losses.py:267): z = x / tau, loss = 1/2 [mean_i(LSE_j z_ij - z_ii) + mean_j(LSE_i z_ij - z_jj)];
+ *                   ws holds the row and column log-sum-exp.  The maximum is subtracted before every exponential
+ *   tag_triplet_*   mode 0 MaxTripletLoss (:285): (sum_i max_{j!=i} relu(m + x_ij - x_ii) + sum_j max_{i!=j} relu(m + x_ij -
+ *                   x_jj)) / n; mode 1 WeightedTripletLoss (:355): a row of x or x^T with q = max off-diagonal, p = diagonal
+ *                   and q + m > p adds clamp(0.2 p^2 - 0.7 p + 0.5, 0) + clamp(0.9 q^2 - 0.4 q + 0.03, 0), total / n.  ws holds
+ *                   the row and column argmax of the RAW entries (exact ties: the lowest index), -1 where inactive.
+ *                   mode 2 RandomTripletLoss (:319): s_index / a_index (n) device int32 drawn by the caller,
+ *                   (sum_i relu(m + x[i][s_i] - x[i][i]) + sum_i relu(m + x[i][a_i] - x[a_i][a_i])) / n, a draw of the
+ *                   diagonal (or outside [0,n)) adds nothing; the index pointers may be null in modes 0 and 1
+ *   tag_milnce_*    MilNceLoss (:46): clip_sim, label (B,N) contiguous, loss = mean_b[LSE_n(c / tau) - LSE_n(c l / tau)];
+ *                   dclip (B,N), label gets no gradient.  One wave per row, any N >= 1
+ * TAG_EINVAL (message in tag_last_error) for n < 1, tau <= 0 or a null pointer.
+ */
+size_t tag_contrastive_ws_bytes(int n);
+int tag_infonce_forward(const float* x, int n, double tau, float* loss, void* ws, void* stream);
+int tag_infonce_backward(const float* x, int n, double tau, const float* dloss, float* dx, const void* ws, void* stream);
+int tag_triplet_forward(const float* x, int n, int mode, double margin, const int* s_index, const int* a_index, float* loss,
+                        void* ws, void* stream);
+int tag_triplet_backward(const float* x, int n, int mode, double margin, const int* s_index, const int* a_index,
+                         const float* dloss, float* dx, const void* ws, void* stream);
+int tag_milnce_forward(const float* clip_sim, const float* label, int B, int N, double tau, float* loss, void* ws,
+                       void* stream);
+int tag_milnce_backward(const float* clip_sim, const float* label, int B, int N, double tau, const float* dloss, float* dclip,
+                        const void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1510,3 +1510,98 @@ def grad_sumsq(flat_grad):
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, gnorm_sq=None, max_norm=0.0, grad_scale=1.0):
     call("tag_adam_step", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, step, ptr(gnorm_sq),
          float(max_norm), float(grad_scale))
+
+
+# ------------------------------------------------------------------------------------------------ contrastive objectives
+TRIPLET_MODES = {"max": 0, "weighted": 1, "random": 2}
+
+
+def _square(sim, name="sim"):
+    x = _chk(sim, name)                                  # sim.T arrives strided: the kernels read rows
+    if x.ndim != 2 or x.shape[0] != x.shape[1] or x.shape[0] < 1:
+        raise RuntimeError(f"{name}: expected a square (n,n) matrix with n >= 1, got {tuple(x.shape)}")
+    return x, x.shape[0]
+
+
+def _contrastive_ws(n, like):
+    return _ws(query("tag_contrastive_ws_bytes", n), like)
+
+
+def _dloss(dloss):
+    return _chk(dloss.reshape(1), "grad")
+
+
+def infonce_forward(sim, tau):
+    """InfoNceLoss (losses.py:267-281) on sim (n,n) -> (0-dim loss, workspace holding the row / column log-sum-exp)."""
+    x, n = _square(sim)
+    loss, ws = _empty(1, like=x), _contrastive_ws(n, x)
+    call("tag_infonce_forward", ptr(x), n, float(tau), ptr(loss), ptr(ws))
+    return loss.view(()), ws
+
+
+def infonce_backward(sim, tau, dloss, ws=None):
+    """d loss / d sim.  ws: what infonce_forward returned for the SAME sim; None runs that forward again to refill it."""
+    x, n = _square(sim)
+    if ws is None:
+        ws = infonce_forward(x, tau)[1]
+    dx = torch.empty_like(x)
+    call("tag_infonce_backward", ptr(x), n, float(tau), ptr(_dloss(dloss)), ptr(dx), ptr(ws))
+    return dx
+
+
+def _triplet_indices(mode, n, s_index, a_index, like):
+    if mode != TRIPLET_MODES["random"]:
+        return None, None
+    out = []
+    for name, t in (("s_index", s_index), ("a_index", a_index)):
+        if t is None or not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (n,):
+            raise RuntimeError(f"{name}: the random triplet needs a device int32 vector of {n} draws, got "
+                               f"{None if t is None else (t.device, t.dtype, tuple(t.shape))}; there is no CPU fallback")
+        out.append(t.contiguous())
+    return out
+
+
+def triplet_forward(sim, mode, margin, s_index=None, a_index=None):
+    """Max / Weighted / RandomTripletLoss (losses.py:285-417; mode: TRIPLET_MODES value) on sim (n,n) -> (0-dim loss,
+    workspace holding the row / column argmax, -1 where inactive)."""
+    x, n = _square(sim)
+    if mode not in TRIPLET_MODES.values():
+        raise RuntimeError(f"triplet mode {mode!r}: expected one of {TRIPLET_MODES}")
+    s, a = _triplet_indices(mode, n, s_index, a_index, x)
+    loss, ws = _empty(1, like=x), _contrastive_ws(n, x)
+    call("tag_triplet_forward", ptr(x), n, int(mode), float(margin), ptr(s), ptr(a), ptr(loss), ptr(ws))
+    return loss.view(()), ws
+
+
+def triplet_backward(sim, mode, margin, s_index, a_index, dloss, ws=None):
+    x, n = _square(sim)
+    s, a = _triplet_indices(mode, n, s_index, a_index, x)
+    if ws is None:                                         # (the random mode keeps nothing: its workspace is never read)
+        ws = triplet_forward(x, mode, margin, s, a)[1] if mode != TRIPLET_MODES["random"] else _contrastive_ws(n, x)
+    dx = torch.empty_like(x)
+    call("tag_triplet_backward", ptr(x), n, int(mode), float(margin), ptr(s), ptr(a), ptr(_dloss(dloss)), ptr(dx), ptr(ws))
+    return dx
+
+
+def _clip_pair(clip_sim, label):
+    c, y = _chk(clip_sim, "clip_sim"), _chk(label, "label")
+    if c.ndim != 2 or c.shape != y.shape or c.numel() < 1:
+        raise RuntimeError(f"clip_sim {tuple(c.shape)} and label {tuple(y.shape)}: expected the same (B,N), B, N >= 1")
+    return c, y, c.shape[0], c.shape[1]
+
+
+def milnce_forward(clip_sim, label, tau):
+    """MilNceLoss (losses.py:46-56) on clip_sim / label (B,N) -> (0-dim loss, workspace holding both log-sum-exp per row)."""
+    c, y, B, N = _clip_pair(clip_sim, label)
+    loss, ws = _empty(1, like=c), _contrastive_ws(B, c)
+    call("tag_milnce_forward", ptr(c), ptr(y), B, N, float(tau), ptr(loss), ptr(ws))
+    return loss.view(()), ws
+
+
+def milnce_backward(clip_sim, label, tau, dloss, ws=None):
+    c, y, B, N = _clip_pair(clip_sim, label)
+    if ws is None:
+        ws = milnce_forward(c, y, tau)[1]
+    dc = torch.empty_like(c)
+    call("tag_milnce_backward", ptr(c), ptr(y), B, N, float(tau), ptr(_dloss(dloss)), ptr(dc), ptr(ws))
+    return dc

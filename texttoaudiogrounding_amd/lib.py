@@ -199,6 +199,13 @@ _SIGS = {
     "tag_masked_frame_bce_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tag_masked_frame_bce_forward": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, P, P]),
     "tag_masked_frame_bce_backward": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, P, P, P]),
+    "tag_contrastive_ws_bytes": (c_size_t, [c_int]),
+    "tag_infonce_forward": (c_int, [P, c_int, c_double, P, P, P]),
+    "tag_infonce_backward": (c_int, [P, c_int, c_double, P, P, P, P]),
+    "tag_triplet_forward": (c_int, [P, c_int, c_int, c_double, P, P, P, P, P]),
+    "tag_triplet_backward": (c_int, [P, c_int, c_int, c_double, P, P, P, P, P, P]),
+    "tag_milnce_forward": (c_int, [P, P, c_int, c_int, c_double, P, P, P]),
+    "tag_milnce_backward": (c_int, [P, P, c_int, c_int, c_double, P, P, P, P]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 """FrameBceLoss behind the reference interface (losses.py:11-35 in the reference)."""
 from typing import Dict
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -45,6 +46,85 @@ class MaxMarginRankingLoss(nn.Module):
 
     def forward(self, x):
         return ops.MaxMarginFunction.apply(x[self.sim_key], self.margin, self.lamda1, self.fix_norm)
+
+
+class InfoNceLoss(nn.Module):
+    """losses.py:267-281 in the reference: symmetric cross-entropy of sim / tau against the diagonal of the (B,B) matrix."""
+
+    def __init__(self, tau=0.07):
+        super().__init__()
+        self.tau = tau
+
+    def forward(self, output: Dict):
+        return torch.ops.tag.infonce(output["sim"], float(self.tau))
+
+
+class _TripletLoss(nn.Module):
+    mode = None
+
+    def __init__(self, margin=1.0):
+        super().__init__()
+        self.margin = margin
+
+    def forward(self, output: Dict):
+        return torch.ops.tag.triplet(output["sim"], ops.TRIPLET_MODES[self.mode], float(self.margin), None, None)
+
+
+class MaxTripletLoss(_TripletLoss):
+    """losses.py:285-315 in the reference: the hardest negative of every row and of every column of the (B,B) matrix."""
+    mode = "max"
+
+
+class WeightedTripletLoss(_TripletLoss):
+    """losses.py:355-417 in the reference (polyloss): for every row of sim and of sim^T whose hardest negative q violates the
+    margin against the positive p, clamp(0.2 p^2 - 0.7 p + 0.5, 0) + clamp(0.9 q^2 - 0.4 q + 0.03, 0); total / B."""
+    mode = "weighted"
+
+
+class RandomTripletLoss(_TripletLoss):
+    """losses.py:319-351 in the reference: one negative per row, drawn on the host exactly as the reference draws it
+    (np.random.randint(n, size=n) for s_index, then again for a_index: a seeded numpy stream gives the reference's draws)
+    and uploaded as int32."""
+    mode = "random"
+
+    def forward(self, output: Dict):
+        sim = output["sim"]
+        n = sim.size(0)
+        s_index = np.random.randint(n, size=n)
+        a_index = np.random.randint(n, size=n)
+        s_index, a_index = (torch_ops.stage_to_device(torch.from_numpy(v), sim.device, torch.int32) for v in (s_index, a_index))
+        return torch.ops.tag.triplet(sim, ops.TRIPLET_MODES[self.mode], float(self.margin), s_index, a_index)
+
+
+class MilNceLoss(nn.Module):
+    """losses.py:46-56 in the reference: mean_b[LSE_n(clip_sim / tau) - LSE_n(clip_sim * label / tau)] over (B,N)."""
+
+    def __init__(self, tau=1.0) -> None:
+        super().__init__()
+        self.tau = tau
+
+    def forward(self, output: Dict):
+        clip_sim = output["clip_sim"]
+        return torch.ops.tag.milnce(clip_sim, output["label"].to(clip_sim.device).float(), float(self.tau))
+
+
+class MultipleLossSum(nn.Module):
+    """losses.py:420-440 in the reference: sum_k weights[k] * names[k], where a name already present in the output dict is
+    taken as a ready value and any other is the sub-loss registered under it."""
+
+    def __init__(self, names, weights, **loss_fns):
+        super().__init__()
+        self.names = names
+        self.weights = weights
+        for name, loss_fn in loss_fns.items():
+            self.add_module(name, loss_fn)
+
+    def forward(self, output: Dict):
+        tot_loss = 0
+        for name, weight in zip(self.names, self.weights):
+            loss = output[name] if name in output else getattr(self, name)(output)
+            tot_loss = tot_loss + weight * loss
+        return tot_loss
 
 
 class ClipFrameBceLoss(nn.Module):

@@ -15,7 +15,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .losses import ClipMaskedFrameBceLoss, FrameBceLoss
+from .losses import ClipMaskedFrameBceLoss, FrameBceLoss, MaxMarginRankingLoss
 from .utils.train_util import init_obj_from_str
 
 
@@ -353,6 +353,29 @@ class ClassMappingRunner(StrongRunner):
                 output.update({"frame_sim": frame_sim, "strong_label": strong_label,
                                "length": torch.clamp(output["length"], 1, tt)})
         return output
+
+
+class WeakSentenceRunner(StrongRunner):
+    """Training-step driver of the sentence-level weak supervision (Runner.forward / train_epoch of python_scripts/training/
+    run_weak_sentence.py:76-124): AudioTextAlignByWord / AudioTextAlignByPhrase (or any model returning the (B,B) "sim") + a
+    loss that reads the output dict (MaxMarginRankingLoss, InfoNceLoss, the triplet losses, MultipleLossSum).  Flat parameters,
+    direct gradients, clip + Adam and the gradient buckets are StrongRunner's.
+
+    Under data parallelism the negatives of a clip are the other clips of ITS RANK's batch: nothing is gathered across ranks, as
+    in the reference run under DistributedDataParallel, and the ranks' gradients are averaged.  The reference's host-side
+    "zero the gradients when the loss is NaN" (:114-115) is not done: it costs a device-to-host sync every step."""
+
+    def __init__(self, model, loss_fn=None, **kwargs):
+        super().__init__(model, **kwargs)
+        self.loss_fn = loss_fn if loss_fn is not None else MaxMarginRankingLoss()
+
+    def forward(self, batch: Dict, training: bool = True):
+        for k, v in batch.items():
+            if isinstance(v, torch.Tensor):
+                batch[k] = v.to(self.device)             # dtypes kept (run_weak_sentence.py:78-80)
+        input_dict = {"specaug": False, "output_matrix": not training}
+        input_dict.update(batch)
+        return self.model(input_dict)
 
 
 def init_distributed(backend: Optional[str] = None):

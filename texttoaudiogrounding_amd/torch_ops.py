@@ -577,6 +577,136 @@ def _mbce_backward(ctx, dloss):
 register_autograd("tag::masked_frame_bce", _mbce_backward, setup_context=_mbce_setup)
 
 
+# ------------------------------------------------------------------------------------------------ contrastive objectives
+# ``tag::infonce`` / ``tag::triplet`` / ``tag::milnce`` return the 0-dim loss alone.  Their forward kernel also fills a small
+# workspace (row / column log-sum-exp, or argmax) that makes the backward ONE elementwise launch; it reaches ``setup_context``
+# through a one-slot hand-over, like the saved state of the encoder operators below, and the backward operator takes it as an
+# optional argument.  A backward that was traced (torch.compile / AOTAutograd: fake tensors, no hand-over) passes None and the
+# backward refills the workspace with one extra forward launch: the same result either way.
+_CONTRASTIVE_WS = [None]
+
+
+def _hand_over(loss, ws):
+    _CONTRASTIVE_WS[0] = (ws, loss.data_ptr())
+    return loss
+
+
+def _take_ws(ctx, output):
+    """The workspace of the forward that produced ``output`` -- not a leftover of an earlier forward whose setup_context never
+    ran (no input needed a gradient), and nothing at all for a traced (fake) output."""
+    slot, _CONTRASTIVE_WS[0] = _CONTRASTIVE_WS[0], None
+    ctx.ws = slot[0] if slot is not None and type(output) is Tensor and output.data_ptr() == slot[1] else None
+
+
+@custom_op("tag::infonce", mutates_args=())
+def infonce(sim: Tensor, tau: float) -> Tensor:
+    """InfoNceLoss (losses.py:267-281) on the (n,n) clip-versus-caption matrix: symmetric cross-entropy of sim / tau against
+    the diagonal -> 0-dim loss."""
+    return _hand_over(*ops.infonce_forward(sim, tau))
+
+
+@infonce.register_fake
+def _(sim, tau):
+    return sim.new_empty(())
+
+
+@custom_op("tag::infonce_backward", mutates_args=())
+def infonce_backward(sim: Tensor, tau: float, dloss: Tensor, ws: Optional[Tensor]) -> Tensor:
+    return ops.infonce_backward(sim, tau, dloss, ws)
+
+
+@infonce_backward.register_fake
+def _(sim, tau, dloss, ws):
+    return sim.new_empty(sim.shape)
+
+
+def _infonce_setup(ctx, inputs, output):
+    sim, ctx.tau = inputs
+    ctx.save_for_backward(sim)
+    _take_ws(ctx, output)
+
+
+def _infonce_backward(ctx, dloss):
+    (sim,) = ctx.saved_tensors
+    return torch.ops.tag.infonce_backward(sim, ctx.tau, dloss, ctx.ws), None
+
+
+register_autograd("tag::infonce", _infonce_backward, setup_context=_infonce_setup)
+
+
+@custom_op("tag::triplet", mutates_args=())
+def triplet(sim: Tensor, mode: int, margin: float, s_index: Optional[Tensor], a_index: Optional[Tensor]) -> Tensor:
+    """Max (mode 0) / Weighted (1) / Random (2) TripletLoss (losses.py:285-417) on the (n,n) matrix -> 0-dim loss.  s_index /
+    a_index: device int32 (n) draws of the random mode (ops.TRIPLET_MODES names the modes)."""
+    return _hand_over(*ops.triplet_forward(sim, mode, margin, s_index, a_index))
+
+
+@triplet.register_fake
+def _(sim, mode, margin, s_index, a_index):
+    return sim.new_empty(())
+
+
+@custom_op("tag::triplet_backward", mutates_args=())
+def triplet_backward(sim: Tensor, mode: int, margin: float, s_index: Optional[Tensor], a_index: Optional[Tensor], dloss: Tensor,
+                     ws: Optional[Tensor]) -> Tensor:
+    return ops.triplet_backward(sim, mode, margin, s_index, a_index, dloss, ws)
+
+
+@triplet_backward.register_fake
+def _(sim, mode, margin, s_index, a_index, dloss, ws):
+    return sim.new_empty(sim.shape)
+
+
+def _triplet_setup(ctx, inputs, output):
+    sim, ctx.mode, ctx.margin, s_index, a_index = inputs
+    ctx.save_for_backward(sim, s_index, a_index)
+    _take_ws(ctx, output)
+
+
+def _triplet_backward(ctx, dloss):
+    sim, s_index, a_index = ctx.saved_tensors
+    return torch.ops.tag.triplet_backward(sim, ctx.mode, ctx.margin, s_index, a_index, dloss, ctx.ws), None, None, None, None
+
+
+register_autograd("tag::triplet", _triplet_backward, setup_context=_triplet_setup)
+
+
+@custom_op("tag::milnce", mutates_args=())
+def milnce(clip_sim: Tensor, label: Tensor, tau: float) -> Tensor:
+    """MilNceLoss (losses.py:46-56) on clip_sim / label (B,N): mean_b[LSE_n(c / tau) - LSE_n(c * l / tau)] -> 0-dim loss;
+    label gets no gradient."""
+    return _hand_over(*ops.milnce_forward(clip_sim, label, tau))
+
+
+@milnce.register_fake
+def _(clip_sim, label, tau):
+    return clip_sim.new_empty(())
+
+
+@custom_op("tag::milnce_backward", mutates_args=())
+def milnce_backward(clip_sim: Tensor, label: Tensor, tau: float, dloss: Tensor, ws: Optional[Tensor]) -> Tensor:
+    return ops.milnce_backward(clip_sim, label, tau, dloss, ws)
+
+
+@milnce_backward.register_fake
+def _(clip_sim, label, tau, dloss, ws):
+    return clip_sim.new_empty(clip_sim.shape)
+
+
+def _milnce_setup(ctx, inputs, output):
+    clip_sim, label, ctx.tau = inputs
+    ctx.save_for_backward(clip_sim, label)
+    _take_ws(ctx, output)
+
+
+def _milnce_backward(ctx, dloss):
+    clip_sim, label = ctx.saved_tensors
+    return torch.ops.tag.milnce_backward(clip_sim, label, ctx.tau, dloss, ctx.ws), None, None
+
+
+register_autograd("tag::milnce", _milnce_backward, setup_context=_milnce_setup)
+
+
 # ------------------------------------------------------------------------------------------------ the fused audio encoders
 # ``tag::cnn8rnn_encoder`` / ``tag::crnn_encoder``: log-mel -> conv stack -> (fc1) -> BiGRU as ONE operator each (rows F1-F3,
 # A1-A4), what models/audio_encoder.py Cnn8Rnn.forward / CrnnEncoder.forward call -- the hot 97 % of the step goes through the
@@ -786,4 +916,5 @@ OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_r
             "gru_bidir", "gru_bidir_backward", "embed_mean", "embed_mean_backward", "frame_match", "frame_match_backward",
             "align_dot", "align_dot_backward", "frame_bce", "frame_bce_backward", "segments", "cnn8rnn_encoder", "crnn_encoder",
             "cross_cnn8rnn", "cross_cdur", "tagging_head", "tagging_head_backward", "masked_frame_bce",
-            "masked_frame_bce_backward", "text_gru", "text_gru_backward", "text_selfattn", "text_selfattn_backward"]
+            "masked_frame_bce_backward", "text_gru", "text_gru_backward", "text_selfattn", "text_selfattn_backward", "infonce",
+            "infonce_backward", "triplet", "triplet_backward", "milnce", "milnce_backward"]
