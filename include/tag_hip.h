@@ -519,6 +519,24 @@ int tag_align_dot_dscore(const float* out, const float* dout, float* ds, int sca
 int tag_l2norm_rows_forward(const float* x, float* y, long rows, int D, void* stream);
 int tag_l2norm_rows_backward(const float* x, const float* du, float* dx, long rows, int D, void* stream);
 
+/* align.ExpNegL2 models/align.py:34-64 (align.hip): out[a][i][t][j] = exp(-||an[a,t,:] - tn[i,j,:]||), (B,B,T,N) as
+ * tag_align_dot_forward.  an (B,T,D), tn (B,N,D) are the rows ALREADY normalised by tag_align_expnegl2_normalize
+ * (y = x / max(||x||, 1e-12): a quotient, where tag_l2norm_rows_forward multiplies by the reciprocal -- exact unit rows at D = 1
+ * and for rows that are multiples of each other).  The distance is the sum of squared differences (VALU tiles, no 2 - 2 cos).
+ * The backward recomputes the distances, leaves g = -dout * out / dist (0 where dist == 0) for every pair in ws
+ * (tag_align_expnegl2_ws_bytes: B*T*B*N floats, then the per-slice sums of a pass whose summed rows are cut over several
+ * workgroups, folded in slice order) and writes dan = sum_pairs g (an - tn), dtn = -sum_pairs g (an - tn) -- gradients with
+ * respect to the NORMALISED rows; the caller applies tag_align_expnegl2_normalize_backward (x the raw rows, u the unit rows:
+ * dx = (du - u (u . du)) / ||x||).  Fixed summation order, no atomics.  Any B, T, N, D >= 1 with B*T <= 2^31 - 1,
+ * B*N <= 65535 * 64 and D <= 65535 * 64; anything else is TAG_EINVAL before any launch, the limit named in tag_last_error. */
+int tag_align_expnegl2_normalize(const float* x, float* y, long rows, int D, void* stream);
+int tag_align_expnegl2_normalize_backward(const float* x, const float* u, const float* du, float* dx, long rows, int D,
+                                          void* stream);
+size_t tag_align_expnegl2_ws_bytes(int B, int T, int N, int D);
+int tag_align_expnegl2_forward(const float* an, const float* tn, float* out, int B, int T, int N, int D, void* stream);
+int tag_align_expnegl2_backward(const float* an, const float* tn, const float* dout, float* dan, float* dtn, int B, int T,
+                                int N, int D, void* ws, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * R1 + L1: FrameBceLoss losses.py:12-24 after the label alignment of run_strong.py:107-118.
  * sim (B, >=Tt) row stride ld_sim, label (B, >=Tt) row stride ld_label, length (B) int64 (unclamped:

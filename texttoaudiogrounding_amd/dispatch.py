@@ -656,6 +656,20 @@ def align_dot(audio, text, l2norm=False, scaled=False):
     return out
 
 
+def align_expnegl2(audio, text):
+    """align.ExpNegL2 forward (models/align.py:34-64): (B,T,D),(B,N,D) -> (B,B,T,N) = exp(-||an - tn||) over the F.normalize'd
+    rows (a quotient row pass), the distances as sums of squared differences in the tiled VALU kernel of align.hip.  Stays on
+    the device (the reference writes into a CPU torch.zeros)."""
+    audio, text = _chk(audio, "audio"), _chk(text, "text")
+    _check_pair_batch("align_expnegl2", audio, text)    # models/align.py:39-40 asserts a_bs == t_bs, a_dim == t_dim
+    B, T, D = audio.shape
+    N = text.shape[1]
+    an, tn = _unit_rows(audio, B * T, D), _unit_rows(text, B * N, D)
+    out = _empty(B, B, T, N, like=audio)
+    call("tag_align_expnegl2_forward", ptr(an), ptr(tn), ptr(out), B, T, N, D)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # bidirectional GRU (row A4): input projection GEMM + persistent recurrence, and its backward
 # ------------------------------------------------------------------------------------------------
@@ -1330,6 +1344,30 @@ def align_dot_backward(audio, text, out, dout, l2norm, scaled):
         call("tag_l2norm_rows_backward", ptr(t), ptr(dt), ptr(dt2), B * N, D)
         da, dt = da2, dt2
     return da.view(B, T, D), dt.view(B, N, D)
+
+
+def _unit_rows(x, rows, D):
+    """F.normalize as a quotient (align.hip): x / max(||x||, 1e-12)."""
+    y = torch.empty_like(x)
+    call("tag_align_expnegl2_normalize", ptr(x), ptr(y), rows, D)
+    return y
+
+
+def align_expnegl2_backward(audio, text, dout):
+    """Gradient of align.ExpNegL2: the distances recomputed from the re-normalised rows, g = -dout * out / dist per pair (0 at
+    dist == 0), the pair sums of g (an - tn) for both operands (no atomics), then the backward of F.normalize."""
+    a, t = _chk(audio, "audio"), _chk(text, "text")
+    _check_pair_batch("align_expnegl2_backward", a, t)
+    B, T, D = a.shape
+    N = t.shape[1]
+    an, tn = _unit_rows(a, B * T, D), _unit_rows(t, B * N, D)
+    ws = _ws(query("tag_align_expnegl2_ws_bytes", B, T, N, D), a)
+    dan, dtn = torch.empty_like(a), torch.empty_like(t)
+    call("tag_align_expnegl2_backward", ptr(an), ptr(tn), ptr(_chk(dout, "grad")), ptr(dan), ptr(dtn), B, T, N, D, ptr(ws))
+    da, dt = torch.empty_like(a), torch.empty_like(t)
+    call("tag_align_expnegl2_normalize_backward", ptr(a), ptr(an), ptr(dan), ptr(da), B * T, D)
+    call("tag_align_expnegl2_normalize_backward", ptr(t), ptr(tn), ptr(dtn), ptr(dt), B * N, D)
+    return da, dt
 
 
 # ------------------------------------------------------------------------------------------------

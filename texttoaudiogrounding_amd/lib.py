@@ -140,6 +140,11 @@ _SIGS = {
     "tag_align_dot_dscore": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "tag_l2norm_rows_forward": (c_int, [P, P, c_long, c_int, P]),
     "tag_l2norm_rows_backward": (c_int, [P, P, P, c_long, c_int, P]),
+    "tag_align_expnegl2_normalize": (c_int, [P, P, c_long, c_int, P]),
+    "tag_align_expnegl2_normalize_backward": (c_int, [P, P, P, P, c_long, c_int, P]),
+    "tag_align_expnegl2_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "tag_align_expnegl2_forward": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    "tag_align_expnegl2_backward": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "tag_roberta_embed_ln": (c_int, [P, P, P, P, P, P, c_float, P, c_int, c_int, c_int, c_int, P]),
     "tag_add_layernorm": (c_int, [P, P, P, P, c_float, P, c_long, c_int, P]),
     "tag_mha_small": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),

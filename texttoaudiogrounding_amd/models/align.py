@@ -1,4 +1,4 @@
-"""Cross-batch frame x text similarity (mirror of models/align.py:7-31 in the reference)."""
+"""Cross-batch frame x text similarity (mirror of models/align.py:7-64 in the reference)."""
 import torch
 import torch.nn as nn
 
@@ -17,3 +17,15 @@ class DotProduct(nn.Module):
         assert a_bs == t_bs
         assert a_dim == t_dim
         return torch.ops.tag.align_dot(audio, text, bool(self.l2norm), bool(self.scaled))
+
+
+class ExpNegL2(nn.Module):
+    """exp(-||normalize(audio) - normalize(text)||) for every (clip, frame) x (clip, phrase) pair, (B,B,T,N).  The result stays on
+    the device of its inputs; the reference writes it into a CPU ``torch.zeros``."""
+
+    def forward(self, audio: torch.Tensor, text: torch.Tensor):
+        a_bs, _, a_dim = audio.size()
+        t_bs, _, t_dim = text.size()
+        assert a_bs == t_bs
+        assert a_dim == t_dim
+        return torch.ops.tag.align_expnegl2(audio, text)

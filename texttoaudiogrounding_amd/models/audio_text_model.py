@@ -1,6 +1,7 @@
 """Model composition (mirror of BiEncoder, models/audio_text_model.py:16-98 in the reference) and the early-fusion grounding
 models CrossCnn8_Rnn (models/audio_text_model.py:571-840) and CrossCDur (models/audio_text_model.py:461-568), and the
-class-mapping baseline AudioTagging (models/audio_text_model.py:405-458)."""
+class-mapping baseline AudioTagging (models/audio_text_model.py:405-458); the weakly supervised MultiTextBiEncoder (:101-229) and
+MultiTextBiEncoderWithAlign (:232-402)."""
 import sys
 from typing import Optional
 
@@ -111,25 +112,27 @@ class MultiTextBiEncoder(BiEncoder):
         frame_sim = sim.view(B, N, -1).transpose(1, 2)                                       # (B, T', N)
         return {"frame_sim": frame_sim, "clip_sim": clip_sim, "length": length}
 
-    def _forward_general(self, input_dict):
-        """The reference's own data flow (models/audio_text_model.py:148-203): the audio embedding repeated for the N phrases
-        of its clip, (B*N)-row cross-encoder and head.  Taken with a cross-encoder or a head other than the grouped
-        DotProduct; ``safe_size`` chunking is unnecessary (the heads are row kernels, nothing is materialised per chunk)."""
+    def _encode(self, input_dict):
+        """One audio pass and one text pass (models/audio_text_model.py:148-162): the audio embedding behind ``audio_proj`` and the
+        text encoder's output over the B*N flattened phrases -- shared by the phrase-level head and, in
+        MultiTextBiEncoderWithAlign, the sentence-level one."""
         audio_output = self.audio_encoder(input_dict)
         audio_emb = audio_output["embedding"]
         if hasattr(self, "audio_proj"):
             audio_emb = ops.LinearFunction.apply(audio_emb, self.audio_proj.weight, self.audio_proj.bias)
-        B = audio_emb.size(0)
-        N = input_dict[self.text_forward_keys[0]].shape[1]
         text_forward_dict = {}
         for key in self.text_forward_keys:
             x = torch.as_tensor(input_dict[key])
             text_forward_dict[key] = x.reshape(x.shape[0] * x.shape[1], *x.shape[2:])
         text_emb = self.text_encoder(text_forward_dict)
-        length = audio_output["length"]
+        return audio_output, audio_emb, text_forward_dict, text_emb
+
+    def _phrase_general(self, audio_emb, length, text_len, text_emb, B, N):
+        """The reference's own data flow (models/audio_text_model.py:164-203): the audio embedding repeated for the N phrases
+        of its clip, (B*N)-row cross-encoder and head.  Taken with a cross-encoder or a head other than the grouped
+        DotProduct; ``safe_size`` chunking is unnecessary (the heads are row kernels, nothing is materialised per chunk)."""
         forward_dict = {"audio_emb": ops.GroupExpandFunction.apply(audio_emb, N), "text_emb": text_emb,
-                        "audio_len": torch.as_tensor(length).repeat_interleave(N),
-                        "text_len": text_forward_dict["text_len"]}
+                        "audio_len": torch.as_tensor(length).repeat_interleave(N), "text_len": text_len}
         if self.cross_encoder is not None:
             forward_dict.update(self.cross_encoder(forward_dict))
         if hasattr(self, "text_proj"):
@@ -140,27 +143,82 @@ class MultiTextBiEncoder(BiEncoder):
         sim = self.match_fn(forward_dict)                                                     # (B*N, T')
         return self._pool(sim.contiguous(), B, N, length)
 
-    def forward(self, input_dict):
+    def _phrase_level(self, audio_output, audio_emb, text_forward_dict, text_emb, general=False):
+        """frame_sim (B,T',N) and clip_sim (B,N).  ``text_emb`` is left as the text encoder returned it: the general path works
+        on a shallow copy of the dict (the reference clones the tensors, :288), so a projection replaces entries of the copy."""
         from .match import DotProduct
-        if (self.cross_encoder is not None or not isinstance(self.match_fn, DotProduct) or self.match_fn.l2norm
-                or self.match_fn.text_level != "seq"):
-            return self._forward_general(input_dict)
-        audio_output = self.audio_encoder(input_dict)
-        audio_emb = audio_output["embedding"]
-        if hasattr(self, "audio_proj"):
-            audio_emb = ops.LinearFunction.apply(audio_emb, self.audio_proj.weight, self.audio_proj.bias)
         B = audio_emb.size(0)
-        N = input_dict[self.text_forward_keys[0]].shape[1]
-        text_forward_dict = {}
-        for key in self.text_forward_keys:
-            x = torch.as_tensor(input_dict[key])
-            text_forward_dict[key] = x.reshape(x.shape[0] * x.shape[1], *x.shape[2:])
-        text_emb = self.text_encoder(text_forward_dict)
+        N = text_forward_dict[self.text_forward_keys[0]].shape[0] // B
+        length = audio_output["length"]
+        if (general or self.cross_encoder is not None or not isinstance(self.match_fn, DotProduct) or self.match_fn.l2norm
+                or self.match_fn.text_level != "seq"):
+            return self._phrase_general(audio_emb, length, text_forward_dict["text_len"], dict(text_emb), B, N)
         seq = text_emb["seq_emb"]
         if hasattr(self, "text_proj"):
             seq = ops.LinearFunction.apply(seq, self.text_proj.weight, self.text_proj.bias)
         sim = ops.MatchGroupFunction.apply(audio_emb, seq, N, self.match_fn.scale)            # (B*N, T')
-        return self._pool(sim, B, N, audio_output["length"])
+        return self._pool(sim, B, N, length)
+
+    def _forward_general(self, input_dict):
+        return self._phrase_level(*self._encode(input_dict), general=True)
+
+    def forward(self, input_dict):
+        return self._phrase_level(*self._encode(input_dict))
+
+
+class MultiTextBiEncoderWithAlign(MultiTextBiEncoder):
+    """MultiTextBiEncoder plus a sentence-level score (mirror of models/audio_text_model.py:232-402): from ONE audio pass and ONE
+    text pass, the phrase-level frame_sim / clip_sim of the parent and ``sentence_sim`` (B,B) = sentence_pooling(align_fn(audio_emb,
+    seq_emb of every clip's positive phrases)), for MultipleLossSum over a clip-level and a sentence-level objective.
+
+    The positives of clip i are its first ``label[i].sum()`` phrases.  The reference gathers and pads them to the longest count;
+    here align_fn sees all N phrases of every clip and the pooling masks the columns at and beyond ``text_len = label.sum(1)``
+    (every sim_pooling reducer does, in both directions) -- the same sentence_sim with no gather, and no device-to-host copy of
+    the counts.  With ``output_matrix`` (evaluation / inspection) the operand is cut to the reference's max(count) columns and
+    the phrases beyond a clip's count are zeroed first, so ``sim_matrix`` is the reference's, padded columns included; that path
+    does read the counts back.  As in the reference, align_fn takes the PROJECTED audio embedding and the UNPROJECTED seq_emb, so
+    with ``add_proj`` and unequal sizes its assert fails, and the sentence branch never sees the cross-encoder.
+
+    A clip without a positive phrase divides by zero in the reference: a host-resident ``label`` with such a row raises
+    ValueError before anything is launched; a device-resident one is not read back -- its row of sentence_sim is then NaN / inf
+    for the mean reducers, as in the reference."""
+
+    def __init__(self, audio_encoder, text_encoder, match_fn, align_fn, sentence_pooling, shared_dim, text_forward_keys,
+                 cross_encoder=None, phrase_pooling="linear_softmax", add_proj=False, upsample=False,
+                 freeze_audio_encoder=False, freeze_text_encoder=False, safe_size=None):
+        super().__init__(audio_encoder, text_encoder, match_fn, shared_dim, text_forward_keys, cross_encoder, phrase_pooling,
+                         add_proj, upsample, freeze_audio_encoder, freeze_text_encoder, safe_size)
+        self.align_fn = align_fn
+        self.sentence_pooling = sentence_pooling
+
+    def forward(self, input_dict):
+        sentence = self.training or "label" in input_dict
+        if sentence:
+            label = torch.as_tensor(input_dict["label"])
+            if not label.is_cuda and bool((label.sum(1) < 1).any()):
+                raise ValueError("MultiTextBiEncoderWithAlign: every clip needs at least one positive phrase (a row of `label` "
+                                 "sums to 0; the sentence-level mean over its phrases would divide by zero)")
+        audio_output, audio_emb, text_forward_dict, text_emb = self._encode(input_dict)
+        output = self._phrase_level(audio_output, audio_emb, text_forward_dict, text_emb)
+        if not sentence:
+            return output
+        B = audio_emb.size(0)
+        seq_emb = text_emb["seq_emb"]
+        seq_emb = seq_emb.reshape(B, seq_emb.shape[0] // B, *seq_emb.shape[1:])               # (B, N, D), unprojected (:366-369)
+        phrases_num = label.sum(1).long()
+        output_matrix = input_dict.get("output_matrix", False)
+        if output_matrix:
+            # the matrix as the reference returns it: max(count) columns, the phrases beyond a clip's count as ZERO rows (what
+            # pad_sequence leaves there); reads the counts back.  sentence_sim does not depend on those columns
+            width = int(phrases_num.max())
+            keep = torch.arange(width, device=seq_emb.device)[None, :] < phrases_num.to(seq_emb.device)[:, None]
+            seq_emb = (seq_emb[:, :width] * keep[..., None].to(seq_emb.dtype)).contiguous()
+        sim_matrix = self.align_fn(audio_emb, seq_emb)
+        output["sentence_sim"] = self.sentence_pooling({"sim": sim_matrix, "audio_len": audio_output["length"],
+                                                        "text_len": phrases_num})
+        if output_matrix:
+            output["sim_matrix"] = sim_matrix
+        return output
 
 
 class AudioTextAlignByWord(nn.Module):

@@ -15,14 +15,14 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .losses import ClipMaskedFrameBceLoss, FrameBceLoss, MaxMarginRankingLoss
+from .losses import ClipBceLoss, ClipMaskedFrameBceLoss, FrameBceLoss, MaxMarginRankingLoss
 from .utils.train_util import init_obj_from_str
 
 
 def build_model(model_cfg: Dict):
     """get_model of run_strong.py:71-89: instantiate sub-modules first, then the composition."""
     kwargs = {}
-    for k in ("audio_encoder", "text_encoder", "match_fn"):
+    for k in ("audio_encoder", "text_encoder", "match_fn", "align_fn", "sentence_pooling", "cross_encoder"):
         if k in model_cfg:
             kwargs[k] = init_obj_from_str(model_cfg[k])
     return init_obj_from_str({"type": model_cfg["type"], "args": model_cfg.get("args", {})}, **kwargs)
@@ -376,6 +376,59 @@ class WeakSentenceRunner(StrongRunner):
         input_dict = {"specaug": False, "output_matrix": not training}
         input_dict.update(batch)
         return self.model(input_dict)
+
+
+class WeakPhraseRunner(StrongRunner):
+    """Training-step driver of the phrase-level weak supervision (Runner.forward / train_epoch of python_scripts/training/
+    run_weak_phrase.py:39-104): MultiTextBiEncoder / MultiTextBiEncoderWithAlign + a loss that reads the output dict (ClipBceLoss,
+    MilNceLoss, ClipFrameBceLoss, MultipleLossSum).  Flat parameters, direct gradients, clip + Adam and the gradient buckets are
+    StrongRunner's.  ``text`` is staged as int64, every other tensor as fp32 (so ``label`` is on the device before the model sums
+    it); at evaluation every ``model.text_forward_keys`` entry gets the phrase axis (one phrase per clip).  The reference's
+    host-side "zero the gradients when the loss is NaN" (:87-88) is not done: it costs a device-to-host sync every step."""
+
+    def __init__(self, model, loss_fn=None, **kwargs):
+        super().__init__(model, **kwargs)
+        self.loss_fn = loss_fn if loss_fn is not None else ClipBceLoss()
+
+    def _stage(self, batch: Dict):
+        for k, v in batch.items():
+            if isinstance(v, torch.Tensor):
+                batch[k] = v.long().to(self.device) if k == "text" else v.float().to(self.device)
+
+    def forward(self, batch: Dict, training: bool = True):
+        self._stage(batch)
+        if not training:
+            for key in self.model.text_forward_keys:
+                batch[key] = batch[key].unsqueeze(1)
+        input_dict = {"specaug": False}
+        input_dict.update(batch)
+        output = self.model(input_dict)
+        if training:
+            output.update(batch)
+        return output
+
+
+class WeakPhraseSelfSupervisionRunner(WeakPhraseRunner):
+    """run_weak_phrase_self_supervision.py:24-51: a ``teacher`` model, kept in eval() and run under no_grad on the SAME input_dict,
+    raises the weak labels -- output["label"] = max(batch["label"], teacher clip_sim) elementwise on the device, and
+    output["frame_label"] = teacher frame_sim.  The teacher's parameters are outside FlatParams: no gradient, no Adam step."""
+
+    def __init__(self, model, teacher, loss_fn=None, **kwargs):
+        super().__init__(model, loss_fn=loss_fn, **kwargs)
+        self.teacher = teacher.to(self.device).eval()
+        for p in self.teacher.parameters():
+            p.requires_grad_(False)
+
+    def forward(self, batch: Dict, training: bool = True):
+        output = super().forward(batch, training)
+        input_dict = {"specaug": False}
+        input_dict.update(batch)
+        self.teacher.eval()
+        with torch.no_grad():
+            teacher_output = self.teacher(input_dict)
+            output["label"] = torch.maximum(batch["label"], teacher_output["clip_sim"])
+            output["frame_label"] = teacher_output["frame_sim"]
+        return output
 
 
 def init_distributed(backend: Optional[str] = None):

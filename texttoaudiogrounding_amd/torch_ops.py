@@ -459,6 +459,42 @@ def _align_backward(ctx, dout):
 register_autograd("tag::align_dot", _align_backward, setup_context=_align_setup)
 
 
+# ------------------------------------------------------------------------------------------------ align.ExpNegL2
+@custom_op("tag::align_expnegl2", mutates_args=())
+def align_expnegl2(audio: Tensor, text: Tensor) -> Tensor:
+    """align.ExpNegL2: (B,T,D),(B,N,D) -> (B,B,T,N) = exp(-||normalize(audio) - normalize(text)||), tiled VALU kernel."""
+    return ops.align_expnegl2(audio, text)
+
+
+@align_expnegl2.register_fake
+def _(audio, text):
+    B, T, _ = audio.shape
+    return audio.new_empty(B, B, T, text.shape[1])
+
+
+@custom_op("tag::align_expnegl2_backward", mutates_args=())
+def align_expnegl2_backward(audio: Tensor, text: Tensor, dout: Tensor) -> Tuple[Tensor, Tensor]:
+    return ops.align_expnegl2_backward(audio, text, dout)
+
+
+@align_expnegl2_backward.register_fake
+def _(audio, text, dout):
+    return torch.empty_like(audio), torch.empty_like(text)
+
+
+def _expnegl2_setup(ctx, inputs, output):
+    audio, text = inputs
+    ctx.save_for_backward(audio, text)
+
+
+def _expnegl2_backward(ctx, dout):
+    audio, text = ctx.saved_tensors
+    return torch.ops.tag.align_expnegl2_backward(audio, text, dout)
+
+
+register_autograd("tag::align_expnegl2", _expnegl2_backward, setup_context=_expnegl2_setup)
+
+
 # ------------------------------------------------------------------------------------------------ L1 frame BCE
 @custom_op("tag::frame_bce", mutates_args=())
 def frame_bce(frame_sim: Tensor, label: Tensor, length: Tensor, Tt: int) -> Tensor:
@@ -914,7 +950,8 @@ def _(frame_sim, thresholds, window_size, n_connect):
 
 OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_relu_pool", "conv3x3_bn_relu_pool_backward",
             "gru_bidir", "gru_bidir_backward", "embed_mean", "embed_mean_backward", "frame_match", "frame_match_backward",
-            "align_dot", "align_dot_backward", "frame_bce", "frame_bce_backward", "segments", "cnn8rnn_encoder", "crnn_encoder",
+            "align_dot", "align_dot_backward", "align_expnegl2", "align_expnegl2_backward", "frame_bce", "frame_bce_backward",
+            "segments", "cnn8rnn_encoder", "crnn_encoder",
             "cross_cnn8rnn", "cross_cdur", "tagging_head", "tagging_head_backward", "masked_frame_bce",
             "masked_frame_bce_backward", "text_gru", "text_gru_backward", "text_selfattn", "text_selfattn_backward", "infonce",
             "infonce_backward", "triplet", "triplet_backward", "milnce", "milnce_backward"]
