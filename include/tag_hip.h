@@ -629,6 +629,39 @@ int tag_embed_tokens_backward(const float* dtok, const long* text, float* dtable
                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * AudioTextCrossAlignByPhrase (models/audio_text_model.py:979-1073): the cross-encoder above and the token-level DotProduct
+ * over ALL pairs (clip i, phrase p) of a batch.  a (B,T,D) audio with alen (B); w (P,L,D) tokens with wlen (P); pnum (B) phrases
+ * per clip, a HOST array with entries >= 0 and sum P (clip j owns phrases off[j] .. off[j] + pnum[j] - 1, off = its exclusive
+ * prefix sum); N >= max(pnum).  The caller projects with tag_gemm first: aq = a Wq^T, gu = sigmoid(a Wu^T + b_u) (B,T,D),
+ * ak = w Wk^T + b_h, ws_tok = w Ws^T (P,L,D) -- fc_s(attn @ tok) = attn @ (tok Ws^T) + b_s because the weights sum to 1.  Per
+ * row (i,p,t): the scores, mask fills, softmax over all L slots and the fully-filled-row convention of tag_addattn_*,
+ * c = alpha @ w[p], z = alpha @ ws_tok[p] + b_s, u = a[i,t] * sigmoid(z), s = c * gu[i,t], then the arithmetic and clamp
+ * gradient of tag_rowdot_sigmoid_*.  Nothing of B*P*T*D elements exists; every sum over pairs has one fixed order (no atomics),
+ * so two calls agree bit for bit.
+ * Limits (TAG_EINVAL with a tag_last_error message otherwise): L <= 32; D a multiple of 32, D <= 1024; pnum as above.
+ * ------------------------------------------------------------------------------------------- */
+/* bytes of everything a forward keeps for its backward (aq, gu, ak, ws_tok, alpha, dyfac), the forward's simp and the backward's
+ * workspace; 0 with a tag_last_error message for a shape that is not served */
+size_t tag_crosspairs_ws_bytes(int B, int T, int P, int L, int D);
+size_t tag_crosspairs_backward_ws_bytes(int B, int T, int P, int L, int D);
+/* sim (B,B,N,T) with sim[i,j,n,t] = the score of clip i, frame t against phrase n of clip j, 0 where n >= pnum[j];
+ * alpha (B,P,T,L) and dyfac (B,P,T) are kept for the backward; simp (B,P,T) is scratch */
+int tag_crosspairs_forward(const float* a, const float* aq, const float* gu, const float* w, const float* ak,
+                           const float* ws_tok, const float* v, const float* b_s, const long* alen, const long* wlen,
+                           const long* pnum_host, float* sim, float* alpha, float* dyfac, float* simp, int B, int T, int P,
+                           int L, int D, int N, int scale, void* stream);
+/* from dsim (B,B,N,T): daq, da (the term through u only), dgu (B,T,D); dak, dw (the term through c only), dws (P,L,D);
+ * dv, db_s (D).  Entries of dsim with n >= pnum[j] are not read.  The frame side and the token side are separate kernels that
+ * each recompute the tanh; dscore (B,P,T,L) is formed once, in ws, between them. */
+int tag_crosspairs_backward(const float* a, const float* aq, const float* gu, const float* w, const float* ak,
+                            const float* ws_tok, const float* v, const float* b_s, const long* alen, const long* wlen,
+                            const long* pnum_host, const float* alpha, const float* dyfac, const float* dsim, float* daq,
+                            float* da, float* dgu, float* dak, float* dw, float* dws, float* dv, float* db_s, int B, int T,
+                            int P, int L, int D, int N, void* ws, void* stream);
+/* g = sigmoid(z): dz = dg * g * (1 - g) (dgu of tag_crosspairs_backward -> the fc_u pre-activation); dz may be dg */
+int tag_sigmoid_backward(const float* dg, const float* g, float* dz, long n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Weak supervision (next row of the scope table): MultiTextBiEncoder (models/audio_text_model.py:101-229) -- N phrases
  * per clip scored against the SAME audio embedding (no (B*N,T,D) expansion), pooled by linear_softmax_with_lens
  * (models/utils.py:75-76); ClipBceLoss (losses.py:38-43) is tag_frame_bce_* over the (B,N) clip matrix.

@@ -1034,6 +1034,90 @@ class CrossGatingFunction(TagFunction):
         return (da, dcx, *g)
 
 
+def cross_pairs_served(L, D):
+    """Whether csrc/cross_pairs.hip serves L tokens per phrase at width D (a host-side question: no launch, no device)."""
+    return query("tag_crosspairs_ws_bytes", 1, 1, 1, int(L), int(D)) > 0
+
+
+class CrossPairsFunction(TagFunction):
+    """The tail of AudioTextCrossAlignByPhrase (models/audio_text_model.py:1033-1063 in the reference) as ONE node:
+    CrossAttentionGating + match.DotProduct(text_level="token") of every clip against every phrase of the batch.
+    a (B,T,D) with alen (B); w (P,L,D) with wlen (P); pnum (B) phrases per clip (host integers, sum P) ->
+    sim_matrix (B,B,T,N), N = max(pnum), zero where n >= pnum[j].  The reference expands each clip to (P,T,D) and runs the
+    cross-encoder on P*T rows, B times; here four GEMMs project the B*T frames and the P*L tokens once (fc_s is applied to the
+    tokens: the attention weights sum to 1) and csrc/cross_pairs.hip does the rest per (clip, phrase, frame) row.
+    params: h2attn.weight (D,2D), h2attn.bias, v, fc_u.weight, fc_u.bias, fc_s.weight, fc_s.bias."""
+
+    @staticmethod
+    def forward(ctx, a, alen, w, wlen, pnum, w_h, b_h, v, w_u, b_u, w_s, b_s, scale):
+        a_, t_ = _chk(a, "audio_emb"), _chk(w, "token_emb")
+        B, T, D = a_.shape
+        P, L = t_.shape[0], t_.shape[1]
+        params = [w_h, b_h, v, w_u, b_u, w_s, b_s]
+        ctx.sinks = _sinks(params)
+        ctx.params = params if cfg.DIRECT_GRADS else None
+        w_h, b_h, v, w_u, b_u, w_s, b_s = (_chk(x.detach(), "parameter") for x in params)
+        if (t_.shape[2] != D or w_h.shape != (D, 2 * D) or b_h.shape != (D,) or v.shape != (D,) or w_u.shape != (D, D)
+                or w_s.shape != (D, D) or b_u.shape != (D,) or b_s.shape != (D,)):
+            raise RuntimeError("CrossPairs: inconsistent dimensions")
+        pn = torch.as_tensor(pnum).detach().to("cpu", torch.int64).contiguous()
+        if pn.shape != (B,) or int(pn.sum()) != P or int(pn.min()) < 0:
+            raise RuntimeError(f"CrossPairs: {pn.tolist()} phrases per clip for {B} clips and {P} phrases")
+        N = int(pn.max())
+        dev = a_.device
+        al = torch.as_tensor(alen).long().to(dev).contiguous()
+        wl = torch.as_tensor(wlen).long().to(dev).contiguous()
+        if al.shape != (B,) or wl.shape != (P,):
+            raise RuntimeError("CrossPairs: one length per clip and per phrase is needed")
+        aq = gemm(a_, w_h, B * T, D, D, transB=True, ldb=2 * D)
+        ak = gemm(t_, w_h[:, D:], P * L, D, D, transB=True, ldb=2 * D, bias=b_h)
+        gu = gemm(a_, w_u, B * T, D, D, transB=True, bias=b_u, act=5)
+        ws = gemm(t_, w_s, P * L, D, D, transB=True)
+        sim = _empty(B, B, N, T, like=a_)
+        alpha, dyfac, simp = _empty(B, P, T, L, like=a_), _empty(B, P, T, like=a_), _empty(B, P, T, like=a_)
+        call("tag_crosspairs_forward", ptr(a_), ptr(aq), ptr(gu), ptr(t_), ptr(ak), ptr(ws), ptr(v), ptr(b_s), ptr(al), ptr(wl),
+             pn.data_ptr(), ptr(sim), ptr(alpha), ptr(dyfac), ptr(simp), B, T, P, L, D, N, int(bool(scale)))
+        ctx.save_for_backward(a_, t_, aq, ak, gu, ws, alpha, dyfac, al, wl, w_h, v, w_u, w_s, b_s)
+        ctx.pn, ctx.N = pn, N
+        return sim.transpose(2, 3)                       # (B,B,T,N), as align.py returns its matrices
+
+    @staticmethod
+    def backward(ctx, dsim):
+        a, t, aq, ak, gu, ws, alpha, dyfac, al, wl, w_h, v, w_u, w_s, b_s = ctx.saved_tensors
+        B, T, D = a.shape
+        P, L = t.shape[0], t.shape[1]
+        M, ML, N = B * T, P * L, ctx.N
+        dsim = _chk(dsim.transpose(2, 3), "grad")        # (B,B,N,T), contiguous
+        daq, da, dgu = torch.empty_like(a), torch.empty_like(a), torch.empty_like(a)
+        dak, dt, dws = torch.empty_like(t), torch.empty_like(t), torch.empty_like(t)
+        dv, db_s = _empty(D, like=a), _empty(D, like=a)
+        wsp = _ws(query("tag_crosspairs_backward_ws_bytes", B, T, P, L, D), a)
+        call("tag_crosspairs_backward", ptr(a), ptr(aq), ptr(gu), ptr(t), ptr(ak), ptr(ws), ptr(v), ptr(b_s), ptr(al), ptr(wl),
+             ctx.pn.data_ptr(), ptr(alpha), ptr(dyfac), ptr(dsim), ptr(daq), ptr(da), ptr(dgu), ptr(dak), ptr(dt), ptr(dws),
+             ptr(dv), ptr(db_s), B, T, P, L, D, N, ptr(wsp))
+        # h2attn = [Wq | Wk]: aq = a Wq^T, ak = t Wk^T + b_h
+        dw_h = _empty(D, 2 * D, like=a)
+        gemm(daq, a, D, D, M, transA=True, lda=D, out=dw_h, ldc=2 * D)
+        gemm(dak, t, D, D, ML, transA=True, lda=D, out=dw_h[:, D:], ldc=2 * D)
+        db_h = colsum(dak, ML, D)
+        gemm(daq, w_h, M, D, D, ldb=2 * D, out=da, accumulate=True)
+        gemm(dak, w_h[:, D:], ML, D, D, ldb=2 * D, out=dt, accumulate=True)
+        # gu = sigmoid(a Wu^T + b_u): dz_u = dgu * gu * (1 - gu), in place
+        dz_u = dgu
+        call("tag_sigmoid_backward", ptr(dgu), ptr(gu), ptr(dz_u), dgu.numel())
+        dw_u = gemm(dz_u, a, D, D, M, transA=True, lda=D)
+        db_u = colsum(dz_u, M, D)
+        gemm(dz_u, w_u, M, D, D, out=da, accumulate=True)
+        # ws = t Ws^T
+        dw_s = gemm(dws, t, D, D, ML, transA=True, lda=D)
+        gemm(dws, w_s, ML, D, D, out=dt, accumulate=True)
+        g = [dw_h, db_h, dv, dw_u, db_u, dw_s, db_s]
+        for k in range(7):
+            _deliver(g, ctx.sinks, k, g[k])
+        _ready(ctx.params)
+        return (da, None, dt, None, None, *g, None)
+
+
 class CrossAttentionHeadFunction(TagFunction):
     """match.CrossAttention (models/match.py:63-88): nn.MultiheadAttention(E, H, p, batch_first, kdim = vdim = kvdim) of every
     audio frame over the phrase tokens, ``audio + dropout(out)``, LayerNorm, Linear(E,1), sigmoid -> (B,T).

@@ -158,6 +158,11 @@ _SIGS = {
     "tag_rowpair_forward": (c_int, [P, P, P, c_long, c_int, c_int, c_int, c_int, P]),
     "tag_rowpair_backward": (c_int, [P, P, P, P, P, c_long, c_int, c_int, c_int, c_int, P]),
     "tag_embed_tokens_backward": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    "tag_crosspairs_ws_bytes": (c_size_t, [c_int] * 5),
+    "tag_crosspairs_backward_ws_bytes": (c_size_t, [c_int] * 5),
+    "tag_crosspairs_forward": (c_int, [P] * 15 + [c_int] * 7 + [P]),
+    "tag_crosspairs_backward": (c_int, [P] * 22 + [c_int] * 6 + [P, P]),
+    "tag_sigmoid_backward": (c_int, [P, P, P, c_long, P]),
     "tag_match_group_forward": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "tag_match_group_backward": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "tag_linear_softmax_pool_forward": (c_int, [P, P, P, c_long, c_int, c_int, P]),

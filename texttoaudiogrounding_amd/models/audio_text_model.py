@@ -1,7 +1,8 @@
 """Model composition (mirror of BiEncoder, models/audio_text_model.py:16-98 in the reference) and the early-fusion grounding
 models CrossCnn8_Rnn (models/audio_text_model.py:571-840) and CrossCDur (models/audio_text_model.py:461-568), and the
 class-mapping baseline AudioTagging (models/audio_text_model.py:405-458); the weakly supervised MultiTextBiEncoder (:101-229) and
-MultiTextBiEncoderWithAlign (:232-402)."""
+MultiTextBiEncoderWithAlign (:232-402); the sentence-level AudioTextAlignByWord / ByPhrase (:843-976) and AudioTextCrossAlignByPhrase
+(:979-1073)."""
 import sys
 from typing import Optional
 
@@ -290,6 +291,86 @@ class AudioTextAlignByPhrase(nn.Module):
         if input_dict.get("output_matrix", False):
             output["sim_matrix"] = sim_matrix
         return output
+
+
+class AudioTextCrossAlignByPhrase(nn.Module):
+    """Sentence-level weak alignment WITH a cross-encoder (mirror of models/audio_text_model.py:979-1073): every clip of the
+    batch is cross-encoded against every phrase of the batch, the token-level head scores each (clip, phrase, frame) and
+    sim_pooling reduces the (B,B,T',N) matrix to the (B,B) ``sim`` of MaxMarginRankingLoss / InfoNceLoss / the triplet losses.
+    Same constructor as the reference: ``add_proj`` is positional and creates nothing.
+
+    Two paths, chosen by ``self.fused`` (None = automatic, True = demand the fused one, False = the loop):
+
+    * fused -- ``cross_encoder`` is this package's CrossAttentionGating, ``match_fn`` is match.DotProduct(text_level="token",
+      l2norm=False) and csrc/cross_pairs.hip serves (L, D): ONE ops.CrossPairsFunction call; nothing of B*P*T*D elements exists.
+    * loop -- the reference's data flow with the existing modules: per clip, its audio expanded to the P phrases, the
+      cross-encoder, the head, the scatter into the zero matrix.  Any cross-encoder and any token-level head."""
+
+    def __init__(self, audio_encoder, text_encoder, match_fn, sim_pooling, shared_dim, add_proj, cross_encoder=None,
+                 freeze_audio_encoder=False, freeze_text_encoder=False):
+        super().__init__()
+        self.audio_encoder, self.text_encoder, self.match_fn = audio_encoder, text_encoder, match_fn
+        self.cross_encoder, self.sim_pooling = cross_encoder, sim_pooling
+        self.fused = None
+        if freeze_audio_encoder:
+            for p in self.audio_encoder.parameters():
+                p.requires_grad = False
+        if freeze_text_encoder:
+            for p in self.text_encoder.parameters():
+                p.requires_grad = False
+
+    def _fusable(self, L, D):
+        from .cross_encoder import CrossAttentionGating
+        from .match import DotProduct
+        ce, mf = self.cross_encoder, self.match_fn
+        return (type(ce) is CrossAttentionGating and type(mf) is DotProduct and mf.text_level == "token" and not mf.l2norm
+                and tuple(ce.attn.h2attn.weight.shape) == (D, 2 * D) and ops.cross_pairs_served(L, D))
+
+    def _loop(self, audio_emb, length, token_emb, text_len, phrases_num, T, N):
+        B, P = audio_emb.size(0), token_emb.size(0)
+        rows = []
+        for i in range(B):
+            c_o = self.cross_encoder({"audio_emb": ops.GroupExpandFunction.apply(audio_emb[i:i + 1].contiguous(), P),
+                                      "text_emb": {"token_emb": token_emb}, "audio_len": [int(length[i])] * P,
+                                      "text_len": text_len})
+            sim_i = self.match_fn(c_o)                                         # (P, T)
+            blocks = []
+            for s in torch.split(sim_i, phrases_num, dim=0):                   # clip j's (pnum[j], T) -> (T, N), zero-padded
+                blocks.append(torch.nn.functional.pad(s.transpose(0, 1), (0, N - s.shape[0])))
+            rows.append(torch.stack(blocks))
+        return torch.stack(rows)                                               # (B, B, T, N)
+
+    def forward(self, input_dict):
+        audio_output = self.audio_encoder(input_dict)
+        audio_emb = audio_output["embedding"]
+        text_key = input_dict["text_key"]
+        text_len = input_dict[f"{text_key}_len"]
+        token_emb = self.text_encoder({"text": input_dict[text_key], "text_len": text_len})["token_emb"]
+        phrases_num = [int(v) for v in input_dict[f"{text_key}_num"]]
+        length = audio_output["length"]
+        if not audio_emb.is_cuda or not token_emb.is_cuda:
+            raise RuntimeError(f"AudioTextCrossAlignByPhrase: expected embeddings on the MI355X (cuda) device, got "
+                               f"{audio_emb.device} / {token_emb.device}; the HIP path has no CPU fallback")
+        T, N = int(max(length)), max(phrases_num)
+        if audio_emb.size(1) != T:
+            raise RuntimeError(f"AudioTextCrossAlignByPhrase: the audio encoder returned {audio_emb.size(1)} frames but "
+                               f"max(length) = {T}; sim_matrix has max(length) frames and the two must agree")
+        L, D = token_emb.size(1), audio_emb.size(2)
+        fusable = self._fusable(L, D)
+        if self.fused and not fusable:
+            raise RuntimeError("AudioTextCrossAlignByPhrase: fused = True needs this package's CrossAttentionGating, "
+                               "match.DotProduct(text_level='token', l2norm=False) and a shape cross_pairs.hip serves "
+                               f"(L = {L}, D = {D})")
+        if fusable and self.fused is not False:
+            ce = self.cross_encoder
+            sim_matrix = ops.CrossPairsFunction.apply(audio_emb, length, token_emb, text_len, phrases_num,
+                                                      ce.attn.h2attn.weight, ce.attn.h2attn.bias, ce.attn.v,
+                                                      ce.gating.fc_u.weight, ce.gating.fc_u.bias, ce.gating.fc_s.weight,
+                                                      ce.gating.fc_s.bias, self.match_fn.scale)
+        else:
+            sim_matrix = self._loop(audio_emb, length, token_emb, text_len, phrases_num, T, N)
+        sim = self.sim_pooling({"sim": sim_matrix, "audio_len": length, "text_len": phrases_num})
+        return {"sim": sim, "sim_matrix": sim_matrix}
 
 
 class ConvTextBlock(nn.Module):

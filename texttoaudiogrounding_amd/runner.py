@@ -20,9 +20,10 @@ from .utils.train_util import init_obj_from_str
 
 
 def build_model(model_cfg: Dict):
-    """get_model of run_strong.py:71-89: instantiate sub-modules first, then the composition."""
+    """get_model of run_strong.py:71-89 (run_weak_sentence.py adds ``sim_pooling``): instantiate sub-modules first, then the
+    composition."""
     kwargs = {}
-    for k in ("audio_encoder", "text_encoder", "match_fn", "align_fn", "sentence_pooling", "cross_encoder"):
+    for k in ("audio_encoder", "text_encoder", "match_fn", "align_fn", "sentence_pooling", "sim_pooling", "cross_encoder"):
         if k in model_cfg:
             kwargs[k] = init_obj_from_str(model_cfg[k])
     return init_obj_from_str({"type": model_cfg["type"], "args": model_cfg.get("args", {})}, **kwargs)
