@@ -482,6 +482,41 @@ int tag_text_cls_pe_backward(const float* dx, float* dtok /* nullable */, float*
                              int E, float drop_p, uint64_t seed, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * T5: intra-attention of the text side: IntraAttention.forward, models/text_encoder.py:206-237, with its ConvGRUCell
+ * (:147-188).  Per layer: score = drop(x + pe) drop(x + pe)^T (two independent masks, UNSCALED), cells with query or key
+ * >= text_len FILLED WITH 1e-10 (not -inf: they take part in the softmax), attn = softmax over all L cells,
+ * message = attn @ x (x, not x + pe); then the cell on [message ; x].  The three gate products are tag_gemm calls.
+ * Rows never interact: one workgroup owns a phrase, its L x L scores live in LDS, every output element is a complete
+ * fixed-order sum; no partials, no workspace, no atomics (two runs are bit-identical).  Exact fp32 on the VALU.
+ * R >= 1, 1 <= L <= 64, E even, 2 <= E <= 1024; anything else is TAG_EINVAL.  text_len (R) int64, clamped to [0, L].
+ *   x (R,L,E), pe (>= L rows of E), message (R,L,E), attn (R,L,L) nullable: the softmax output, dead cells included
+ *   drop_p / seed_a / seed_b: the two dropouts behind the positions, tag_keep(seed, flat index of (R,L,E)) scaled by
+ *   1 / (1 - p) -- what tag_dropout_mask materialises; drop_p = 0 is the shared a == b path of eval mode
+ * backward: dmessage (R,L,E), x, pe, attn, text_len -> dx (R,L,E) [+= when accumulate]: the attn-weighted path into x, the
+ *   softmax backward, zero through dead cells, both dropout replays onto x.  pe is a buffer and has no gradient.
+ * ConvGRUCell element-wise kernels (all tensors (M,E) = (R*L,E)):
+ *   gates_forward:   u = sigmoid(u), r = sigmoid(r) in place, xr = x * r
+ *   update_forward:  o = tanh(o) in place, xnew = x (1 - u) + o u; seq_mean (R,E) nullable: sum of xnew over
+ *                    t < min(text_len, L) divided by text_len (0/0 for an empty phrase, like tag_embed_mean_forward)
+ *   update_backward: g = dnew (nullable) + [t < text_len] dseq (nullable; at least one) / text_len ->
+ *                    do_pre = g u (1 - o^2), du_pre = g (o - x) u (1 - u), dx = g (1 - u)
+ *   gates_backward:  dxr (= do_pre W_o[:, E:]) -> dr_pre = dxr x r (1 - r), dx += dxr r
+ * ------------------------------------------------------------------------------------------- */
+int tag_text_intra_forward(const float* x, const float* pe, const int64_t* text_len, float* message, float* attn /* nullable */,
+                           int R, int L, int E, float drop_p, uint64_t seed_a, uint64_t seed_b, void* stream);
+int tag_text_intra_backward(const float* dmessage, const float* x, const float* pe, const float* attn, const int64_t* text_len,
+                            float* dx, int accumulate, int R, int L, int E, float drop_p, uint64_t seed_a, uint64_t seed_b,
+                            void* stream);
+int tag_convgru_gates_forward(float* u, float* r, const float* x, float* xr, long M, int E, void* stream);
+int tag_convgru_update_forward(float* o, const float* u, const float* x, float* xnew, const int64_t* text_len /* nullable */,
+                               float* seq_mean /* nullable */, int R, int L, int E, void* stream);
+int tag_convgru_update_backward(const float* dnew /* nullable */, const float* dseq /* nullable */, const int64_t* text_len,
+                                const float* x, const float* u, const float* o, float* do_pre, float* du_pre, float* dx, int R,
+                                int L, int E, void* stream);
+int tag_convgru_gates_backward(const float* dxr, const float* x, const float* r, float* dr_pre, float* dx, long M, int E,
+                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * T1 + T2: nn.Embedding gather + mean over valid tokens
  * models/text_encoder.py:39-43,79-88; models/utils.py:33-58.
  * text (B,L) int64, text_len (B) int64, table (V,D); token_emb (B,L,D) nullable; seq_emb (B,D).

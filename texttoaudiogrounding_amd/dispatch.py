@@ -1111,6 +1111,201 @@ def text_selfattn_backward(dout, saved, heads, drop_p=0.0, seed=0, outs=None, ne
 
 
 # ------------------------------------------------------------------------------------------------
+# text intra-attention (row T5): per layer ONE row-local core launch (csrc/text_intra.hip), the three gate products of the shared
+# ConvGRUCell as tag_gemm calls over the two K halves of [message ; x], two element-wise launches; and its backward
+# ------------------------------------------------------------------------------------------------
+TEXT_INTRA_MAX_L = 64
+TEXT_INTRA_MAX_E = 1024
+
+
+def text_intra_dropout_seeds(seed, layers):
+    """[(seed_a, seed_b)] per layer -- the 2 x num_layers masks behind the positions -- from ONE operator seed."""
+    return [((int(seed) + 2 * l) % (2 ** 62), (int(seed) + 2 * l + 1) % (2 ** 62)) for l in range(layers)]
+
+
+def text_intra_check(E, L=None):
+    """The domain of tag_text_intra_*, raised before any launch with the limit named."""
+    if E < 2 or E % 2:
+        raise ValueError(f"text_intra: embed_dim {E} is odd (or below 2); the sin/cos position table is defined for even embed_dim only")
+    if E > TEXT_INTRA_MAX_E:
+        raise ValueError(f"text_intra: embed_dim {E}; the kernel serves embed_dim <= {TEXT_INTRA_MAX_E} and there is no eager fallback")
+    if L is not None and not 1 <= L <= TEXT_INTRA_MAX_L:
+        raise ValueError(f"text_intra: {L} tokens per phrase; the kernel serves 1 ... {TEXT_INTRA_MAX_L} tokens and there is no "
+                         "eager fallback")
+
+
+def _text_len_chk(text_len, R):
+    if not text_len.is_cuda or text_len.dtype != torch.long or text_len.numel() != R:
+        raise RuntimeError("text_intra: text_len must be an int64 tensor of R entries on the device (no CPU fallback)")
+    return text_len.contiguous()
+
+
+def _pe_rows(pe, L, E):
+    pe = _chk(pe, "pe").view(-1, E)
+    if pe.shape[0] < L:
+        raise ValueError(f"text_intra: the position table has {pe.shape[0]} rows for {L} positions")
+    return pe
+
+
+def text_intra_core(x, pe, text_len, need_attn=True, drop_p=0.0, seeds=(0, 0)):
+    """ONE launch of tag_text_intra_forward: x (R, L, E), pe (>= L, E), text_len (R) int64 -> message (R, L, E), attn (R, L, L) =
+    the softmax output with the dead cells included, or None."""
+    x = _chk(x, "x")
+    R, L, E = x.shape
+    text_intra_check(E, L)
+    pe, text_len = _pe_rows(pe, L, E), _text_len_chk(text_len, R)
+    msg = _empty(R, L, E, like=x)
+    attn = _empty(R, L, L, like=x) if need_attn else None
+    call("tag_text_intra_forward", ptr(x), ptr(pe), ptr(text_len), ptr(msg), ptr(attn), R, L, E, float(drop_p), int(seeds[0]),
+         int(seeds[1]))
+    return msg, attn
+
+
+def text_intra_core_backward(dmsg, x, pe, attn, text_len, drop_p=0.0, seeds=(0, 0), out=None):
+    """ONE launch of tag_text_intra_backward -> dx (R, L, E); out: a (R, L, E) tensor the result is ADDED to."""
+    dmsg, x, attn = _chk(dmsg, "grad"), _chk(x, "x"), _chk(attn, "attn")
+    R, L, E = x.shape
+    text_intra_check(E, L)
+    pe, text_len = _pe_rows(pe, L, E), _text_len_chk(text_len, R)
+    dx = out if out is not None else _empty(R, L, E, like=x)
+    call("tag_text_intra_backward", ptr(dmsg), ptr(x), ptr(pe), ptr(attn), ptr(text_len), ptr(dx), int(out is not None), R, L, E,
+         float(drop_p), int(seeds[0]), int(seeds[1]))
+    return dx
+
+
+def convgru_gates_forward(u, r, x):
+    """u, r (M, E) pre-activations -> sigmoid in place; -> xr = x * r."""
+    M, E = u.shape
+    xr = _empty(M, E, like=u)
+    call("tag_convgru_gates_forward", ptr(_chk(u, "u")), ptr(_chk(r, "r")), ptr(_chk(x, "x")), ptr(xr), M, E)
+    return xr
+
+
+def convgru_update_forward(o, u, x, R, L, text_len=None):
+    """o (R*L, E) pre-activation -> tanh in place; -> xnew = x (1 - u) + o u and, with text_len, its mean over the valid
+    positions (R, E)."""
+    E = o.shape[-1]
+    xnew = _empty(R * L, E, like=o)
+    seq = _empty(R, E, like=o) if text_len is not None else None
+    call("tag_convgru_update_forward", ptr(_chk(o, "o")), ptr(_chk(u, "u")), ptr(_chk(x, "x")), ptr(xnew), ptr(text_len), ptr(seq),
+         R, L, E)
+    return xnew, seq
+
+
+def convgru_update_backward(dnew, dseq, text_len, x, u, o, R, L):
+    """-> do_pre, du_pre and the direct term dx = g (1 - u), each (R*L, E); g = dnew + the share of dseq (either may be None)."""
+    E = o.shape[-1]
+    dnew = _chk(dnew, "grad") if dnew is not None else None
+    dseq = _chk(dseq, "grad") if dseq is not None else None
+    do_pre, du_pre, dx = (_empty(R * L, E, like=o) for _ in range(3))
+    call("tag_convgru_update_backward", ptr(dnew), ptr(dseq), ptr(text_len), ptr(_chk(x, "x")), ptr(_chk(u, "u")), ptr(_chk(o, "o")),
+         ptr(do_pre), ptr(du_pre), ptr(dx), R, L, E)
+    return do_pre, du_pre, dx
+
+
+def convgru_gates_backward(dxr, x, r, dx):
+    """dxr (M, E) -> dr_pre = dxr x r (1 - r); dx += dxr r (in place)."""
+    M, E = dxr.shape
+    dr_pre = _empty(M, E, like=dxr)
+    call("tag_convgru_gates_backward", ptr(_chk(dxr, "grad")), ptr(_chk(x, "x")), ptr(_chk(r, "r")), ptr(dr_pre), ptr(dx), M, E)
+    return dr_pre
+
+
+def _gate_product(msg, h, w, bias, M, E):
+    """[msg ; h] @ w^T + bias, w (E, 2E), as two K halves into one output: the concatenation is never materialised."""
+    out = gemm(msg, w, M, E, E, transB=True, ldb=2 * E, bias=bias)
+    return gemm(h, w[:, E:], M, E, E, transB=True, ldb=2 * E, out=out, accumulate=True)
+
+
+def text_intra_forward(x, text_len, pe, w_r, b_r, w_u, b_u, w_o, b_o, layers, need_grad, drop_p=0.0, seed=0):
+    """IntraAttention.forward behind the embedding (models/text_encoder.py:213-237): x (R, L, E) embedded tokens, text_len (R)
+    int64 on the device, pe (>= L, E), the ConvGRUCell's reset / update / out gates (E, 2E) / (E), applied ``layers`` times.
+    drop_p > 0 (train): two independent dropouts behind the positions per layer, keep masks of
+    text_intra_dropout_seeds(seed, layers).  -> token_emb (R, L, E), seq_emb (R, E), saved state per layer or None."""
+    x = _chk(x, "x")
+    R, L, E = x.shape
+    text_intra_check(E, L)
+    if layers < 1:
+        raise ValueError("text_intra: num_layers must be >= 1 (IntraAttention serves num_layers = 0 without this operator)")
+    M = R * L
+    w_r, w_u, w_o = _chk(w_r, "reset_gate.weight"), _chk(w_u, "update_gate.weight"), _chk(w_o, "out_gate.weight")
+    b_r, b_u, b_o = _chk(b_r, "reset_gate.bias"), _chk(b_u, "update_gate.bias"), _chk(b_o, "out_gate.bias")
+    seeds = text_intra_dropout_seeds(seed, layers)
+    saved, seq = [], None
+    h = x.view(M, E)
+    for l in range(layers):
+        msg, attn = text_intra_core(h.view(R, L, E), pe, text_len, need_grad, drop_p, seeds[l])
+        msg = msg.view(M, E)
+        u = _gate_product(msg, h, w_u, b_u, M, E)
+        r = _gate_product(msg, h, w_r, b_r, M, E)
+        xr = convgru_gates_forward(u, r, h)
+        o = _gate_product(msg, xr, w_o, b_o, M, E)
+        hnew, seq = convgru_update_forward(o, u, h, R, L, text_len if l == layers - 1 else None)
+        if need_grad:
+            saved.append(dict(x=h, msg=msg, attn=attn, u=u, r=r, o=o, xr=xr))
+        h = hnew
+    return h.view(R, L, E), seq, (saved if need_grad else None)
+
+
+def text_intra_backward(dtok, dseq, text_len, pe, saved, w_r, w_u, w_o, drop_p=0.0, seed=0, outs=None, need=None, need_dx=True):
+    """-> (dx (R, L, E) or None, [dw_r, db_r, dw_u, db_u, dw_o, db_o]).  dtok (R, L, E) / dseq (R, E): either may be None.  The
+    cell is shared by the layers: every gate's gradient is accumulated over them (tag_gemm accumulate into ONE buffer per gate,
+    the bias column sums added).  outs: optional destination per parameter (flat-gradient views), written directly; need: per
+    parameter, False skips its GEMMs / column sums (a frozen parameter) and leaves None."""
+    layers = len(saved)
+    M, E = saved[0]["x"].shape
+    L = saved[0]["attn"].shape[1]
+    R = M // L
+    outs = list(outs) if outs is not None else [None] * 6
+    need = list(need) if need is not None else [True] * 6
+    seeds = text_intra_dropout_seeds(seed, layers)
+    w_r, w_u, w_o = _chk(w_r, "reset_gate.weight"), _chk(w_u, "update_gate.weight"), _chk(w_o, "out_gate.weight")
+    g = [None] * 6
+
+    def weight_grad(i, dpre, msg, h):
+        if not need[i]:
+            return
+        first = g[i] is None
+        if first:
+            g[i] = outs[i] if outs[i] is not None else _empty(E, 2 * E, like=dpre)
+        gemm(dpre, msg, E, E, M, transA=True, lda=E, out=g[i], ldc=2 * E, accumulate=not first)
+        gemm(dpre, h, E, E, M, transA=True, lda=E, out=g[i][:, E:], ldc=2 * E, accumulate=not first)
+
+    def bias_grad(i, dpre):
+        if not need[i]:
+            return
+        if g[i] is None:
+            g[i] = colsum(dpre, M, E, out=outs[i])
+        else:
+            g[i].add_(colsum(dpre, M, E))
+
+    dnew, dsq, dx = (dtok.reshape(M, E) if dtok is not None else None), dseq, None
+    for l in range(layers - 1, -1, -1):
+        sv = saved[l]
+        h, msg = sv["x"], sv["msg"]
+        do_pre, du_pre, dx = convgru_update_backward(dnew, dsq, text_len, h, sv["u"], sv["o"], R, L)
+        dxr = gemm(do_pre, w_o[:, E:], M, E, E, ldb=2 * E)
+        dr_pre = convgru_gates_backward(dxr, h, sv["r"], dx)
+        weight_grad(4, do_pre, msg, sv["xr"])
+        bias_grad(5, do_pre)
+        weight_grad(2, du_pre, msg, h)
+        bias_grad(3, du_pre)
+        weight_grad(0, dr_pre, msg, h)
+        bias_grad(1, dr_pre)
+        if l == 0 and not need_dx:
+            dx = None
+            break
+        dmsg = gemm(do_pre, w_o, M, E, E, ldb=2 * E)
+        gemm(du_pre, w_u, M, E, E, ldb=2 * E, out=dmsg, accumulate=True)
+        gemm(dr_pre, w_r, M, E, E, ldb=2 * E, out=dmsg, accumulate=True)
+        gemm(du_pre, w_u[:, E:], M, E, E, ldb=2 * E, out=dx, accumulate=True)
+        gemm(dr_pre, w_r[:, E:], M, E, E, ldb=2 * E, out=dx, accumulate=True)
+        text_intra_core_backward(dmsg.view(R, L, E), h.view(R, L, E), pe, sv["attn"], text_len, drop_p, seeds[l], out=dx.view(R, L, E))
+        dnew, dsq = dx, None
+    return (dx.view(R, L, E) if dx is not None else None), g
+
+
+# ------------------------------------------------------------------------------------------------
 # One conv3x3 -> BatchNorm -> ReLU (-> pool) stage as a standalone operator: what SURVEY.md section 8(b) lists as
 # ``conv3x3_bn_relu[_pool]`` and what ConvBlock.forward (models/panns.py:46-62) is made of.  The fused Cnn8Rnn node (functions.py)
 # never materialises relu(bn(y)); this stage does (its output IS that tensor, pooled), so that it composes like an nn.Module.

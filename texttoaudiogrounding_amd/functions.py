@@ -35,6 +35,7 @@ from .dispatch import (bias_bnrelu_backward, bias_bnrelu_forward, bias_bnrelu_po
 from .dispatch import class_pool_forward, tagging_head_dlogit
 from .dispatch import text_gru_backward, text_gru_forward
 from .dispatch import text_selfattn_backward, text_selfattn_forward
+from .dispatch import text_intra_backward, text_intra_forward
 from . import engine
 
 # ------------------------------------------------------------------------------------------------
@@ -933,6 +934,39 @@ class TextSelfAttnFunction(TagFunction):
                 _deliver(grads, sk, i, g[i] if sk[i] is not None else g[i].view(ctx.shapes[i]))
         _ready(ctx.params)
         return (dtok, None, None, None, None, None, *grads)
+
+
+class TextIntraFunction(TagFunction):
+    """torch.ops.tag.text_intra with direct gradients (StrongRunner): IntraAttention behind its embedding
+    (models/text_encoder.py:213-237) whose gate gradients, accumulated over the layers that share the cell, go straight into
+    their flat-gradient views; a parameter with requires_grad = False costs no GEMM / column sum and its flat-gradient rows
+    are not touched.  Same kernels as the operator."""
+
+    @staticmethod
+    def forward(ctx, x, text_len, pe, layers, drop_p, seed, *params):
+        need = engine._RECORDING and any(ctx.needs_input_grad)
+        tok, seq, saved = text_intra_forward(x, text_len, pe, *[p.detach() for p in params], layers, need, drop_p, seed)
+        ctx.ti = (saved, text_len, pe, drop_p, seed)
+        ctx.weights = [params[i].detach() for i in (0, 2, 4)]
+        ctx.sinks = _sinks(list(params))
+        ctx.params = list(params) if cfg.DIRECT_GRADS else None
+        ctx.set_materialize_grads(False)
+        return tok, seq
+
+    @staticmethod
+    def backward(ctx, dtok, dseq):
+        saved, text_len, pe, drop_p, seed = ctx.ti
+        sk, need = ctx.sinks, list(ctx.needs_input_grad[6:])
+        if (dtok is None and dseq is None) or saved is None:
+            return (None,) * 12
+        dx, g = text_intra_backward(dtok, dseq, text_len, pe, saved, *ctx.weights, drop_p, seed, outs=[sk[i] for i in range(6)],
+                                    need=need, need_dx=ctx.needs_input_grad[0])
+        grads = [None] * 6
+        for i in range(6):
+            if need[i]:
+                _deliver(grads, sk, i, g[i])
+        _ready(ctx.params)
+        return (dx, None, None, None, None, None, *grads)
 
 
 class Seq2SeqAttentionFunction(TagFunction):

@@ -131,6 +131,12 @@ _SIGS = {
     "tag_text_selfattn_backward": (c_int, [P] * 5 + [c_int] * 4 + [c_float, c_uint64, P]),
     "tag_text_cls_pe_forward": (c_int, [P] * 4 + [c_int] * 3 + [c_float, c_uint64, P]),
     "tag_text_cls_pe_backward": (c_int, [P] * 3 + [c_int] * 3 + [c_float, c_uint64, P]),
+    "tag_text_intra_forward": (c_int, [P] * 5 + [c_int] * 3 + [c_float, c_uint64, c_uint64, P]),
+    "tag_text_intra_backward": (c_int, [P] * 6 + [c_int] * 4 + [c_float, c_uint64, c_uint64, P]),
+    "tag_convgru_gates_forward": (c_int, [P] * 4 + [c_long, c_int, P]),
+    "tag_convgru_update_forward": (c_int, [P] * 6 + [c_int] * 3 + [P]),
+    "tag_convgru_update_backward": (c_int, [P] * 9 + [c_int] * 3 + [P]),
+    "tag_convgru_gates_backward": (c_int, [P] * 5 + [c_long, c_int, P]),
     "tag_embed_mean_forward": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_mean_backward": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_check_ids": (c_int, [P, c_long, c_int, P, P]),

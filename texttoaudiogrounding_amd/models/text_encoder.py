@@ -1,5 +1,5 @@
-"""Learned text encoders: the word-embedding bag EmbeddingAgg, the recurrent RnnEncoder and the SelfAttention encoder (mirror
-of models/text_encoder.py:14-43,61-145,240-268 in the reference)."""
+"""Learned text encoders: the word-embedding bag EmbeddingAgg, the recurrent RnnEncoder, the IntraAttention encoder with its
+ConvGRUCell and the SelfAttention encoder (mirror of models/text_encoder.py:14-43,61-268 in the reference)."""
 import math
 from typing import Dict
 
@@ -160,6 +160,122 @@ class PositionalEncoding(nn.Module):
         pe[:, 0::2] = torch.sin(position * div_term)
         pe[:, 1::2] = torch.cos(position * div_term)
         self.register_buffer("pe", pe.unsqueeze(0))
+
+
+class ConvGRUCell(nn.Module):
+    """Parameter container with the reference's layout and init (models/text_encoder.py:147-163): ``reset_gate``,
+    ``update_gate``, ``out_gate`` = Linear(input_size + hidden_size, hidden_size), weights orthogonal, biases zero.  The
+    arithmetic (u = sigmoid(W_u [m ; h] + b_u), r likewise, o = tanh(W_o [m ; h * r] + b_o), h <- h (1 - u) + o u) runs in
+    ``torch.ops.tag.text_intra``."""
+
+    def __init__(self, input_size, hidden_size, kernel_size=1):
+        super().__init__()
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        self.reset_gate = nn.Linear(input_size + hidden_size, hidden_size)
+        self.update_gate = nn.Linear(input_size + hidden_size, hidden_size)
+        self.out_gate = nn.Linear(input_size + hidden_size, hidden_size)
+        for gate in (self.reset_gate, self.update_gate, self.out_gate):
+            nn.init.orthogonal_(gate.weight)
+        for gate in (self.reset_gate, self.update_gate, self.out_gate):
+            nn.init.constant_(gate.bias, 0.)
+
+
+class IntraAttention(nn.Module):
+    """models/text_encoder.py:191-237: ``embedding`` (any module with ``.embed_dim`` whose forward returns (R, L, E) or a dict
+    with "token_emb": EmbeddingLayer, EmbeddingAgg) -> ``num_layers`` times, with the SAME ``conv_gru`` cell (its gradients
+    accumulate over the layers): an unscaled dot-product attention of the phrase over itself, whose message and the current
+    state go through the cell -> ``token_emb`` = the final state, ``seq_emb`` = its mean over the first ``text_len`` positions.
+
+    ``pe`` and ``conv_gru`` only HOLD the buffer and the parameters (state-dict keys ``embedding...``, ``pe.pe``,
+    ``conv_gru.reset_gate.weight / .bias``, ``conv_gru.update_gate...``, ``conv_gru.out_gate...``); the arithmetic runs in
+    ``torch.ops.tag.text_intra``: the core and the cell's element-wise steps are the row-local HIP kernels of
+    csrc/text_intra.hip, the gate products are tag_gemm calls.  Every quirk of the reference is kept:
+
+    * the score is ``pe(x) @ pe(x)^T`` from TWO separate calls of ``pe``: in train mode two independent dropout masks behind
+      the positions, at the FIXED p = 0.2 (not a constructor argument); in eval mode both operands are the same x + pe;
+    * the score is unscaled (it reaches the hundreds: |pe_i|^2 = E / 2);
+    * cells whose query or key is >= text_len are filled with 1e-10, NOT -inf: dead cells take part in the softmax with a
+      score of about 0, a padded query row attends uniformly over all L positions, valid scores that are negative are
+      outweighed by the dead cells, and no gradient reaches the score operands through a dead cell;
+    * the message is ``attn @ x`` -- x, not x + pe;
+    * ``token_emb`` is non-zero at padded positions, and pad tokens are looked up like any other (row 0 of the table, which
+      therefore receives gradient); the result of a row depends on the batch's padded L.
+
+    Unlike the reference, ``text`` / ``text_len`` may carry leading dimensions (flattened here, as in the two other encoders;
+    the reference raises on a 3-D ``text``).  max(text_len) < L runs, as in the reference.  ``text_len`` 0 gives a finite
+    ``token_emb`` (every cell of the row is dead) and ``seq_emb`` = 0/0 = NaN: the masked mean divides by text_len exactly as
+    ``tag_embed_mean_forward`` (EmbeddingAgg) does for an empty phrase.  ``num_layers`` 0 returns the embedding and its
+    masked mean.
+
+    Dropout (train mode): the project's counter-based keep masks (``tag_dropout_mask``; seeds
+    ops.text_intra_dropout_seeds(ops.new_seed(), num_layers), drawn from torch's global generator like the audio encoders'
+    dropouts and decorrelated per rank by ops.SEED_RANK): the same rule as nn.Dropout's, not torch's random stream.
+
+    There is no eager fallback: at most 64 tokens, embed_dim even and <= 1024; anything else raises ValueError."""
+
+    MAX_TOKENS = ops.TEXT_INTRA_MAX_L
+
+    def __init__(self, embedding: nn.Module, num_layers: int, pooling: str = "mean") -> None:
+        super().__init__()
+        if not hasattr(embedding, "embed_dim"):
+            raise ValueError(f"IntraAttention: the embedding module {type(embedding).__name__} has no embed_dim attribute")
+        ops.text_intra_check(embedding.embed_dim)
+        self.embedding = embedding
+        self.embed_dim = embedding.embed_dim
+        self.pe = PositionalEncoding(self.embed_dim, 0.2)
+        self.conv_gru = ConvGRUCell(self.embed_dim, self.embed_dim)
+        self.num_layers = num_layers
+        self.pooling = pooling
+
+    def forward(self, input_dict):
+        n_tok = np.shape(input_dict["text"])[-1]
+        if n_tok > self.MAX_TOKENS:                        # before any launch
+            raise ValueError(f"IntraAttention: {n_tok} tokens per phrase; the attention kernel serves at most {self.MAX_TOKENS} "
+                             "and there is no eager fallback")
+        lead = tuple(np.shape(input_dict["text"])[:-1])
+        if len(lead) != 1:                                 # the inner module sees the flat (R, L) batch the reference's would
+            input_dict = dict(input_dict, text=torch.as_tensor(input_dict["text"]).reshape(-1, n_tok),
+                              text_len=torch.as_tensor(input_dict["text_len"]).reshape(-1))
+        if self.num_layers < 1:
+            out = self._embedding_and_mean(input_dict)
+            return {k: v.view(*lead, *v.shape[1:]) for k, v in out.items()}
+        x = self.embedding(input_dict)
+        if isinstance(x, dict) and "token_emb" in x:
+            x = x["token_emb"]
+        L, E = x.shape[-2], x.shape[-1]
+        x = x.reshape(-1, L, E)
+        text_len = torch.as_tensor(input_dict["text_len"]).long().to(x.device).reshape(-1).contiguous()
+        g = self.conv_gru
+        params = [g.reset_gate.weight, g.reset_gate.bias, g.update_gate.weight, g.update_gate.bias, g.out_gate.weight,
+                  g.out_gate.bias]
+        p = float(self.pe.p) if self.training else 0.0
+        seed = ops.new_seed() if p > 0.0 else 0
+        pe = self.pe.pe[0]
+        if ops.DIRECT_GRADS:
+            tok, seq = ops.TextIntraFunction.apply(x, text_len, pe, self.num_layers, p, seed, *params)
+        else:
+            tok, seq, _ = torch.ops.tag.text_intra(x, text_len, pe, params, self.num_layers, p, seed)
+        out = {"token_emb": tok.view(*lead, L, E)}
+        if self.pooling == "mean":
+            out["seq_emb"] = seq.view(*lead, E)
+        return out
+
+    def _embedding_and_mean(self, input_dict):
+        """num_layers = 0: the loop of the reference does not run and its outputs are the embedding and mean_with_lens of it --
+        the fused gather + mean launch (``tag_embed_mean_forward``) on the inner module's table."""
+        layer = self.embedding if isinstance(self.embedding, EmbeddingLayer) else getattr(self.embedding, "embedding", None)
+        if not isinstance(layer, EmbeddingLayer):
+            raise NotImplementedError(f"IntraAttention: num_layers = 0 over {type(self.embedding).__name__} has no HIP kernel "
+                                      "(served: EmbeddingLayer, EmbeddingAgg); there is no eager fallback")
+        table = layer.core.weight
+        ids = _ids_to_device(input_dict["text"], table)
+        lens = torch.as_tensor(input_dict["text_len"]).long().to(table.device).reshape(-1).contiguous()
+        if ops.DIRECT_GRADS:
+            seq, tok = ops.EmbedMeanFunction.apply(table, ids, lens, True)
+        else:
+            seq, tok = torch.ops.tag.embed_mean(table, ids, lens)
+        return {"token_emb": tok, "seq_emb": seq} if self.pooling == "mean" else {"token_emb": tok}
 
 
 class SelfAttention(nn.Module):

@@ -383,6 +383,84 @@ def _tsa_backward(ctx, dout, _dsaved):
 register_autograd("tag::text_selfattn", _tsa_backward, setup_context=_tsa_setup)
 
 
+# ------------------------------------------------------------------------------------------------ T5 text intra-attention
+_TIA_PER_LAYER = ("msg", "attn", "u", "r", "o", "xr")
+
+
+def _tia_saved(x, saved, layers):
+    """The per-layer state ops.text_intra_backward expects, from what the operator returned: six tensors per layer, then the
+    input of every layer but the first (the first layer's is the operator's input)."""
+    R, L, E = x.shape
+    n = len(_TIA_PER_LAYER)
+    xs = [x.reshape(R * L, E)] + list(saved[n * layers:])
+    return [dict(zip(_TIA_PER_LAYER, saved[n * l: n * (l + 1)]), x=xs[l]) for l in range(layers)]
+
+
+@custom_op("tag::text_intra", mutates_args=())
+def text_intra(x: Tensor, text_len: Tensor, pe: Tensor, params: List[Tensor], layers: int, drop_p: float,
+               seed: int) -> Tuple[Tensor, Tensor, List[Tensor]]:
+    """IntraAttention behind its embedding (models/text_encoder.py:213-237): x (R, L, E) embedded tokens, text_len (R) int64,
+    pe (>= L, E) positions, params = conv_gru's [reset_gate.weight, reset_gate.bias, update_gate.weight, update_gate.bias,
+    out_gate.weight, out_gate.bias], the SAME cell applied ``layers`` >= 1 times -> token_emb (R, L, E), seq_emb (R, E) and the
+    saved state (message, attn, u, r, o, x * r per layer, then the input of every layer but the first).  drop_p > 0 (the
+    caller passes 0 in eval mode): two independent dropouts behind the positions per layer, keep masks of
+    ops.text_intra_dropout_seeds(seed, layers)."""
+    tok, seq, saved = ops.text_intra_forward(x, text_len, pe, *params, layers, True, drop_p, seed)
+    return tok, seq, [sv[k] for sv in saved for k in _TIA_PER_LAYER] + [sv["x"] for sv in saved[1:]]
+
+
+@text_intra.register_fake
+def _(x, text_len, pe, params, layers, drop_p, seed):
+    R, L, E = x.shape
+    per = [x.new_empty(R * L, E), x.new_empty(R, L, L)] + [x.new_empty(R * L, E) for _ in range(4)]
+    return (x.new_empty(R, L, E), x.new_empty(R, E),
+            [torch.empty_like(t) for _ in range(layers) for t in per] + [x.new_empty(R * L, E) for _ in range(layers - 1)])
+
+
+@custom_op("tag::text_intra_backward", mutates_args=())
+def text_intra_backward(dtok: Optional[Tensor], dseq: Optional[Tensor], x: Tensor, text_len: Tensor, pe: Tensor,
+                        saved: List[Tensor], params: List[Tensor], layers: int, drop_p: float, seed: int, need: List[bool],
+                        need_dx: bool) -> List[Tensor]:
+    """-> [dx] + one gradient per parameter; an entry that is not needed (need[i] / need_dx False) is an empty tensor."""
+    sv = _tia_saved(x, saved, layers)
+    dx, g = ops.text_intra_backward(dtok, dseq, text_len, pe, sv, params[0], params[2], params[4], drop_p, seed, need=list(need),
+                                    need_dx=need_dx)
+    none = lambda: x.new_empty(0)                                                    # noqa: E731
+    return [dx if dx is not None else none()] + [t if t is not None else none() for t in g]
+
+
+@text_intra_backward.register_fake
+def _(dtok, dseq, x, text_len, pe, saved, params, layers, drop_p, seed, need, need_dx):
+    return [torch.empty_like(x) if need_dx else x.new_empty(0)] + [torch.empty_like(p) if n else x.new_empty(0)
+                                                                    for p, n in zip(params, need)]
+
+
+def _tia_setup(ctx, inputs, output):
+    x, text_len, pe, params, layers, drop_p, seed = inputs
+    _, _, saved = output
+    ctx.save_for_backward(x, text_len, pe, *saved, *params)
+    ctx.meta = (layers, drop_p, seed, len(saved))
+    ctx.need = [bool(p.requires_grad) for p in params]
+    ctx.need_dx = bool(x.requires_grad)
+
+
+def _tia_backward(ctx, dtok, dseq, _dsaved):
+    layers, drop_p, seed, ns = ctx.meta
+    x, text_len, pe = ctx.saved_tensors[:3]
+    saved, params = list(ctx.saved_tensors[3:3 + ns]), list(ctx.saved_tensors[3 + ns:])
+    if dtok is None and dseq is None:
+        return (None,) * 7
+    if dtok is not None:
+        dtok = dtok.contiguous()
+    if dseq is not None:
+        dseq = dseq.contiguous()
+    g = torch.ops.tag.text_intra_backward(dtok, dseq, x, text_len, pe, saved, params, layers, drop_p, seed, ctx.need, ctx.need_dx)
+    return (g[0] if ctx.need_dx else None, None, None, [t if n else None for t, n in zip(g[1:], ctx.need)], None, None, None)
+
+
+register_autograd("tag::text_intra", _tia_backward, setup_context=_tia_setup)
+
+
 # ------------------------------------------------------------------------------------------------ M1/M2 frame x phrase heads
 @custom_op("tag::frame_match", mutates_args=())
 def frame_match(audio: Tensor, text: Tensor, kind: int, l2norm: bool, scale: bool) -> Tensor:
@@ -954,4 +1032,4 @@ OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_r
             "segments", "cnn8rnn_encoder", "crnn_encoder",
             "cross_cnn8rnn", "cross_cdur", "tagging_head", "tagging_head_backward", "masked_frame_bce",
             "masked_frame_bce_backward", "text_gru", "text_gru_backward", "text_selfattn", "text_selfattn_backward", "infonce",
-            "infonce_backward", "triplet", "triplet_backward", "milnce", "milnce_backward"]
+            "infonce_backward", "triplet", "triplet_backward", "milnce", "milnce_backward", "text_intra", "text_intra_backward"]
