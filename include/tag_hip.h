@@ -976,6 +976,35 @@ int tag_milnce_forward(const float* clip_sim, const float* label, int B, int N, 
 int tag_milnce_backward(const float* clip_sim, const float* label, int B, int N, double tau, const float* dloss, float* dclip,
                         const void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Clip-level BCE objectives of weak phrase training (clip_bce.hip) over the flattened (B,N) clip matrix of M elements: fp32 in,
+ * fp32 out, every element term and the sum over M in fp64, in a fixed order, no atomics (two runs give the same bits).
+ * p = clip_sim, y = label (hard or soft in [0,1]), aux (M) = the weight of mode 1 / the prior of mode 4 (may be null otherwise).
+ *   loss[0] = (1/M) sum_i e_i,   dp_i = dloss[0] / M * de_i/dp_i,   y and aux get no gradient
+ *   bce(x,t)  = -(t max(ln x, -100) + (1 - t) max(ln(1 - x), -100)),   bce'(x,t) = (x - t) / max(x (1 - x), 1e-12)
+ *   (torch's own guards; every 1e-12 here is its fp32 constant 1e-12f)
+ *   mode 0  FocalClipBceLoss (losses.py:59), c0 = gamma, c1 = alpha:
+ *           e = -alpha (1-p)^gamma y ln p - (1-alpha) p^gamma (1-y) ln(1-p), with the clamped logarithms of bce, x^0 = 1,
+ *           d(x^gamma) = gamma x^gamma / max(x, 1e-12) and d ln p = -bce'(p,1), d ln(1-p) = -bce'(p,0): finite at p = 0 and
+ *           p = 1 (the reference is NaN/inf there), and gamma = 0, alpha = 1/2 is half of the plain BCE everywhere
+ *   mode 1  ClipBceLossFreqWeight (:75): e = w bce(p,y), w = (y == 0 ? 1 : aux)
+ *   mode 2  SymmetricClipBceLoss (:90), c0 = eps: e = bce(p,y) + bce(yc,p), yc = clamp(y, eps, 1-eps);
+ *           de = bce'(p,y) + ln(1-yc) - ln yc with both logarithms clamped at -100 (forward and backward alike)
+ *   mode 3  OriginSymmetricClipBceLoss (:107), c0 = a, c1 = b, c2 = A = ln eps: e = a bce(p,y) - b A (y (1-p) + (1-y) p)
+ *   mode 4  PriorAdjustedClipBceLoss (:125), c0 = tau, aux = prior pi in (0,1): u = pi^tau, v = (1-pi)^tau, s = p u + (1-p) v,
+ *           e = bce(p u / s, y), de = bce'(p u / s, y) u v / s^2
+ * The forward is one launch of a single workgroup up to an internal M (dispatch.CLIP_BCE_ONE_LAUNCH_MAX); above it the forward
+ * is two launches with fp64 partials in ws (tag_clip_bce_ws_bytes(M) bytes; ws may be null for the one-launch sizes).  The
+ * backward is one elementwise launch; dp may not alias p.  Any M >= 1.
+ * TAG_EINVAL (message in tag_last_error) for M < 1, a mode outside 0..4, a null p / y / loss / dp / dloss, a null aux in modes
+ * 1 and 4, or a NaN constant.
+ */
+size_t tag_clip_bce_ws_bytes(long M);
+int tag_clip_bce_forward(const float* p, const float* y, const float* aux, long M, int mode, double c0, double c1, double c2,
+                         float* loss, void* ws, void* stream);
+int tag_clip_bce_backward(const float* p, const float* y, const float* aux, long M, int mode, double c0, double c1, double c2,
+                          const float* dloss, float* dp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1838,3 +1838,52 @@ def milnce_backward(clip_sim, label, tau, dloss, ws=None):
     dc = torch.empty_like(c)
     call("tag_milnce_backward", ptr(c), ptr(y), B, N, float(tau), ptr(_dloss(dloss)), ptr(dc), ptr(ws))
     return dc
+
+
+# ------------------------------------------------------------------------------------------------ clip-level BCE objectives
+CLIP_BCE_MODES = {"focal": 0, "freq_weight": 1, "symmetric": 2, "origin_symmetric": 3, "prior_adjusted": 4}
+_CLIP_BCE_AUX = (CLIP_BCE_MODES["freq_weight"], CLIP_BCE_MODES["prior_adjusted"])
+CLIP_BCE_ONE_LAUNCH_MAX = 4096        # = ONE_LAUNCH_MAX of csrc/clip_bce.hip: the largest M whose forward is one launch
+
+
+def _clip_bce_args(clip_sim, label, aux, mode, consts):
+    """Shapes, dtypes, mode and constants first (they need no device), then the device of every tensor."""
+    if mode not in CLIP_BCE_MODES.values():
+        raise RuntimeError(f"clip_bce mode {mode!r}: expected one of {CLIP_BCE_MODES}")
+    if any(math.isnan(float(c)) for c in consts):
+        raise RuntimeError(f"clip_bce: a constant is NaN: {tuple(consts)}")
+    if clip_sim.ndim != 2 or clip_sim.numel() < 1:
+        raise RuntimeError(f"clip_sim: expected a (B,N) matrix with B, N >= 1, got {tuple(clip_sim.shape)}")
+    if mode in _CLIP_BCE_AUX and aux is None:
+        raise RuntimeError(f"clip_bce mode {mode}: needs aux (the weight / prior) of clip_sim's shape {tuple(clip_sim.shape)}")
+    for name, t in (("label", label), ("aux", aux)):
+        if t is not None and t.shape != clip_sim.shape:
+            raise RuntimeError(f"{name} {tuple(t.shape)}: expected clip_sim's shape {tuple(clip_sim.shape)}")
+    for name, t in (("clip_sim", clip_sim), ("label", label), ("aux", aux)):
+        if t is not None and t.dtype != F32:
+            raise RuntimeError(f"{name}: expected float32, got {t.dtype}")
+    c, y = _chk(clip_sim, "clip_sim"), _chk(label, "label")      # (a strided clip_sim view is made contiguous)
+    a = _chk(aux, "aux") if aux is not None and mode in _CLIP_BCE_AUX else None
+    for name, t in (("label", y), ("aux", a)):
+        if t is not None and t.device != c.device:
+            raise RuntimeError(f"{name} on {t.device}, clip_sim on {c.device}: expected one device")
+    return c, y, a
+
+
+def clip_bce_forward(clip_sim, label, aux, mode, c0, c1, c2):
+    """The clip-level BCE variants (losses.py:59-143 in the reference; mode: CLIP_BCE_MODES value, the constants as
+    include/tag_hip.h lists them) on clip_sim / label / aux (B,N) -> 0-dim loss."""
+    c, y, a = _clip_bce_args(clip_sim, label, aux, mode, (c0, c1, c2))
+    M = c.numel()
+    loss, ws = _empty(1, like=c), _ws(query("tag_clip_bce_ws_bytes", M), c)
+    call("tag_clip_bce_forward", ptr(c), ptr(y), ptr(a), M, int(mode), float(c0), float(c1), float(c2), ptr(loss), ptr(ws))
+    return loss.view(())
+
+
+def clip_bce_backward(clip_sim, label, aux, mode, c0, c1, c2, dloss):
+    """d loss / d clip_sim (B,N), contiguous; label and aux get no gradient."""
+    c, y, a = _clip_bce_args(clip_sim, label, aux, mode, (c0, c1, c2))
+    dc = torch.empty_like(c)
+    call("tag_clip_bce_backward", ptr(c), ptr(y), ptr(a), c.numel(), int(mode), float(c0), float(c1), float(c2),
+         ptr(_dloss(dloss)), ptr(dc))
+    return dc

@@ -222,6 +222,9 @@ _SIGS = {
     "tag_triplet_backward": (c_int, [P, c_int, c_int, c_double, P, P, P, P, P, P]),
     "tag_milnce_forward": (c_int, [P, P, c_int, c_int, c_double, P, P, P]),
     "tag_milnce_backward": (c_int, [P, P, c_int, c_int, c_double, P, P, P, P]),
+    "tag_clip_bce_ws_bytes": (c_size_t, [c_long]),
+    "tag_clip_bce_forward": (c_int, [P, P, P, c_long, c_int, c_double, c_double, c_double, P, P, P]),
+    "tag_clip_bce_backward": (c_int, [P, P, P, c_long, c_int, c_double, c_double, c_double, P, P, P]),
 }
 
 _lib = None

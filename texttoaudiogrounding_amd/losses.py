@@ -1,4 +1,5 @@
 """FrameBceLoss behind the reference interface (losses.py:11-35 in the reference)."""
+import math
 from typing import Dict
 
 import numpy as np
@@ -106,6 +107,118 @@ class MilNceLoss(nn.Module):
     def forward(self, output: Dict):
         clip_sim = output["clip_sim"]
         return torch.ops.tag.milnce(clip_sim, output["label"].to(clip_sim.device).float(), float(self.tau))
+
+
+def _clip_bce(output: Dict, mode, c0=0.0, c1=0.0, c2=0.0, aux=None):
+    clip_sim = output["clip_sim"]
+    label = output["label"].to(clip_sim.device).float()
+    return torch.ops.tag.clip_bce(clip_sim, label, aux, ops.CLIP_BCE_MODES[mode], float(c0), float(c1), float(c2))
+
+
+def _clip_counts(output: Dict):
+    """output["counts"] (B,N), numpy or tensor, as SamplePhrasesCountDataset fills it with neg_samp_stratg == "similarity"
+    (any other strategy leaves empty lists there)."""
+    counts, clip_sim = output["counts"], output["clip_sim"]
+    if not torch.is_tensor(counts):
+        counts = np.asarray(counts)
+    if tuple(counts.shape) != tuple(clip_sim.shape):
+        raise ValueError(f"counts {tuple(counts.shape)}: expected clip_sim's shape {tuple(clip_sim.shape)} (the dataset "
+                         f"fills counts only with neg_samp_stratg == 'similarity')")
+    return counts
+
+
+def _clip_aux(value, clip_sim):
+    """A host (or device) table formed by the reference's own expression -> fp32 (B,N) on clip_sim's device."""
+    return torch_ops.stage_to_device(torch.as_tensor(value).expand(clip_sim.shape), clip_sim.device, torch.float32)
+
+
+class FocalClipBceLoss(nn.Module):
+    """losses.py:59-72 in the reference: mean of -alpha (1-p)^gamma y ln p - (1-alpha) p^gamma (1-y) ln(1-p) over (B,N).
+    The logarithms are clamped at -100 and the derivative's denominators guarded as in binary_cross_entropy, so the loss and
+    its gradient are finite at clip_sim == 0 and == 1 (the reference is NaN/inf there)."""
+
+    def __init__(self, gamma=2, alpha=0.25) -> None:
+        super().__init__()
+        self.gamma = gamma
+        self.alpha = alpha
+
+    def forward(self, output: Dict):
+        return _clip_bce(output, "focal", self.gamma, self.alpha)
+
+
+class ClipBceLossFreqWeight(nn.Module):
+    """losses.py:75-87 in the reference: binary_cross_entropy weighted by (C / (C + counts))^gamma on the positives (label != 0)
+    and by 1 on the negatives.  The weight is formed by the reference's expression on whatever holds counts (fp64 on the host
+    for numpy) and cast to fp32; the where(label == 0, 1, .) is the kernel's."""
+
+    def __init__(self, C, gamma) -> None:
+        super().__init__()
+        self.C = C
+        self.gamma = gamma
+
+    def forward(self, output: Dict):
+        counts = _clip_counts(output)
+        weight = (self.C / (self.C + counts))**self.gamma
+        return _clip_bce(output, "freq_weight", aux=_clip_aux(weight, output["clip_sim"]))
+
+
+class SymmetricClipBceLoss(nn.Module):
+    """losses.py:90-104 in the reference: bce(clip_sim, label) + bce(clamp(label, eps, 1 - eps), clip_sim); a and b are stored
+    and unused, as there."""
+
+    def __init__(self, a=1, b=1, eps=1e-3) -> None:
+        super().__init__()
+        self.a = a
+        self.b = b
+        self.eps = eps
+
+    def forward(self, output: Dict):
+        return _clip_bce(output, "symmetric", self.eps)
+
+
+class OriginSymmetricClipBceLoss(nn.Module):
+    """losses.py:107-122 in the reference: a * bce(clip_sim, label) - b * A * mean(label (1 - clip_sim) + (1 - label) clip_sim),
+    A = ln eps."""
+
+    def __init__(self, a=1, b=1, eps=1e-3) -> None:
+        super().__init__()
+        self.a = a
+        self.b = b
+        self.A = math.log(eps)
+
+    def forward(self, output: Dict):
+        return _clip_bce(output, "origin_symmetric", self.a, self.b, self.A)
+
+
+class PriorAdjustedClipBceLoss(nn.Module):
+    """losses.py:125-143 in the reference: bce(q, label) with q = p pi^tau / (p pi^tau + (1 - p) (1 - pi)^tau) and the prior
+    pi = counts / data_size in (0,1), formed on whatever holds counts and cast to fp32.  data_size: a scalar or anything that
+    broadcasts against (B,N)."""
+
+    def __init__(self, data_size, tau=1) -> None:
+        super().__init__()
+        self.data_size = data_size
+        self.tau = tau
+
+    def forward(self, output: Dict):
+        counts = _clip_counts(output)
+        prior = counts / self.data_size
+        return _clip_bce(output, "prior_adjusted", self.tau, aux=_clip_aux(prior, output["clip_sim"]))
+
+
+class VectorQuantizeLoss(nn.Module):
+    """losses.py:213-223 in the reference: vq_weight * output["vq_loss"] + loss_fn(output)."""
+
+    def __init__(self, loss_fn, vq_weight=1.0):
+        super().__init__()
+        self.loss_fn = loss_fn
+        self.vq_weight = vq_weight
+
+    def forward(self, output):
+        return self.vq_weight * output["vq_loss"] + self.loss_fn(output)
+
+    def get_separate_loss(self, output):
+        return {"cls_loss": self.loss_fn(output), "vq_loss": output["vq_loss"]}
 
 
 class MultipleLossSum(nn.Module):

@@ -821,6 +821,47 @@ def _milnce_backward(ctx, dloss):
 register_autograd("tag::milnce", _milnce_backward, setup_context=_milnce_setup)
 
 
+# ------------------------------------------------------------------------------------------------ clip-level BCE objectives
+@custom_op("tag::clip_bce", mutates_args=())
+def clip_bce(clip_sim: Tensor, label: Tensor, aux: Optional[Tensor], mode: int, c0: float, c1: float, c2: float) -> Tensor:
+    """Focal (mode 0) / FreqWeight (1) / Symmetric (2) / OriginSymmetric (3) / PriorAdjusted (4) ClipBceLoss
+    (losses.py:59-143) on clip_sim / label (B,N) -> 0-dim loss.  aux (B,N): the weight of mode 1, the prior of mode 4
+    (ops.CLIP_BCE_MODES names the modes; include/tag_hip.h lists what c0, c1, c2 mean in each)."""
+    return ops.clip_bce_forward(clip_sim, label, aux, mode, c0, c1, c2)
+
+
+@clip_bce.register_fake
+def _(clip_sim, label, aux, mode, c0, c1, c2):
+    return clip_sim.new_empty(())
+
+
+@custom_op("tag::clip_bce_backward", mutates_args=())
+def clip_bce_backward(clip_sim: Tensor, label: Tensor, aux: Optional[Tensor], mode: int, c0: float, c1: float, c2: float,
+                      dloss: Tensor) -> Tensor:
+    return ops.clip_bce_backward(clip_sim, label, aux, mode, c0, c1, c2, dloss)
+
+
+@clip_bce_backward.register_fake
+def _(clip_sim, label, aux, mode, c0, c1, c2, dloss):
+    return clip_sim.new_empty(clip_sim.shape)
+
+
+def _clip_bce_setup(ctx, inputs, output):
+    clip_sim, label, aux, ctx.mode, ctx.c0, ctx.c1, ctx.c2 = inputs
+    ctx.has_aux = aux is not None
+    ctx.save_for_backward(clip_sim, label, *([aux] if ctx.has_aux else []))
+
+
+def _clip_bce_backward(ctx, dloss):
+    clip_sim, label = ctx.saved_tensors[:2]
+    aux = ctx.saved_tensors[2] if ctx.has_aux else None
+    dclip = torch.ops.tag.clip_bce_backward(clip_sim, label, aux, ctx.mode, ctx.c0, ctx.c1, ctx.c2, dloss)
+    return dclip, None, None, None, None, None, None
+
+
+register_autograd("tag::clip_bce", _clip_bce_backward, setup_context=_clip_bce_setup)
+
+
 # ------------------------------------------------------------------------------------------------ the fused audio encoders
 # ``tag::cnn8rnn_encoder`` / ``tag::crnn_encoder``: log-mel -> conv stack -> (fc1) -> BiGRU as ONE operator each (rows F1-F3,
 # A1-A4), what models/audio_encoder.py Cnn8Rnn.forward / CrnnEncoder.forward call -- the hot 97 % of the step goes through the
@@ -1032,4 +1073,5 @@ OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_r
             "segments", "cnn8rnn_encoder", "crnn_encoder",
             "cross_cnn8rnn", "cross_cdur", "tagging_head", "tagging_head_backward", "masked_frame_bce",
             "masked_frame_bce_backward", "text_gru", "text_gru_backward", "text_selfattn", "text_selfattn_backward", "infonce",
-            "infonce_backward", "triplet", "triplet_backward", "milnce", "milnce_backward", "text_intra", "text_intra_backward"]
+            "infonce_backward", "triplet", "triplet_backward", "milnce", "milnce_backward", "text_intra", "text_intra_backward",
+            "clip_bce", "clip_bce_backward"]
