@@ -253,12 +253,19 @@ int tag_bn_grad_from_partials(const float* bnpart, int P, int C, float* dgamma, 
 int tag_bnrelu_backward_apply(const float* y, const float* scale, const float* shift, const float* mean,
                               const float* invstd, const float* gamma, const float* da, float* dy,
                               const float* dgamma, const float* dbeta, long rows, int C, int bn_train, void* stream);
+/* Weight gradient (Cout,Cin,3,3); Cin % 4 == 0, Cout % 4 == 0, W <= 64, any H >= 1 and B >= 1 -- images of a few pixels included:
+ * where no all-taps form serves the width, a 32-pixel chunk of the per-tap kernel may hold pixels of three or more images (H W <
+ * 32 + W) and wraps its row index by a true modulo.  The workspace holds tag_conv3x3_wgrad_ws_bytes / (36 Cin Cout) partial
+ * gradients, each written whole, reduced in a fixed order: two calls give the same bits. */
 size_t tag_conv3x3_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout);
 int tag_conv3x3_wgrad(const float* x, int prologue, const float* in_scale, const float* in_shift,
                       const float* dy, float* dw, int B, int H, int W, int Cin, int Cout, void* ws,
                       void* stream);
 /* Cin == 1 (conv_block1.conv1): x (B,H,W) with optional per-column affine x*col_scale[w]+col_shift[w]
- * (bn0 folded: the BatchNorm2d(64) over the mel axis), w (Cout,1,3,3) */
+ * (bn0 folded: the BatchNorm2d(64) over the mel axis; applied BEFORE the zero padding), w (Cout,1,3,3).
+ * Every entry of the family wants B, H, W, Cout > 0 and Cout % 4 == 0 and both or neither of col_scale / col_shift; the weight
+ * gradient and dgrad also want Cout / 4 to divide 64 (Cout 4, 8, 16, 32, 64, 128, 256).  Anything else is TAG_EINVAL with the
+ * outputs untouched (Cout = 0 included: the checks come before any division by Cout / 4). */
 int tag_conv3x3_c1_forward(const float* x, const float* col_scale, const float* col_shift,
                            const float* w, float* y, int B, int H, int W, int Cout, void* stream);
 /* the same with the BatchNorm partial statistics of y written by the kernel (W == 64, Cout == 64: rows > 0):

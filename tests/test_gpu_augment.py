@@ -1,6 +1,8 @@
 """SpecAugment + mixup in the Cnn8Rnn training forward (csrc/augment.hip, ops.Cnn8RnnFunction, tag::cnn8rnn_encoder,
 models/augmentation.py): the kernels against a float64 restatement, the identity of zero-width stripes, parity with the reference
 fixtures (tests/golden/make_golden_specaug.py), the operator, the batch guard of the pairing heads and the benched size."""
+import gc
+
 import numpy as np
 import pytest
 import torch
@@ -339,6 +341,12 @@ def test_benched_size_steps(dev, mixup):
     b = O.synthetic_batch(64, 320000, seed=99, ragged=True)
     wave = b["waveform"].to(dev)
     lam = np.tile([0.3, 0.7], 32) if mixup else None
+    # Earlier tests leave device tensors in reference cycles (the BiEncoder that test_pairing_heads_refuse_mismatched_batches makes
+    # refuse stays alive through the traceback of its exception): the cyclic collector frees them whenever its counters say so, which
+    # may be in the middle of the steps measured here.  Collect them first, so that the figures below are the steps' own.
+    held = torch.cuda.memory_allocated()
+    gc.collect()
+    print(f"device memory held by garbage of earlier tests: {(held - torch.cuda.memory_allocated()) >> 20} MiB")
     mem = []
     for step in range(5):
         m.zero_grad(set_to_none=False)

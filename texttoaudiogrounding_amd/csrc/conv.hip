@@ -931,8 +931,11 @@ __global__ __launch_bounds__(256, TAG_NBUF == 2 ? 2 : 3) void conv3x3_wgrad_kern
             m = in_range ? m : (unsigned)(kend - 1);
             const int t = w0 + pixi[i];                               // < W + 32
             const int dh = W >= 32 ? (t >= W ? 1 : 0) : (int)(((unsigned)t * rW) >> 16);
-            int hh = h0 + dh;
-            hh = hh >= H ? hh - H : hh;                               // a chunk may run into the next image
+            // A chunk may run into the next image -- and, when W < 32 and H W < 32 + W, across SEVERAL image boundaries (3 x 5
+            // images: 32 pixels touch three of them), so the row wraps by a true modulo: h0 + dh < H + 33.  Where one subtraction
+            // was enough (h0 + dh < 2 H: every W >= 32, every image of 32 + W pixels or more) the modulo gives the same row, so
+            // masks, addresses and therefore every result bit are unchanged there.
+            int hh = (int)((unsigned)(h0 + dh) % (unsigned)H);
             hh += dyy;
             const int ww = t - dh * W + dxx;
             const unsigned aok = (unsigned)in_range & (unsigned)((unsigned)hh < (unsigned)H) &
@@ -2498,7 +2501,8 @@ extern "C" int tag_conv3x3_wgrad(const float* x, int prologue, const float* in_s
 static void c1_bwd_geom(int B, int H, int* strips, int* rows);
 extern "C" int tag_conv3x3_c1_forward(const float* x, const float* col_scale, const float* col_shift, const float* w,
                                       float* y, int B, int H, int W, int Cout, void* stream) {
-    TAG_CHECK_ARG(x && w && y && Cout % 4 == 0 && (col_scale == nullptr) == (col_shift == nullptr));
+    TAG_CHECK_ARG(x && w && y && B > 0 && H > 0 && W > 0 && Cout > 0);      // (Cout > 0 before 256 % (Cout / 4) below)
+    TAG_CHECK_ARG(Cout % 4 == 0 && (col_scale == nullptr) == (col_shift == nullptr));
     const long M = (long)B * H * W;
     long nb = (M * (Cout / 4) + 255) / 256;
     if (nb > 8192) nb = 8192;
@@ -2578,7 +2582,8 @@ extern "C" size_t tag_conv3x3_c1_wgrad_ws_bytes(int B, int H, int W, int Cout) {
 
 extern "C" int tag_conv3x3_c1_wgrad(const float* x, const float* col_scale, const float* col_shift, const float* dy,
                                     float* dw, int B, int H, int W, int Cout, void* ws, void* stream) {
-    TAG_CHECK_ARG(x && dy && dw && ws && Cout % 4 == 0 && Cout / 4 <= 64 && 64 % (Cout / 4) == 0);
+    TAG_CHECK_ARG(x && dy && dw && ws && B > 0 && H > 0 && W > 0 && Cout > 0);
+    TAG_CHECK_ARG(Cout % 4 == 0 && Cout / 4 <= 64 && 64 % (Cout / 4) == 0);
     TAG_CHECK_ARG((col_scale == nullptr) == (col_shift == nullptr));
     const long M = (long)B * H * W;
     const int rpi = 256 / (Cout / 4);
@@ -2600,7 +2605,8 @@ extern "C" int tag_conv3x3_c1_wgrad(const float* x, const float* col_scale, cons
 
 extern "C" int tag_conv3x3_c1_dgrad(const float* dy, const float* w, float* dx, int B, int H, int W, int Cout,
                                     void* stream) {
-    TAG_CHECK_ARG(dy && w && dx && Cout % 4 == 0 && Cout / 4 <= 64 && 64 % (Cout / 4) == 0);
+    TAG_CHECK_ARG(dy && w && dx && B > 0 && H > 0 && W > 0 && Cout > 0);
+    TAG_CHECK_ARG(Cout % 4 == 0 && Cout / 4 <= 64 && 64 % (Cout / 4) == 0);
     const long M = (long)B * H * W;
     const int rpi = 256 / (Cout / 4);
     long nb = (M + rpi - 1) / rpi;
