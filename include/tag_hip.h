@@ -524,6 +524,46 @@ int tag_convgru_gates_backward(const float* dxr, const float* x, const float* r,
                                void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * T6: the TRAINING path of the LAION-CLAP text tower: LaionClapEncoder, models/text_encoder.py:311-327 = Hugging Face
+ * ClapTextModel + ClapProjectionLayer (transformers models/clap/modeling_clap.py).  The dense layers are tag_gemm calls, the
+ * attention core is tag_text_selfattn_*; text_clap.hip holds the row kernels in between with their backward.  fp32, one wave
+ * per row, no atomics; sums over rows are per-wave partial rows (rows in a fixed stride) folded by tag_colsum and the table
+ * gradients are a first-occurrence gather like tag_embed_tokens_backward's: two runs are bit-identical.  1 <= D <= 1024, rows >= 1;
+ * anything else (and a null pointer that is not marked nullable) is TAG_EINVAL before any launch.  Rows need 4-byte alignment
+ * only; 16-byte accesses are used when D % 4 == 0 and every base is 16-byte aligned (same bits).
+ * resln_forward (ClapTextSelfOutput / ClapTextOutput: LayerNorm(dropout(dense(x)) + input)):
+ *   y = LayerNorm(x + res) * gamma + beta, res nullable; xhat (rows,D) and rstd (rows), both or neither: the normalised row
+ *   and 1 / sqrt(var + eps), what the backward reads (x-hat is never recovered by dividing by gamma).
+ * resln_backward: dy, xhat, rstd, gamma -> ds (rows,D) = the gradient of x AND of res; dgamma, dbeta (D) nullable (a frozen
+ *   LayerNorm); ws >= tag_text_clap_resln_backward_ws_bytes when either is asked for.
+ * embed_forward (ClapTextEmbeddings): tag_roberta_embed_ln's arithmetic -- position id = cumsum(ids != pad) * (ids != pad)
+ *   + pad, h = LayerNorm(word[ids] + type[0] + pos[position id]) -- and pos_ids (B*L) int64 (nullable), xhat, rstd as above.
+ *   P rows in the position table, P > L + pad_id; an id outside [0,V) reads nothing (tag_embed_check_ids raises the flag).
+ * embed_backward: dh (B*L,D) -> dword (V,D) and dpos (P,D), ACCUMULATED into caller-zeroed tables like
+ *   tag_embed_tokens_backward (repeated ids summed in a fixed order, the first occurrence owns the table row); pad tokens are
+ *   skipped, so row pad_id of both is not touched and stays exactly zero (nn.Embedding(padding_idx = pad_token_id) on both); dtype0 (D) = the column sum over ALL B*L rows; dgamma, dbeta.
+ *   Every output is nullable (at least one is asked for).  ws >= tag_text_clap_embed_backward_ws_bytes.
+ * gelu_forward (ClapTextIntermediate, ACT2FN["gelu"]): f = u Phi(u), Phi by erf; gelu_backward: du = df (Phi(u) + u phi(u)).
+ * tanh_backward (ClapTextPooler): dx = dy (1 - y^2).  Any n >= 1; out must not alias an input.
+ * ------------------------------------------------------------------------------------------- */
+int tag_text_clap_resln_forward(const float* x, const float* res /* nullable */, const float* gamma, const float* beta, float eps,
+                                float* y, float* xhat /* nullable */, float* rstd /* nullable */, long rows, int D, void* stream);
+size_t tag_text_clap_resln_backward_ws_bytes(long rows, int D);
+int tag_text_clap_resln_backward(const float* dy, const float* xhat, const float* rstd, const float* gamma, float* ds,
+                                 float* dgamma /* nullable */, float* dbeta /* nullable */, long rows, int D, void* ws,
+                                 void* stream);
+int tag_text_clap_embed_forward(const int64_t* ids, const float* word, const float* type0, const float* pos, const float* gamma,
+                                const float* beta, float eps, float* h, int64_t* pos_ids /* nullable */, float* xhat /* nullable */,
+                                float* rstd /* nullable */, int B, int L, int D, int V, int P, int pad_id, void* stream);
+size_t tag_text_clap_embed_backward_ws_bytes(int B, int L, int D);
+int tag_text_clap_embed_backward(const float* dh, const float* xhat, const float* rstd, const float* gamma, const int64_t* ids,
+                                 const int64_t* pos_ids, float* dword, float* dpos, float* dtype0, float* dgamma, float* dbeta,
+                                 int B, int L, int D, int V, int P, int pad_id, void* ws, void* stream);
+int tag_text_clap_gelu_forward(const float* u, float* f, long n, void* stream);
+int tag_text_clap_gelu_backward(const float* u, const float* df, float* du, long n, void* stream);
+int tag_text_clap_tanh_backward(const float* y, const float* dy, float* dx, long n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * T1 + T2: nn.Embedding gather + mean over valid tokens
  * models/text_encoder.py:39-43,79-88; models/utils.py:33-58.
  * text (B,L) int64, text_len (B) int64, table (V,D); token_emb (B,L,D) nullable; seq_emb (B,D).

@@ -1306,6 +1306,323 @@ def text_intra_backward(dtok, dseq, text_len, pe, saved, w_r, w_u, w_o, drop_p=0
 
 
 # ------------------------------------------------------------------------------------------------
+# LAION-CLAP text tower for training (row T6): the RoBERTa embedding block, per layer one packed q|k|v GEMM + the row-local
+# attention core of T4 + out-projection + residual LayerNorm + GELU feed-forward + residual LayerNorm, the tanh pooler and the
+# two-layer projection; row kernels of csrc/text_clap.hip, and its backward
+# ------------------------------------------------------------------------------------------------
+TEXT_CLAP_MAX_L = 64
+TEXT_CLAP_HEAD = ("embeddings.word_embeddings.weight", "embeddings.token_type_embeddings.weight",
+                  "embeddings.position_embeddings.weight", "embeddings.LayerNorm.weight", "embeddings.LayerNorm.bias")
+TEXT_CLAP_LAYER = ("attention.self.query.weight", "attention.self.query.bias", "attention.self.key.weight",
+                   "attention.self.key.bias", "attention.self.value.weight", "attention.self.value.bias",
+                   "attention.output.dense.weight", "attention.output.dense.bias", "attention.output.LayerNorm.weight",
+                   "attention.output.LayerNorm.bias", "intermediate.dense.weight", "intermediate.dense.bias", "output.dense.weight",
+                   "output.dense.bias", "output.LayerNorm.weight", "output.LayerNorm.bias")
+TEXT_CLAP_TAIL = ("model.pooler.dense.weight", "model.pooler.dense.bias", "projection.linear1.weight", "projection.linear1.bias",
+                  "projection.linear2.weight", "projection.linear2.bias")
+#: what the forward keeps per layer for the backward, in the order the operator returns it
+TEXT_CLAP_SAVED_LAYER = ("x", "qkv", "attn", "ctx", "xhat1", "rstd1", "h1", "u", "f", "xhat2", "rstd2")
+TEXT_CLAP_SAVED_HEAD = ("pos_ids", "klen", "xhat0", "rstd0", "buf", "t1", "seq_raw")
+
+
+def text_clap_param_names(layers):
+    """State-dict names of LaionClapEncoder's parameters in the order the operator takes them: 5 of the embedding block, 16 per
+    layer, the pooler and the two projection layers."""
+    return (["model." + n for n in TEXT_CLAP_HEAD]
+            + [f"model.encoder.layer.{l}.{n}" for l in range(layers) for n in TEXT_CLAP_LAYER] + list(TEXT_CLAP_TAIL))
+
+
+def text_clap_layers(n_params):
+    layers, rest = divmod(n_params - len(TEXT_CLAP_HEAD) - len(TEXT_CLAP_TAIL), len(TEXT_CLAP_LAYER))
+    if layers < 1 or rest:
+        raise ValueError(f"text_clap: {n_params} parameters are not 5 + 16 per layer (>= 1 layer) + 6")
+    return layers
+
+
+def text_clap_dropout_seeds(seed, layers):
+    """(seed behind the embedding LayerNorm, [(attention weights, behind attention.output.dense, behind output.dense)] per layer)
+    -- Hugging Face's four dropout sites -- from ONE operator seed: seed, then seed + 1 + 3 l + {0, 1, 2}, modulo 2^62."""
+    s = int(seed)
+    return s % (2 ** 62), [tuple((s + 1 + 3 * l + k) % (2 ** 62) for k in range(3)) for l in range(layers)]
+
+
+def text_clap_check(D, heads, L=None):
+    """The domain of the tower's kernels, raised before any launch with the limit named."""
+    text_selfattn_check(D, heads)
+    if L is not None and not 2 <= L <= TEXT_CLAP_MAX_L:
+        raise ValueError(f"text_clap: {L} tokens per phrase; the attention kernel serves 2 ... {TEXT_CLAP_MAX_L} tokens and there is "
+                         "no eager fallback")
+
+
+def text_clap_resln_forward(x, res, gamma, beta, eps, need_state=True, out=None):
+    """y = LayerNorm(x + res) gamma + beta over the rows of x (M, D), res (M, D) or None -> y, xhat (M, D), rstd (M) (None unless
+    need_state).  out: a (M, D) destination for y."""
+    x = _chk(x, "x")
+    M, D = x.shape
+    res = _chk(res, "res") if res is not None else None
+    y = out if out is not None else _empty(M, D, like=x)
+    xhat = _empty(M, D, like=x) if need_state else None
+    rstd = _empty(M, like=x) if need_state else None
+    call("tag_text_clap_resln_forward", ptr(x), ptr(res), ptr(_chk(gamma, "gamma")), ptr(_chk(beta, "beta")), float(eps), ptr(y),
+         ptr(xhat), ptr(rstd), M, D)
+    return y, xhat, rstd
+
+
+def text_clap_resln_backward(dy, xhat, rstd, gamma, need_dgamma=True, need_dbeta=True, dgamma_out=None, dbeta_out=None):
+    """-> ds (M, D) (the gradient of x AND of res), dgamma, dbeta (D) (None when not needed; written into *_out when given)."""
+    dy, xhat = _chk(dy, "grad"), _chk(xhat, "xhat")
+    M, D = xhat.shape
+    ds = _empty(M, D, like=dy)
+    dg = (dgamma_out if dgamma_out is not None else _empty(D, like=dy)) if need_dgamma else None
+    db = (dbeta_out if dbeta_out is not None else _empty(D, like=dy)) if need_dbeta else None
+    ws = _ws(query("tag_text_clap_resln_backward_ws_bytes", M, D), dy) if (need_dgamma or need_dbeta) else None
+    call("tag_text_clap_resln_backward", ptr(dy), ptr(xhat), ptr(_chk(rstd, "rstd")), ptr(_chk(gamma, "gamma")), ptr(ds), ptr(dg),
+         ptr(db), M, D, ptr(ws))
+    return ds, dg, db
+
+
+def _clap_ids_chk(ids, what):
+    if not ids.is_cuda or ids.dtype != torch.long:
+        raise RuntimeError(f"text_clap: {what} must be an int64 tensor on the device (no CPU fallback)")
+    return ids.contiguous()
+
+
+def text_clap_embed_forward(ids, word, type0, pos, gamma, beta, eps, pad_id, need_state=True):
+    """ClapTextEmbeddings: ids (B, L) int64 -> h (B*L, D) = LayerNorm(word[ids] + type0 + pos[position ids]), the position ids
+    (B*L) int64, xhat (B*L, D), rstd (B*L) (the last three None unless need_state)."""
+    ids = _clap_ids_chk(ids, "input_ids")
+    B, L = ids.shape
+    word, pos = _chk(word, "word_embeddings"), _chk(pos, "position_embeddings")
+    V, D = word.shape
+    M = B * L
+    h = _empty(M, D, like=word)
+    pos_ids = torch.empty(M, device=ids.device, dtype=torch.long) if need_state else None
+    xhat = _empty(M, D, like=word) if need_state else None
+    rstd = _empty(M, like=word) if need_state else None
+    call("tag_embed_check_ids", ptr(ids), M, V, ptr(_embed_flag(word)))       # nn.Embedding raises; see check_async_errors
+    call("tag_text_clap_embed_forward", ptr(ids), ptr(word), ptr(_chk(type0, "token_type_embeddings")), ptr(pos),
+         ptr(_chk(gamma, "gamma")), ptr(_chk(beta, "beta")), float(eps), ptr(h), ptr(pos_ids), ptr(xhat), ptr(rstd), B, L, D, V,
+         pos.shape[0], int(pad_id))
+    return h, pos_ids, xhat, rstd
+
+
+def text_clap_embed_backward(dh, xhat, rstd, gamma, ids, pos_ids, V, P, pad_id, need=None, outs=None):
+    """dh (B*L, D) -> [dword (V, D), dtype0 (1, D), dpos (P, D), dgamma (D), dbeta (D)] (None where need[i] is False).  outs:
+    optional destination per gradient; the two table destinations must be ZEROED (the flat-gradient rows after zero_grad): the
+    gather accumulates.  Row pad_id of dword and dpos receives exactly zero."""
+    dh = _chk(dh, "grad")
+    ids, pos_ids = _clap_ids_chk(ids, "input_ids"), _clap_ids_chk(pos_ids, "position ids")
+    B, L = ids.shape
+    D = dh.shape[-1]
+    need = list(need) if need is not None else [True] * 5
+    outs = list(outs) if outs is not None else [None] * 5
+    if not any(need):
+        return [None] * 5
+    shapes = ((V, D), (1, D), (P, D), (D,), (D,))
+    g = [None] * 5
+    for i in range(5):
+        if need[i]:
+            g[i] = outs[i] if outs[i] is not None else (torch.zeros if i in (0, 2) else torch.empty)(
+                shapes[i], device=dh.device, dtype=F32)
+    ws = _ws(query("tag_text_clap_embed_backward_ws_bytes", B, L, D), dh)
+    call("tag_text_clap_embed_backward", ptr(dh), ptr(_chk(xhat, "xhat")), ptr(_chk(rstd, "rstd")), ptr(_chk(gamma, "gamma")),
+         ptr(ids), ptr(pos_ids), ptr(g[0]), ptr(g[2]), ptr(g[1]), ptr(g[3]), ptr(g[4]), B, L, D, V, P, int(pad_id), ptr(ws))
+    return g
+
+
+def text_clap_gelu_forward(u):
+    f = torch.empty_like(_chk(u, "u"))
+    call("tag_text_clap_gelu_forward", ptr(u), ptr(f), u.numel())
+    return f
+
+
+def text_clap_gelu_backward(u, df):
+    """du = df (Phi(u) + u phi(u)) on the saved pre-activation u."""
+    du = torch.empty_like(_chk(u, "u"))
+    call("tag_text_clap_gelu_backward", ptr(u), ptr(_chk(df, "grad")), ptr(du), u.numel())
+    return du
+
+
+def text_clap_tanh_backward(y, dy):
+    """dx = dy (1 - y^2); y, dy any contiguous views of the same size."""
+    if not (y.is_contiguous() and dy.is_contiguous()):
+        raise RuntimeError("text_clap_tanh_backward: contiguous tensors expected")
+    dx = torch.empty_like(_chk(y, "y"))
+    call("tag_text_clap_tanh_backward", ptr(y), ptr(_chk(dy, "grad")), ptr(dx), y.numel())
+    return dx
+
+
+def text_clap_l2norm_backward(x, du):
+    """Gradient of F.normalize over the rows of x (R, P)."""
+    x, du = _chk(x, "x"), _chk(du, "grad")
+    dx = torch.empty_like(x)
+    call("tag_l2norm_rows_backward", ptr(x), ptr(du), ptr(dx), x.shape[0], x.shape[1])
+    return dx
+
+
+def _clap_dropout(x2d, p, seed, backward=False):
+    return text_gru_dropout(x2d, p, seed, backward) if p > 0.0 else x2d
+
+
+def text_clap_forward(ids, mask, params, heads, eps, pad_id, need_grad, p_hidden=0.0, p_attn=0.0, seed=0):
+    """LaionClapEncoder.forward (models/text_encoder.py:320-327) over Hugging Face's ClapTextModel + ClapProjectionLayer:
+    ids, mask (R, L) int64 on the device, mask a right-padded prefix (only its row sums are read: klen = mask.sum(-1), a row
+    without a valid key attends position 0 -- the clamp of the attention core); params in the order of text_clap_param_names.
+    p_hidden / p_attn > 0 (train): Hugging Face's dropouts behind the embedding LayerNorm, on the attention weights, behind
+    attention.output.dense and behind output.dense, keep masks of text_clap_dropout_seeds(seed, layers) over the flat index of
+    (R*L, D) / (R, H, L, L).  -> token_emb (R, L, P), seq_emb (R, P) L2-normalised, saved state or None."""
+    ids, mask = _clap_ids_chk(ids, "input_ids"), _clap_ids_chk(mask, "attention_mask")
+    R, L = ids.shape
+    layers = text_clap_layers(len(params))
+    params = [_chk(p, "parameter") for p in params]
+    word, type0, pos, g0, b0 = params[:5]
+    D = word.shape[1]
+    text_clap_check(D, heads, L)
+    if pos.shape[0] <= L + pad_id:
+        raise ValueError(f"text_clap: the position table has {pos.shape[0]} rows; {L} tokens need {L + pad_id + 1}")
+    M = R * L
+    klen = mask.sum(-1)
+    s_emb, s_layers = text_clap_dropout_seeds(seed, layers)
+    h, pos_ids, xhat0, rstd0 = text_clap_embed_forward(ids, word, type0, pos, g0, b0, eps, pad_id, need_grad)
+    h = _clap_dropout(h, p_hidden, s_emb)
+    buf = h.new_empty(M + R, D)                       # the last layer's rows, then the pooled rows: ONE projection over both
+    saved = []
+    for l in range(layers):
+        b = 5 + 16 * l
+        qw, qb, kw, kb, vw, vb, aow, aob, g1, b1, iw, ib, ow, ob, g2, b2 = params[b:b + 16]
+        s_attn, s_ao, s_out = s_layers[l]
+        I = iw.shape[0]
+        wqkv, bqkv = torch.cat((qw, kw, vw), 0), torch.cat((qb, kb, vb), 0)
+        qkv = gemm(h, wqkv, M, 3 * D, D, transB=True, bias=bqkv)
+        ctx, attn = text_selfattn_core(qkv.view(R, L, 3 * D), klen, heads, need_grad, p_attn, s_attn)
+        ctx = ctx.view(M, D)
+        a = _clap_dropout(gemm(ctx, aow, M, D, D, transB=True, bias=aob), p_hidden, s_ao)
+        h1, xhat1, rstd1 = text_clap_resln_forward(a, h, g1, b1, eps, need_grad)
+        u = gemm(h1, iw, M, I, D, transB=True, bias=ib)      # no fused activation: the backward reads the pre-activation
+        f = text_clap_gelu_forward(u)
+        f2 = _clap_dropout(gemm(f, ow, M, D, I, transB=True, bias=ob), p_hidden, s_out)
+        hn, xhat2, rstd2 = text_clap_resln_forward(f2, h1, g2, b2, eps, need_grad, out=buf[:M] if l == layers - 1 else None)
+        if need_grad:
+            saved.append(dict(x=h, qkv=qkv, attn=attn, ctx=ctx, xhat1=xhat1, rstd1=rstd1, h1=h1, u=u, f=f, xhat2=xhat2, rstd2=rstd2,
+                              wqkv=wqkv))
+        h = hn
+    pw, pb, w1, c1, w2, c2 = params[-6:]
+    P = w1.shape[0]
+    gemm(buf, pw, R, D, D, transB=True, lda=L * D, bias=pb, act=4, out=buf[M:])         # tanh(dense(h[:, 0]))
+    t1 = gemm(buf, w1, M + R, P, D, transB=True, bias=c1, act=1)
+    t2 = gemm(t1, w2, M + R, P, P, transB=True, bias=c2)
+    seq_raw = t2[M:]
+    seq = _l2norm_rows(seq_raw, R, P)
+    state = dict(pos_ids=pos_ids, klen=klen, xhat0=xhat0, rstd0=rstd0, buf=buf, t1=t1, seq_raw=seq_raw, layers=saved) \
+        if need_grad else None
+    return t2[:M].view(R, L, P), seq, state
+
+
+def text_clap_backward(dtok, dseq, ids, saved, params, heads, pad_id, p_hidden=0.0, p_attn=0.0, seed=0, outs=None, need=None):
+    """-> one gradient per parameter (text_clap_param_names order).  dtok (R, L, P) / dseq (R, P): either may be None.  outs:
+    optional destination per parameter (flat-gradient views), written directly -- the two embedding tables' must be zeroed, the
+    gather accumulates; need: per parameter, False skips its GEMM / column sum (a frozen parameter) and leaves None.  The walk
+    stops below the lowest parameter that needs a gradient.  The q / k / v weights are used packed; their gradients go to the
+    three parameters separately."""
+    n = len(params)
+    layers = text_clap_layers(n)
+    params = [_chk(p, "parameter") for p in params]
+    outs = list(outs) if outs is not None else [None] * n
+    need = list(need) if need is not None else [True] * n
+    g = [None] * n
+    if not any(need):
+        return g
+    R, L = ids.shape
+    M = R * L
+    D = params[0].shape[1]
+    pw, _, w1, _, w2, _ = params[-6:]
+    P = w1.shape[0]
+    buf, t1 = saved["buf"], saved["t1"]
+    s_emb, s_layers = text_clap_dropout_seeds(seed, layers)
+
+    def below(i):                                   # does anything at an index < i need a gradient?
+        return any(need[:i])
+
+    dt2 = buf.new_zeros(M + R, P) if (dtok is None or dseq is None) else buf.new_empty(M + R, P)
+    if dtok is not None:
+        dt2[:M].copy_(_chk(dtok, "grad").view(M, P))
+    if dseq is not None:
+        dt2[M:].copy_(text_clap_l2norm_backward(saved["seq_raw"], dseq))
+    if need[n - 2]:
+        g[n - 2] = gemm(dt2, t1, P, P, M + R, transA=True, lda=P, out=outs[n - 2])
+    if need[n - 1]:
+        g[n - 1] = colsum(dt2, M + R, P, out=outs[n - 1])
+    if not below(n - 2):
+        return g
+    dt1 = relu_backward(t1, gemm(dt2, w2, M + R, P, P))
+    if need[n - 4]:
+        g[n - 4] = gemm(dt1, buf, P, D, M + R, transA=True, lda=P, out=outs[n - 4])
+    if need[n - 3]:
+        g[n - 3] = colsum(dt1, M + R, P, out=outs[n - 3])
+    if not below(n - 4):
+        return g
+    dbuf = gemm(dt1, w1, M + R, D, P)
+    dpre = text_clap_tanh_backward(buf[M:], dbuf[M:])
+    if need[n - 6]:
+        g[n - 6] = gemm(dpre, buf, D, D, R, transA=True, lda=D, ldb=L * D, out=outs[n - 6])
+    if need[n - 5]:
+        g[n - 5] = colsum(dpre, R, D, out=outs[n - 5])
+    if not below(n - 6):
+        return g
+    gemm(dpre, pw, R, D, D, out=dbuf, ldc=L * D, accumulate=True)                       # into the rows h[:, 0]
+    dh = dbuf[:M]
+    for l in range(layers - 1, -1, -1):
+        b = 5 + 16 * l
+        sv = saved["layers"][l]
+        _, _, _, _, _, _, aow, _, g1, _, iw, _, ow, _, g2, _ = params[b:b + 16]
+        s_attn, s_ao, s_out = s_layers[l]
+        I = iw.shape[0]
+        ds2, g[b + 14], g[b + 15] = text_clap_resln_backward(dh, sv["xhat2"], sv["rstd2"], g2, need[b + 14], need[b + 15],
+                                                             outs[b + 14], outs[b + 15])
+        df2 = _clap_dropout(ds2, p_hidden, s_out, backward=True)
+        if need[b + 12]:
+            g[b + 12] = gemm(df2, sv["f"], D, I, M, transA=True, lda=D, out=outs[b + 12])
+        if need[b + 13]:
+            g[b + 13] = colsum(df2, M, D, out=outs[b + 13])
+        if not below(b + 12):
+            return g
+        du = text_clap_gelu_backward(sv["u"], gemm(df2, ow, M, I, D))
+        if need[b + 10]:
+            g[b + 10] = gemm(du, sv["h1"], I, D, M, transA=True, lda=I, out=outs[b + 10])
+        if need[b + 11]:
+            g[b + 11] = colsum(du, M, I, out=outs[b + 11])
+        if not below(b + 10):
+            return g
+        dh1 = gemm(du, iw, M, D, I, out=ds2, accumulate=True)                           # + the residual branch (df2 is spent)
+        ds1, g[b + 8], g[b + 9] = text_clap_resln_backward(dh1, sv["xhat1"], sv["rstd1"], g1, need[b + 8], need[b + 9],
+                                                           outs[b + 8], outs[b + 9])
+        if not below(b + 8):
+            return g
+        da = _clap_dropout(ds1, p_hidden, s_ao, backward=True)
+        if need[b + 6]:
+            g[b + 6] = gemm(da, sv["ctx"], D, D, M, transA=True, lda=D, out=outs[b + 6])
+        if need[b + 7]:
+            g[b + 7] = colsum(da, M, D, out=outs[b + 7])
+        if not below(b + 6):
+            return g
+        dctx = gemm(da, aow, M, D, D)
+        dqkv = text_selfattn_core_backward(sv["qkv"].view(R, L, 3 * D), sv["attn"], dctx.view(R, L, D), saved["klen"], heads,
+                                           p_attn, s_attn).view(M, 3 * D)
+        for j in range(3):
+            if need[b + 2 * j]:
+                g[b + 2 * j] = gemm(dqkv[:, j * D:], sv["x"], D, D, M, transA=True, lda=3 * D, out=outs[b + 2 * j])
+            if need[b + 2 * j + 1]:
+                g[b + 2 * j + 1] = colsum(dqkv[:, j * D:], M, D, ld=3 * D, out=outs[b + 2 * j + 1])
+        if not below(b):
+            return g
+        dh = gemm(dqkv, sv["wqkv"], M, D, 3 * D, out=ds1, accumulate=True)              # + the residual branch (da is spent)
+    dh0 = _clap_dropout(dh, p_hidden, s_emb, backward=True)
+    g[:5] = text_clap_embed_backward(dh0, saved["xhat0"], saved["rstd0"], params[3], ids, saved["pos_ids"], params[0].shape[0],
+                                     params[2].shape[0], pad_id, need[:5], outs[:5])
+    return g
+
+
+# ------------------------------------------------------------------------------------------------
 # One conv3x3 -> BatchNorm -> ReLU (-> pool) stage as a standalone operator: what SURVEY.md section 8(b) lists as
 # ``conv3x3_bn_relu[_pool]`` and what ConvBlock.forward (models/panns.py:46-62) is made of.  The fused Cnn8Rnn node (functions.py)
 # never materialises relu(bn(y)); this stage does (its output IS that tensor, pooled), so that it composes like an nn.Module.

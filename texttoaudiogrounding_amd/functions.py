@@ -35,6 +35,7 @@ from .dispatch import (bias_bnrelu_backward, bias_bnrelu_forward, bias_bnrelu_po
 from .dispatch import class_pool_forward, tagging_head_dlogit
 from .dispatch import text_gru_backward, text_gru_forward
 from .dispatch import text_selfattn_backward, text_selfattn_forward
+from .dispatch import text_clap_backward, text_clap_forward
 from .dispatch import text_intra_backward, text_intra_forward
 from . import engine
 
@@ -967,6 +968,46 @@ class TextIntraFunction(TagFunction):
                 _deliver(grads, sk, i, g[i])
         _ready(ctx.params)
         return (dx, None, None, None, None, None, *grads)
+
+
+class TextClapFunction(TagFunction):
+    """torch.ops.tag.text_clap with direct gradients (StrongRunner / WeakPhraseRunner): LaionClapEncoder
+    (models/text_encoder.py:311-327) whose parameter gradients go straight into their flat-gradient views -- the two embedding
+    tables' rows are accumulated into the zeroed flat buffer, like EmbedMeanFunction's; a parameter with requires_grad = False
+    costs no GEMM / column sum, its flat-gradient rows are not touched and the walk stops below the lowest trainable parameter.
+    With nothing to differentiate (a frozen tower, eval, no_grad) nothing is saved.  Same kernels as the operator."""
+
+    N_ARGS = 8                                          # arguments in front of the parameters
+
+    @staticmethod
+    def forward(ctx, input_ids, attention_mask, heads, eps, pad_id, p_hidden, p_attn, seed, *params):
+        need = engine._RECORDING and any(ctx.needs_input_grad)
+        tok, seq, saved = text_clap_forward(input_ids, attention_mask, [p.detach() for p in params], heads, eps, pad_id, need,
+                                            p_hidden, p_attn, seed)
+        ctx.tc = (saved, input_ids, heads, pad_id, p_hidden, p_attn, seed)
+        ctx.weights = [p.detach() for p in params] if need else None
+        ctx.shapes = [tuple(p.shape) for p in params]
+        ctx.sinks = _sinks(list(params))
+        ctx.params = list(params) if cfg.DIRECT_GRADS else None
+        ctx.set_materialize_grads(False)
+        return tok, seq
+
+    @staticmethod
+    def backward(ctx, dtok, dseq):
+        saved, input_ids, heads, pad_id, p_hidden, p_attn, seed = ctx.tc
+        k = TextClapFunction.N_ARGS
+        sk, need = ctx.sinks, list(ctx.needs_input_grad[k:])
+        n = len(need)
+        if (dtok is None and dseq is None) or saved is None:
+            return (None,) * (k + n)
+        g = text_clap_backward(dtok, dseq, input_ids, saved, ctx.weights, heads, pad_id, p_hidden, p_attn, seed,
+                               outs=[sk[i] for i in range(n)], need=need)
+        grads = [None] * n
+        for i in range(n):
+            if need[i]:
+                _deliver(grads, sk, i, g[i] if sk[i] is not None else g[i].view(ctx.shapes[i]))
+        _ready(ctx.params)
+        return (*([None] * k), *grads)
 
 
 class Seq2SeqAttentionFunction(TagFunction):

@@ -137,6 +137,15 @@ _SIGS = {
     "tag_convgru_update_forward": (c_int, [P] * 6 + [c_int] * 3 + [P]),
     "tag_convgru_update_backward": (c_int, [P] * 9 + [c_int] * 3 + [P]),
     "tag_convgru_gates_backward": (c_int, [P] * 5 + [c_long, c_int, P]),
+    "tag_text_clap_resln_forward": (c_int, [P] * 4 + [c_float] + [P] * 3 + [c_long, c_int, P]),
+    "tag_text_clap_resln_backward_ws_bytes": (c_size_t, [c_long, c_int]),
+    "tag_text_clap_resln_backward": (c_int, [P] * 7 + [c_long, c_int, P, P]),
+    "tag_text_clap_embed_forward": (c_int, [P] * 6 + [c_float] + [P] * 4 + [c_int] * 6 + [P]),
+    "tag_text_clap_embed_backward_ws_bytes": (c_size_t, [c_int] * 3),
+    "tag_text_clap_embed_backward": (c_int, [P] * 11 + [c_int] * 6 + [P, P]),
+    "tag_text_clap_gelu_forward": (c_int, [P, P, c_long, P]),
+    "tag_text_clap_gelu_backward": (c_int, [P, P, P, c_long, P]),
+    "tag_text_clap_tanh_backward": (c_int, [P, P, P, c_long, P]),
     "tag_embed_mean_forward": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_mean_backward": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_check_ids": (c_int, [P, c_long, c_int, P, P]),

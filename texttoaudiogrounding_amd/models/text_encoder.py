@@ -1,5 +1,6 @@
 """Learned text encoders: the word-embedding bag EmbeddingAgg, the recurrent RnnEncoder, the IntraAttention encoder with its
-ConvGRUCell and the SelfAttention encoder (mirror of models/text_encoder.py:14-43,61-268 in the reference)."""
+ConvGRUCell, the SelfAttention encoder and the trainable LAION-CLAP tower LaionClapEncoder (mirror of
+models/text_encoder.py:14-43,61-268,311-327 in the reference)."""
 import math
 from typing import Dict
 
@@ -334,3 +335,121 @@ class SelfAttention(nn.Module):
         else:
             out, _ = torch.ops.tag.text_selfattn(x, text_len, pe, params, mha.num_heads, p, seed)
         return {"token_emb": out[:, 1:].contiguous().view(*lead, L, E), "seq_emb": out[:, 0].contiguous().view(*lead, E)}
+
+
+class LaionClapEncoder(nn.Module):
+    """models/text_encoder.py:311-327: the text tower of LAION-CLAP -- Hugging Face ``ClapTextModel`` (a RoBERTa-style
+    post-LayerNorm encoder) as ``self.model`` and ``ClapProjectionLayer`` as ``self.projection`` -- TRAINABLE:
+    ``forward(input_dict)`` reads ``input_ids`` / ``attention_mask`` (what ``datasets.text_tokenizer.HuggingFaceTokenizer``
+    returns), of shape (R, L) or with any leading shape (flattened like the other text encoders), and returns
+    ``token_emb`` = projection(last_hidden_state) (..., L, P) and ``seq_emb`` = normalize(projection(pooler_output)) (..., P).
+
+    ``model`` and ``projection`` only HOLD the parameters, under Hugging Face's names (state-dict keys ``model.embeddings...``,
+    ``model.encoder.layer.N...``, ``model.pooler.dense...``, ``projection.linear1 / linear2...``: a ``ClapModel`` checkpoint's
+    ``text_model`` / ``text_projection`` load with ``load_state_dict``; the ``position_ids`` / ``token_type_ids`` index buffers
+    are optional there).  The arithmetic runs in ``torch.ops.tag.text_clap``: dense layers on tag_gemm, the attention core of
+    csrc/text_attn.hip, the row kernels of csrc/text_clap.hip.  ``models.hf_modeling_grounding.LaionClapEncoder`` stays the
+    forward-only inference class.
+
+    ``model_type``: a directory or a name that resolves WITHOUT the network (``local_files_only=True``) -- its weights and
+    configuration are copied; otherwise the tower is built from ``CLAP_TEXT_DEFAULTS`` (RoBERTa-base + a 512-d projection)
+    updated by ``config``, randomly initialised.  ``embed_dim`` = ``projection_dim``.
+
+    Limits (ValueError before any launch, there is no eager fallback): 2 <= L <= 64 tokens; head_dim 16, 32 or a multiple of 64;
+    hidden_size <= 1024.  ``attention_mask`` must be a right-padded PREFIX (ones, then zeros: what a tokenizer with
+    ``padding=True`` returns): only its row sums reach the kernel.  A host-resident mask that is not a prefix raises ValueError; a
+    device-resident one is NOT read back -- it is trusted.  A row with no valid key attends position 0 only (the attention
+    core's clamp) instead of producing NaN.  Padded positions produce ``token_emb`` like any other query, as in Hugging Face.
+
+    Dropout (train mode): Hugging Face's four sites -- behind the embedding LayerNorm, on the attention weights, behind
+    ``attention.output.dense`` and behind ``output.dense`` -- at ``hidden_dropout_prob`` / ``attention_probs_dropout_prob`` of the
+    configuration (0.1 both, ClapTextConfig's default), with the project's counter-based keep masks (``tag_dropout_mask``; seeds
+    ops.text_clap_dropout_seeds(ops.new_seed(), layers), drawn from torch's global generator and decorrelated per rank by
+    ops.SEED_RANK): the same rule as nn.Dropout's, not torch's random stream.  With nothing to differentiate
+    (``freeze_text_encoder``, eval, ``no_grad``) nothing is saved for a backward pass."""
+
+    MAX_TOKENS = ops.TEXT_CLAP_MAX_L
+
+    def __init__(self, model_type: str = None, config: dict = None):
+        super().__init__()
+        from .hf_modeling_grounding import CLAP_TEXT_DEFAULTS, _Holder, _text_model
+        cfg = dict(CLAP_TEXT_DEFAULTS, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1)
+        pretrained = self._local_pretrained(model_type)
+        if pretrained is not None:
+            cfg.update(pretrained[0])
+        else:
+            cfg.update(config or {})
+        ops.text_clap_check(cfg["hidden_size"], cfg["num_attention_heads"])
+        if cfg["num_hidden_layers"] < 1:
+            raise ValueError("LaionClapEncoder: num_hidden_layers must be >= 1")
+        self.config = cfg
+        self.model_type = model_type
+        self.model = _text_model(cfg)
+        self.projection = _Holder()
+        self.projection.linear1 = nn.Linear(cfg["hidden_size"], cfg["projection_dim"])
+        self.projection.linear2 = nn.Linear(cfg["projection_dim"], cfg["projection_dim"])
+        self.embed_dim = cfg["projection_dim"]
+        self._names = ops.text_clap_param_names(cfg["num_hidden_layers"])
+        if pretrained is not None:
+            self.load_state_dict(pretrained[1], strict=True)
+
+    @staticmethod
+    def _local_pretrained(model_type):
+        """(configuration entries, state dict) of a ``ClapModel`` that resolves locally, else None.  Never touches the network."""
+        if not model_type:
+            return None
+        try:
+            from transformers import ClapModel
+            clap = ClapModel.from_pretrained(model_type, local_files_only=True)
+        except Exception:                                   # noqa: BLE001 - not cached / no such directory / no transformers
+            return None
+        tc = clap.config.text_config
+        keys = ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "max_position_embeddings",
+                "layer_norm_eps", "pad_token_id", "hidden_dropout_prob", "attention_probs_dropout_prob")
+        cfg = {k: getattr(tc, k) for k in keys}
+        cfg["projection_dim"] = clap.config.projection_dim
+        st = {"model." + k: v for k, v in clap.text_model.state_dict().items()}
+        st.update({"projection." + k: v for k, v in clap.text_projection.state_dict().items()})
+        return cfg, st
+
+    def load_state_dict(self, state_dict, *a, **k):
+        state_dict = dict(state_dict)
+        for name in ("model.embeddings.position_ids", "model.embeddings.token_type_ids"):       # optional in checkpoints
+            state_dict.setdefault(name, self.state_dict()[name])
+        return super().load_state_dict(state_dict, *a, **k)
+
+    def _params(self):
+        own = dict(self.named_parameters())
+        return [own[n] for n in self._names]
+
+    def forward(self, input_dict: Dict):
+        ids, mask = input_dict["input_ids"], input_dict["attention_mask"]
+        shape = tuple(np.shape(ids))
+        L = shape[-1]
+        if not 2 <= L <= self.MAX_TOKENS:                   # before any launch
+            raise ValueError(f"LaionClapEncoder: {L} tokens per phrase; the attention kernel serves 2 ... {self.MAX_TOKENS} tokens "
+                             "and there is no eager fallback")
+        if tuple(np.shape(mask)) != shape:
+            raise ValueError(f"LaionClapEncoder: input_ids {shape} and attention_mask {tuple(np.shape(mask))} differ in shape")
+        mask = torch.as_tensor(mask)
+        if not mask.is_cuda:
+            m = mask.reshape(-1, L) != 0
+            if bool((m[:, 1:] & ~m[:, :-1]).any()):
+                raise ValueError("LaionClapEncoder: attention_mask must be a right-padded prefix (ones, then zeros); the attention "
+                                 "kernel reads only the number of valid keys per row")
+        cfg = self.config
+        table = self.model.embeddings.word_embeddings.weight
+        ids = _ids_to_device(ids, table).reshape(-1, L)
+        mask = mask.long().to(table.device).reshape(-1, L).contiguous()
+        params = self._params()
+        p_h = float(cfg["hidden_dropout_prob"]) if self.training else 0.0
+        p_a = float(cfg["attention_probs_dropout_prob"]) if self.training else 0.0
+        seed = ops.new_seed() if (p_h > 0.0 or p_a > 0.0) else 0
+        heads, eps, pad = int(cfg["num_attention_heads"]), float(cfg["layer_norm_eps"]), int(cfg["pad_token_id"])
+        if ops.DIRECT_GRADS:
+            tok, seq = ops.TextClapFunction.apply(ids, mask, heads, eps, pad, p_h, p_a, seed, *params)
+        else:
+            need = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+            tok, seq, _ = torch.ops.tag.text_clap(ids, mask, params, heads, eps, pad, p_h, p_a, seed, need)
+        lead = shape[:-1]
+        return {"seq_emb": seq.view(*lead, seq.shape[-1]), "token_emb": tok.view(*lead, L, tok.shape[-1])}

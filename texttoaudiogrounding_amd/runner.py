@@ -18,6 +18,10 @@ from . import ops
 from .losses import ClipBceLoss, ClipMaskedFrameBceLoss, FrameBceLoss, MaxMarginRankingLoss
 from .utils.train_util import init_obj_from_str
 
+#: batch entries that hold token ids or masks (DictTokenizer's ``text``, HuggingFaceTokenizer's ``input_ids`` / ``attention_mask``):
+#: staged as int64; every other tensor is cast to fp32
+_INT64_KEYS = ("text", "input_ids", "attention_mask")
+
 
 def build_model(model_cfg: Dict):
     """get_model of run_strong.py:71-89 (run_weak_sentence.py adds ``sim_pooling``): instantiate sub-modules first, then the
@@ -269,7 +273,7 @@ class StrongRunner:
                     v = (v.pin_memory() if self.device.type == "cuda" else v).to(self.device, non_blocking=True)
                 batch[k] = v.long()
             elif isinstance(v, torch.Tensor):
-                batch[k] = v.long().to(self.device) if k == "text" else v.float().to(self.device)
+                batch[k] = v.long().to(self.device) if k in _INT64_KEYS else v.float().to(self.device)
 
     def forward(self, batch: Dict, training: bool = True):
         self._stage(batch)
@@ -394,7 +398,7 @@ class WeakPhraseRunner(StrongRunner):
     def _stage(self, batch: Dict):
         for k, v in batch.items():
             if isinstance(v, torch.Tensor):
-                batch[k] = v.long().to(self.device) if k == "text" else v.float().to(self.device)
+                batch[k] = v.long().to(self.device) if k in _INT64_KEYS else v.float().to(self.device)
 
     def forward(self, batch: Dict, training: bool = True):
         self._stage(batch)

@@ -461,6 +461,101 @@ def _tia_backward(ctx, dtok, dseq, _dsaved):
 register_autograd("tag::text_intra", _tia_backward, setup_context=_tia_setup)
 
 
+# ------------------------------------------------------------------------------------------------ T6 LAION-CLAP text tower
+_TCL_HEAD, _TCL_LAYER = _dispatch.TEXT_CLAP_SAVED_HEAD, _dispatch.TEXT_CLAP_SAVED_LAYER
+
+
+def _tcl_saved(saved, params, layers):
+    """The state ops.text_clap_backward expects, from what the operator returned: seven tensors of the embedding block and the
+    tail, then eleven per layer; the packed q|k|v weights are formed again from the three parameters."""
+    nh, nl = len(_TCL_HEAD), len(_TCL_LAYER)
+    st = dict(zip(_TCL_HEAD, saved[:nh]))
+    st["layers"] = []
+    for l in range(layers):
+        sv = dict(zip(_TCL_LAYER, saved[nh + nl * l: nh + nl * (l + 1)]))
+        b = 5 + 16 * l
+        sv["wqkv"] = torch.cat((params[b], params[b + 2], params[b + 4]), 0)
+        st["layers"].append(sv)
+    return st
+
+
+@custom_op("tag::text_clap", mutates_args=())
+def text_clap(input_ids: Tensor, attention_mask: Tensor, params: List[Tensor], heads: int, eps: float, pad_id: int,
+              p_hidden: float, p_attn: float, seed: int, need_grad: bool) -> Tuple[Tensor, Tensor, List[Tensor]]:
+    """LaionClapEncoder.forward (models/text_encoder.py:320-327): input_ids, attention_mask (R, L) int64, params in the order of
+    ops.text_clap_param_names -> token_emb (R, L, P), seq_emb (R, P) and the saved state (ops.TEXT_CLAP_SAVED_HEAD, then
+    ops.TEXT_CLAP_SAVED_LAYER per layer; empty when need_grad is False: a frozen tower, eval, no_grad).  p_hidden / p_attn > 0
+    (the caller passes 0 in eval mode): Hugging Face's four dropout sites, keep masks of ops.text_clap_dropout_seeds(seed, layers)."""
+    tok, seq, st = ops.text_clap_forward(input_ids, attention_mask, list(params), heads, eps, pad_id, need_grad, p_hidden, p_attn, seed)
+    if st is None:
+        return tok, seq, []
+    st = dict(st, seq_raw=st["seq_raw"].clone())                  # token_emb and seq_raw are two views of one buffer
+    return tok, seq, [st[k] for k in _TCL_HEAD] + [sv[k] for sv in st["layers"] for k in _TCL_LAYER]
+
+
+def _tcl_dims(input_ids, params, heads):
+    R, L = input_ids.shape
+    D, I, P = params[0].shape[1], params[5 + 10].shape[0], params[-4].shape[0]
+    return R, L, D, I, P
+
+
+@text_clap.register_fake
+def _(input_ids, attention_mask, params, heads, eps, pad_id, p_hidden, p_attn, seed, need_grad):
+    R, L, D, I, P = _tcl_dims(input_ids, params, heads)
+    M = R * L
+    x = params[0]
+    out = (x.new_empty(R, L, P), x.new_empty(R, P))
+    if not need_grad:
+        return (*out, [])
+    head = [input_ids.new_empty(M), input_ids.new_empty(R), x.new_empty(M, D), x.new_empty(M), x.new_empty(M + R, D),
+            x.new_empty(M + R, P), x.new_empty(R, P)]
+    per = [x.new_empty(M, D), x.new_empty(M, 3 * D), x.new_empty(R, heads, L, L), x.new_empty(M, D), x.new_empty(M, D), x.new_empty(M),
+           x.new_empty(M, D), x.new_empty(M, I), x.new_empty(M, I), x.new_empty(M, D), x.new_empty(M)]
+    layers = _dispatch.text_clap_layers(len(params))
+    return (*out, head + [torch.empty_like(t) for _ in range(layers) for t in per])
+
+
+@custom_op("tag::text_clap_backward", mutates_args=())
+def text_clap_backward(dtok: Optional[Tensor], dseq: Optional[Tensor], input_ids: Tensor, saved: List[Tensor], params: List[Tensor],
+                       heads: int, pad_id: int, p_hidden: float, p_attn: float, seed: int, need: List[bool]) -> List[Tensor]:
+    """-> one gradient per parameter; an entry that is not needed (need[i] False) is an empty tensor."""
+    st = _tcl_saved(list(saved), list(params), _dispatch.text_clap_layers(len(params)))
+    g = ops.text_clap_backward(dtok, dseq, input_ids, st, list(params), heads, pad_id, p_hidden, p_attn, seed, need=list(need))
+    return [t.view(p.shape) if t is not None else p.new_empty(0) for t, p in zip(g, params)]
+
+
+@text_clap_backward.register_fake
+def _(dtok, dseq, input_ids, saved, params, heads, pad_id, p_hidden, p_attn, seed, need):
+    return [torch.empty_like(p) if n else p.new_empty(0) for p, n in zip(params, need)]
+
+
+def _tcl_setup(ctx, inputs, output):
+    input_ids, _, params, heads, _, pad_id, p_hidden, p_attn, seed, _ = inputs
+    _, _, saved = output
+    ctx.save_for_backward(input_ids, *saved, *params)
+    ctx.meta = (heads, pad_id, p_hidden, p_attn, seed, len(saved))
+    ctx.need = [bool(p.requires_grad) for p in params]
+
+
+def _tcl_backward(ctx, dtok, dseq, _dsaved):
+    heads, pad_id, p_hidden, p_attn, seed, ns = ctx.meta
+    input_ids = ctx.saved_tensors[0]
+    saved, params = list(ctx.saved_tensors[1:1 + ns]), list(ctx.saved_tensors[1 + ns:])
+    if (dtok is None and dseq is None) or not any(ctx.need):
+        return (None,) * 10
+    if ns == 0:
+        raise RuntimeError("tag::text_clap ran with need_grad = False: nothing was saved for a backward pass")
+    if dtok is not None:
+        dtok = dtok.contiguous()
+    if dseq is not None:
+        dseq = dseq.contiguous()
+    g = torch.ops.tag.text_clap_backward(dtok, dseq, input_ids, saved, params, heads, pad_id, p_hidden, p_attn, seed, ctx.need)
+    return (None, None, [t if n else None for t, n in zip(g, ctx.need)], None, None, None, None, None, None, None)
+
+
+register_autograd("tag::text_clap", _tcl_backward, setup_context=_tcl_setup)
+
+
 # ------------------------------------------------------------------------------------------------ M1/M2 frame x phrase heads
 @custom_op("tag::frame_match", mutates_args=())
 def frame_match(audio: Tensor, text: Tensor, kind: int, l2norm: bool, scale: bool) -> Tensor:
@@ -1074,4 +1169,4 @@ OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_r
             "cross_cnn8rnn", "cross_cdur", "tagging_head", "tagging_head_backward", "masked_frame_bce",
             "masked_frame_bce_backward", "text_gru", "text_gru_backward", "text_selfattn", "text_selfattn_backward", "infonce",
             "infonce_backward", "triplet", "triplet_backward", "milnce", "milnce_backward", "text_intra", "text_intra_backward",
-            "clip_bce", "clip_bce_backward"]
+            "clip_bce", "clip_bce_backward", "text_clap", "text_clap_backward"]
