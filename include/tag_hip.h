@@ -153,7 +153,15 @@ int tag_conv3x3_forward(const float* x, const float* wpack, int prologue, const 
  * 6 of the 9 partial products by default (error of the dropped terms <= 2^-23 per product), TAG_X3_PRODUCTS=9
  * for all of them, =1 for plain bf16.  Opt-in; tag_conv3x3_forward above stays the exact-fp32 default.
  *   wfwd / wdgrad: tag_conv3x3_x3_pack_bytes(Cin, Cout) bytes each (pre-split, MFMA-fragment order).
- *   Requires W in {8,16,32,64}, Cin % 32 == 0, Cout % 64 == 0. */
+ * Argument rules of tag_conv3x3_forward_x3 and tag_conv3x3_forward_x3_bf16 (anything else returns -1 before any launch, outputs
+ * untouched): B, H > 0; W in {8,16,32,64}; Cin % 32 == 0 and Cin <= 512 (the prologue table of one workgroup: 2 x 512 floats);
+ * Cout % 64 == 0 (tiles of 128 couts where Cout % 128 == 0, else of 64); prologue 0..3, with in_scale AND in_shift unless 0;
+ * B H W < 2^31 and H W Cin sizeof(element) < 2^32 (32-bit byte offsets inside one image).  The data gradient is the same entry
+ * on the wdgrad pack with Cin and Cout exchanged, so it needs Cout % 32 == 0, Cout <= 512 and Cin % 64 == 0.
+ * tag_pack_conv_weight_x3: Cin % 32 == 0, Cout % 32 == 0, both packs non-NULL.  Pack layout: 16-byte fragment pieces at
+ * (((tap * K/16 + kk) * N/32 + nb) * 3 + plane) * 64 + lane, lane holding k = kk*16 + 8*(lane>>5) + 0..7 of n = nb*32 + (lane&31);
+ * forward K = Cin, N = Cout; dgrad K = Cout, N = Cin, tap 8 - tap.  Planes hi / mid / lo by truncation (hi + mid + lo == w
+ * exactly); products == 1: hi rounded to nearest even, mid = lo = 0. */
 size_t tag_conv3x3_x3_pack_bytes(int Cin, int Cout);
 /* products: partial products per fp32 multiply -- 6 (default), 9 (all), 1 (plain bf16: operands rounded to nearest
  * bf16, one product; BASELINE configs[2] arithmetic), 0 = process default (TAG_X3_PRODUCTS, else 6).  A weight pack
@@ -162,9 +170,11 @@ int tag_pack_conv_weight_x3(const float* w /*(Cout,Cin,3,3)*/, void* wfwd, void*
                             int products, void* stream);
 int tag_conv3x3_x3_stats_rows(int B, int H, int W, int Cout);
 /* the same for the bf16-storage entry points (tag_conv3x3_forward_x3_bf16 with this Cin / prologue; tag_conv3x3_dgrad_bnsums_bf16:
- * prologue 0).  Layers with Cin <= 128 run on the row-streaming kernel (csrc/conv_rows.hip: weights stationary in registers,
- * input rows by LDS-DMA into a ring) whose statistics accumulate over a whole strip of rows: one partial row per (strip, wave
- * M-group); the other layers write one row per tile M-group of the tile kernel.  (ABI 2: Cin and prologue were added.) */
+ * prologue 0).  The shapes (W, Cin, Cout) = (64, 64, 64) and (32, 64, multiple of 128) with H >= 2 and prologue 0 | 1 run on
+ * the row-streaming kernel (csrc/conv_rows.hip: weights stationary in registers, input rows by LDS-DMA into a ring) whose
+ * statistics accumulate over a whole strip of rows: B * strips * 2 * (2 | 1) partial rows, strips = min(ceil(CUs / (B * n-tiles)),
+ * H / 16), at least 1; every other shape writes one row per tile M-group of the tile kernel: B * ceil(H / (128 / W)) * (1 where
+ * Cout % 128 == 0, else 2).  (ABI 2: Cin and prologue were added.) */
 int tag_conv3x3_x3_bf16_stats_rows(int B, int H, int W, int Cin, int Cout, int prologue);
 /* 0: keep every bf16-storage layer on the tile kernel (A/B timing, tools/conv_rows_bench.py); returns the previous setting.
  * The environment variable TAG_CONV_ROWS=0 is the process-wide form. */
@@ -177,7 +187,11 @@ int tag_conv3x3_forward_x3(const float* x, const void* wpack, int prologue, cons
                            const float* in_shift, float* y, float* stats, int B, int H, int W, int Cin, int Cout,
                            int products, void* stream);
 /* wgrad with the same arithmetic (K = pixels; operands fetched with the transposing LDS read ds_read_b64_tr_b16).
- * Requires W in {8,16,32,64}, Cin % 64 == 0, Cout % 64 == 0; ws: tag_conv3x3_wgrad_x3_ws_bytes. */
+ * Requires B, H > 0, W in {8,16,32,64}, Cin % 64 == 0, Cout % 64 == 0 (no upper limit on either), prologue 0..3 with both tables
+ * unless 0, B H W < 2^31, H W Cin sizeof(element) < 2^32 and H W Cout sizeof(element) < 2^32; the same rules hold for
+ * tag_conv3x3_wgrad_x3_bf16.  ws: tag_conv3x3_wgrad_x3_ws_bytes (non-NULL) = splits * 9 * Cin * Cout floats for the larger of the
+ * two split counts (32-pixel chunks: fp32 tensors; 64-pixel chunks: bf16 tensors); a launch writes its own split count of
+ * partials and leaves the rest untouched.  The result is bit-identical from run to run. */
 size_t tag_conv3x3_wgrad_x3_ws_bytes(int B, int H, int W, int Cin, int Cout);
 int tag_conv3x3_wgrad_x3(const float* x, int prologue, const float* in_scale, const float* in_shift,
                          const float* dy, float* dw /*(Cout,Cin,3,3)*/, int B, int H, int W, int Cin, int Cout,
@@ -334,7 +348,10 @@ int tag_conv3x3_forward_bnrelu_pool_eval(const float* x, const float* wpack, int
                                          const float* in_shift, float* out, const float* bn_scale, const float* bn_shift, int B,
                                          int H, int W, int Cin, int Cout, int ph, int pw, int pool, void* stream);
 /* bf16-storage twin (BASELINE configs[2] mode): the sums are taken from the bf16 values of dx the apply pass will read back; rows:
- * tag_conv3x3_dgrad_poolsums_bf16_rows (0 = shape not served: keep tag_bnrelu_pool_backward_bf16) */
+ * tag_conv3x3_dgrad_poolsums_bf16_rows = B * ceil(H / (128 / W)), one per workgroup m-tile (0 = shape not served: keep
+ * tag_bnrelu_pool_backward_bf16).  Served: W in {8,16,32,64}, Cin % 32 == 0, Cin <= 512, Cout % 64 == 0 and NOT a shape of the
+ * row-streaming kernel (tag_conv3x3_x3_bf16_stats_rows above) while that kernel is enabled; pw == 2, ph 1 | 2, H == Hf / ph,
+ * W == Wf / 2, pool 0 | 2 | 3, 0 <= drop_p < 1, B Hf Wf < 2^31.  Anything else returns -1 with nothing written. */
 int tag_conv3x3_dgrad_poolsums_bf16_rows(int B, int H, int W, int Cin, int Cout);
 int tag_conv3x3_dgrad_poolsums_bf16(const void* dy, const void* wpack, void* dx, const void* yref, const float* bn_scale,
                                     const float* bn_shift, const float* bn_mean, const float* bn_invstd, float* bnpart, int B,
@@ -868,7 +885,8 @@ int tag_bnrelu_pool_backward_bf16(const void* y, const float* scale, const float
                                   uint64_t seed, int bn_train, void* ws, void* stream);
 /* bf16 twins of tag_conv3x3_dgrad_bnsums / tag_bnrelu_backward_apply (BASELINE configs[2] mode): the sums are taken from the
  * fp32 accumulators of the dgrad conv before its output is rounded to bf16; bnpart rows [P][2][Cout],
- * P = tag_conv3x3_x3_stats_rows(B,H,W,Cout). */
+ * P = tag_conv3x3_x3_bf16_stats_rows(B,H,W,Cin,Cout,0) (the row-streaming kernel writes one row per strip and wave M-group, not
+ * one per tile: tag_conv3x3_x3_stats_rows is the count of the fp32 entry only).  Argument rules of tag_conv3x3_forward_x3_bf16. */
 int tag_conv3x3_dgrad_bnsums_bf16(const void* dy, const void* wpack, void* da, const void* yref, const float* bn_scale,
                                   const float* bn_shift, const float* bn_mean, const float* bn_invstd, float* bnpart,
                                   int B, int H, int W, int Cin, int Cout, void* stream);
