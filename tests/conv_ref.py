@@ -1,4 +1,4 @@
-"""Plain-torch statements of every operation of csrc/conv.hip (channels-last, as the kernels see them), the launchers' host
+"""Plain-torch statements of every operation of csrc/conv.hip and csrc/conv_c1.hip (channels-last, as the kernels see them), the launchers' host
 formulas restated in Python, and the case tables of tests/test_gpu_conv_sweep.py with the CLAIM each row makes about the kernel it
 reaches.  tests/test_conv_ref_cpu.py checks the statements against F.conv2d / autograd / F.batch_norm / the torch pools to 1e-12
 and every claim against the restated formulas; the GPU module compares the kernels with the statements.

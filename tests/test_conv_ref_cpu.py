@@ -3,6 +3,8 @@ claim of the case tables of tests/test_gpu_conv_sweep.py re-derived from the lau
 condition of the cases (the fp32 floor is at most a quarter of the bound); the index arithmetic of the per-tap weight gradient's
 chunk loader, fixed and as the parent commit had it; and the calls the entry points refuse before any HIP call."""
 import ctypes
+import os
+import re
 
 import pytest
 import torch
@@ -246,6 +248,20 @@ def test_c1_case_claims():
     assert {c[4][0] for c in big} == {"wgrad4", "generic"}
     assert {h for _, h in R.C1_BWD_CASES} >= {1, 7, 8, 9}
     assert R.c1_bwd_geom(2, 1) == (1, 8) and R.c1_bwd_geom(3, 9) == (2, 8) and R.c1_bwd_geom(300, 9) == (2, 8)
+
+
+def test_c1_entries_live_in_conv_c1():
+    """the Cin = 1 convolution is its own translation unit: built with the library, every tag_conv3x3_c1_* entry of the
+    signature table defined there and none left behind in conv.hip (whose private builds then no longer compile them)"""
+    from texttoaudiogrounding_amd import lib
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "texttoaudiogrounding_amd", "csrc")
+    srcs = re.search(r"^SRCS = (.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1).split()
+    assert "conv_c1.hip" in srcs and "conv.hip" in srcs
+    names = [s for s in lib.declared_symbols() if s.startswith("tag_conv3x3_c1_")]
+    assert len(names) == 13
+    defined = lambda f: set(re.findall(r'^extern "C" \w+ (tag_\w+)\(', open(os.path.join(csrc, f)).read(), re.M))
+    assert set(names) <= defined("conv_c1.hip") and not any("_c1_" in s for s in defined("conv.hip"))
+    assert defined("conv.hip") >= {"tag_conv3x3_forward", "tag_conv3x3_wgrad"}
 
 
 def test_epilogue_case_claims():

@@ -1,4 +1,4 @@
-"""csrc/conv.hip over its edge shapes, every entry point called through the C ABI (ops.call / ops.query / ops.ptr) so that the
+"""csrc/conv.hip and csrc/conv_c1.hip over their edge shapes, every entry point called through the C ABI (ops.call / ops.query / ops.ptr) so that the
 kernel a row reaches is the one its table in tests/conv_ref.py claims (the claims are re-derived from the launchers' formulas in
 tests/test_conv_ref_cpu.py; the split counts are asserted here through tag_conv3x3_wgrad_ws_bytes, the statistics rows through
 tag_conv3x3_stats_rows): the weight packs, the halo-tile forward / dgrad with and without fused statistics, the tap-by-tap forward
@@ -577,7 +577,7 @@ C1_WGRAD_PARAMS = [(c, a) for c in R.C1_WGRAD_CASES for a in (True, False) if a 
 
 @pytest.mark.parametrize("case,affine", C1_WGRAD_PARAMS, ids=lambda v: pid(v, 4) if isinstance(v, tuple) else ("affine" if v else "plain"))
 def test_c1_wgrad_dgrad(ops, dev, case, affine):
-    """conv_c1_wgrad4_kernel (W % 4 == 0) and conv_c1_wgrad_kernel, Cout 4 .. 256, M below one block's first trip and above
+    """conv_c1_wgrad_kernel<4> (W % 4 == 0) and conv_c1_wgrad_kernel<1>, Cout 4 .. 256, M below one block's first trip and above
     1024 rpi 64 (a second grid-stride trip); tag_conv3x3_c1_dgrad on the same dy"""
     if IMPL:
         pytest.skip("the Cin = 1 kernels have no conv_impl switch")

@@ -30,7 +30,7 @@ __device__ __forceinline__ ClipMask clip_mask(const int* __restrict__ stripes, i
     return m;
 }
 
-// one clip's 4 values: bn0 affine exactly as the Cin = 1 convolutions form it on load (conv.hip c1_in: fmaf(v, cs[w], ct[w])),
+// one clip's 4 values: bn0 affine exactly as the Cin = 1 convolutions form it on load (conv_c1.hip c1_in: fmaf(v, cs[w], ct[w])),
 // then the stripes' zeros
 __device__ __forceinline__ f32x4 bn0_masked(const float* __restrict__ lm, const float* __restrict__ cs,
                                             const float* __restrict__ ct, const int* __restrict__ stripes, int nt, int nf,
