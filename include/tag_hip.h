@@ -1070,6 +1070,22 @@ int tag_clip_bce_forward(const float* p, const float* y, const float* aux, long 
 int tag_clip_bce_backward(const float* p, const float* y, const float* aux, long M, int mode, double c0, double c1, double c2,
                           const float* dloss, float* dp, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Thresholded similarity count (phrase_sim.hip; utils/data/calc_phrase_sim_count.py of the reference without its N x N matrix):
+ *   out[i] = sum_j weight[j] * [ sum_d q[i,d] * bank[j,d] >= threshold ]          i < M, j < N
+ * q (M, D) with row stride ldq, bank (N, D) with row stride ldb (both >= D, in floats), rows taken as given (the caller
+ * normalises them); weight (N) int64, null = all ones; out (M) int64.  The products are fp32 on the exact-fp32 MFMA (operands
+ * are not rounded), the comparison is >= on the fp32 sum, the counts are int64.  A workgroup owns 128 query rows and one slice
+ * of the bank's columns and leaves its sums in ws[slice][row]; a second launch adds the slices in slice order: no atomics, ws
+ * needs no zeroing, the same bits on every run.  ws (tag_phrase_sim_count_ws_bytes, a function of the shape alone) and out are
+ * the only device memory: no M x N or chunk x N scores exist.  Any M, N, D >= 1 (the D tail is zero-filled); q may equal bank.
+ * TAG_EINVAL before any launch, the limit named in tag_last_error: M, N or D < 1, ldq / ldb < D, a null q / bank / out / ws, M
+ * or N above 2^31 - 129, or a launch of more than 2^31 - 1 workgroups.
+ */
+size_t tag_phrase_sim_count_ws_bytes(int M, int N, int D);
+int tag_phrase_sim_count(const float* q, int ldq, const float* bank, int ldb, const long long* weight, float threshold,
+                         long long* out, int M, int N, int D, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

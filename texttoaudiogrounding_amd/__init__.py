@@ -36,6 +36,7 @@ def install_aliases(force: bool = False):
         # ``datasets`` itself stays whatever it is (the reference's directory has no __init__ and is shadowed by the
         # installed HF package of that name); only the sub-module names the YAML configs spell are registered
         "datasets.single_phrase_dataset": "texttoaudiogrounding_amd.datasets.single_phrase_dataset",
+        "datasets.multi_phrase_dataset": "texttoaudiogrounding_amd.datasets.multi_phrase_dataset",
         "datasets.collate_function": "texttoaudiogrounding_amd.datasets.collate_function",
         "datasets.text_tokenizer": "texttoaudiogrounding_amd.datasets.text_tokenizer",
     }

@@ -1,7 +1,9 @@
-"""Batch layout of the reference's loaders (mirror of datasets/collate_function.py:7-85): list of item dicts -> dict of
+"""Batch layout of the reference's loaders (mirror of datasets/collate_function.py:7-133): list of item dicts -> dict of
 batched values.  Keys in ``pad_keys`` are zero-padded to the longest item (``<key>`` tensor + ``<key>_len`` numpy array);
 ``TextCollate`` sends the ``text_key`` column (phrases) through the tokenizer (-> ``text`` / ``text_len``) and records
-``text_key``; every other column becomes a tensor when its items are numpy arrays, else a numpy array of the values."""
+``text_key``; every other column becomes a tensor when its items are numpy arrays, else a numpy array of the values.
+``VarNumTextCollate`` takes items with DIFFERENT numbers of phrases: the phrase lists are concatenated, tokenised as one flat
+list and stored under ``<text_key>`` / ``<text_key>_len`` with the per-item counts in ``<text_key>_num``."""
 from typing import Dict, List
 
 import numpy as np
@@ -59,6 +61,24 @@ class TextCollate(VarLenPadCollate):
                 out[f"{k}_len"] = lens.numpy()
             elif k == self.text_key:
                 out.update(self.tokenizer(cols[k]))          # the phrase strings stay under their own key
+            else:
+                out[k] = self._plain(cols[k])
+        return out
+
+
+class VarNumTextCollate(TextCollate):
+    def __call__(self, batch: List[Dict]):
+        cols = self._columns(batch)
+        out = dict(cols)
+        out["text_key"] = self.text_key
+        for k in batch[0].keys():
+            if k in self.pad_keys:
+                out[k], lens = pad_sequence(cols[k])
+                out[f"{k}_len"] = lens.numpy()
+            elif k == self.text_key:
+                out[f"{k}_num"] = [len(texts) for texts in cols[k]]
+                tokens = self.tokenizer([t for texts in cols[k] for t in texts])
+                out[k], out[f"{k}_len"] = tokens["text"], tokens["text_len"]
             else:
                 out[k] = self._plain(cols[k])
         return out

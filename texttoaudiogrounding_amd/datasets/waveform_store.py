@@ -42,11 +42,19 @@ def write_waveform_pack(path: str, clips: Iterable[Tuple[str, np.ndarray]], csv_
     return csv_path
 
 
+def load_pack_map(path: str) -> Dict[str, str]:
+    """audio_id -> pack file of a waveform TSV under either header the reference writes: ``audio_id<TAB>hdf5_path`` (the strong
+    datasets) or ``audio_id<TAB>file_path`` (datasets/multi_phrase_dataset.py:65-67)."""
+    with open(path, newline="") as f:
+        header = f.readline().rstrip("\r\n").split("\t")
+    return load_dict_from_csv(path, ("audio_id", "file_path" if "hdf5_path" not in header and "file_path" in header else "hdf5_path"))
+
+
 class WaveformStore:
     """audio_id -> samples, over the packs listed in a waveform TSV; pack handles are opened once and cached."""
 
     def __init__(self, waveform_csv: str):
-        self.aid_to_pack = load_dict_from_csv(waveform_csv, ("audio_id", "hdf5_path"))
+        self.aid_to_pack = load_pack_map(waveform_csv)
         self._open = {}
 
     def _pack(self, path: str):

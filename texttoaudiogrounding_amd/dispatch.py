@@ -2204,3 +2204,46 @@ def clip_bce_backward(clip_sim, label, aux, mode, c0, c1, c2, dloss):
     call("tag_clip_bce_backward", ptr(c), ptr(y), ptr(a), c.numel(), int(mode), float(c0), float(c1), float(c2),
          ptr(_dloss(dloss)), ptr(dc))
     return dc
+
+
+# ------------------------------------------------------------------------------------------------
+# thresholded similarity count (utils/data/calc_phrase_sim_count.py in the reference), phrase_sim.hip
+# ------------------------------------------------------------------------------------------------
+
+def _phrase_sim_rows(t, name):
+    """(rows, D) fp32 on the device with unit column stride; a row-strided view of a wider buffer is passed as it is."""
+    if not t.is_cuda:
+        _chk(t, name)
+    if t.dtype != F32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise RuntimeError(f"{name}: expected a float32 matrix (rows >= 1, D >= 1), got {t.dtype} {tuple(t.shape)}")
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t
+
+
+def phrase_sim_count(q, bank, weight=None, threshold=0.5, normalize=True):
+    """out[i] = sum_j weight[j] * [q[i] . bank[j] >= threshold] as int64 (M,), q (M, D) against bank (N, D); weight (N) int64
+    or None for all ones.  normalize: both operands through x / max(||x||, 1e-12) first (sklearn's cosine_similarity, the
+    all-zero row staying zero); ``q is bank`` normalises once.  No (M, N) scores exist on the device."""
+    same = q is bank
+    qr = _phrase_sim_rows(q, "q")
+    br = qr if same else _phrase_sim_rows(bank, "bank")
+    if br.device != qr.device or br.shape[1] != qr.shape[1]:
+        raise RuntimeError(f"bank {tuple(br.shape)} on {br.device}: expected q's device {qr.device} and D = {qr.shape[1]}")
+    (M, D), N = qr.shape, br.shape[0]
+    if normalize:
+        qr = _unit_rows(qr.contiguous(), M, D)
+        br = qr if same else _unit_rows(br.contiguous(), N, D)
+    w = None
+    if weight is not None:
+        if not weight.is_cuda:
+            _chk(weight, "weight")
+        if weight.dtype != torch.int64 or weight.shape != (N,) or weight.device != qr.device:
+            raise RuntimeError(f"weight: expected int64 ({N},) on {qr.device}, got {weight.dtype} {tuple(weight.shape)} on "
+                               f"{weight.device}")
+        w = weight.contiguous()
+    out = torch.empty(M, device=qr.device, dtype=torch.int64)
+    ws = _ws(query("tag_phrase_sim_count_ws_bytes", M, N, D), qr)
+    call("tag_phrase_sim_count", ptr(qr), qr.stride(0), ptr(br), br.stride(0), ptr(w), float(threshold), ptr(out), M, N, D,
+         ptr(ws))
+    return out

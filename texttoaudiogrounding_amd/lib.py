@@ -234,6 +234,8 @@ _SIGS = {
     "tag_clip_bce_ws_bytes": (c_size_t, [c_long]),
     "tag_clip_bce_forward": (c_int, [P, P, P, c_long, c_int, c_double, c_double, c_double, P, P, P]),
     "tag_clip_bce_backward": (c_int, [P, P, P, c_long, c_int, c_double, c_double, c_double, P, P, P]),
+    "tag_phrase_sim_count_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "tag_phrase_sim_count": (c_int, [P, c_int, P, c_int, P, c_float, P, c_int, c_int, c_int, P, P]),
 }
 
 _lib = None
