@@ -1086,6 +1086,32 @@ size_t tag_phrase_sim_count_ws_bytes(int M, int N, int D);
 int tag_phrase_sim_count(const float* q, int ldq, const float* bank, int ldb, const long long* weight, float threshold,
                          long long* out, int M, int N, int D, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device k-means (kmeans.hip; python_scripts/clustering/kmeans_emb.py of the reference runs sklearn on the host).  x (N, D) with
+ * row stride ldx, centers (K, D) with row stride ldc (both >= D, in floats), all fp32.  Every *_ws_bytes is a function of the
+ * shape alone (0 for a shape the call would refuse); ws is never zeroed; no atomics: the same bits on every run.
+ *
+ * tag_kmeans_assign: label[i] (int32) = argmin_k (||c_k||^2 - 2 x_i . c_k), the products fp32 on the exact-fp32 MFMA (operands
+ *   not rounded), ||c_k||^2 computed once per call into ws; ties go to the lowest k (identical centre rows score identically
+ *   bit for bit); a column past K never wins.  dist2[i] (fp32) = sum_d (x_id - c_label,d)^2 from the differences, not from the
+ *   expansion.  No (N, K) scores exist on the device.
+ * tag_kmeans_update: sums (K x D, fp64, dense) = sum of the rows of each label, count (K, int64), centers[k] = sums[k] / count[k]
+ *   for count > 0; a row of centers with count 0 is left untouched.  Row slices leave fp32 partials in ws (MFMA with a one-hot
+ *   operand formed in registers), a second launch folds them in fp64 in slice order.  A label outside [0, K) is counted nowhere
+ *   (the caller checks the range).
+ * tag_kmeans_seed_step: closest[i] = min(closest[i], ||x_i - x_p||^2), p = *pick read on the device (int64); first != 0 writes
+ *   the distance without the min.  A pick outside [0, N) writes nothing.
+ * TAG_EINVAL before any launch, the numbers named in tag_last_error: N, K or D < 1, a row stride < D, a null pointer, N above
+ * 2^31 - 129, K above 65535 * 32.
+ */
+size_t tag_kmeans_assign_ws_bytes(int N, int K, int D);
+int tag_kmeans_assign(const float* x, int ldx, const float* centers, int ldc, int* label, float* dist2, int N, int K, int D,
+                      void* ws, void* stream);
+size_t tag_kmeans_update_ws_bytes(int N, int K, int D);
+int tag_kmeans_update(const float* x, int ldx, const int* label, double* sums, long long* count, float* centers, int ldc, int N,
+                      int K, int D, void* ws, void* stream);
+int tag_kmeans_seed_step(const float* x, int ldx, const long long* pick, float* closest, int first, int N, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

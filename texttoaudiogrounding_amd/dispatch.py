@@ -2247,3 +2247,80 @@ def phrase_sim_count(q, bank, weight=None, threshold=0.5, normalize=True):
     call("tag_phrase_sim_count", ptr(qr), qr.stride(0), ptr(br), br.stride(0), ptr(w), float(threshold), ptr(out), M, N, D,
          ptr(ws))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# device k-means (python_scripts/clustering/kmeans_emb.py in the reference runs sklearn on the host), kmeans.hip
+# ------------------------------------------------------------------------------------------------
+
+def _kmeans_vec(t, name, dtype, n, like):
+    if not t.is_cuda:
+        _chk(t, name)
+    if t.dtype != dtype or t.shape != (n,) or t.device != like.device:
+        raise RuntimeError(f"{name}: expected {dtype} ({n},) on {like.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t.contiguous()
+
+
+def _kmeans_pair(x, centers):
+    xr, cr = _phrase_sim_rows(x, "x"), _phrase_sim_rows(centers, "centers")
+    if cr.device != xr.device or cr.shape[1] != xr.shape[1]:
+        raise RuntimeError(f"centers {tuple(cr.shape)} on {cr.device}: expected x's device {xr.device} and D = {xr.shape[1]}")
+    return xr, cr
+
+
+def kmeans_assign(x, centers):
+    """(label int32 (N,), dist2 fp32 (N,)): label[i] = argmin_k (||c_k||^2 - 2 x_i . c_k) on the exact-fp32 MFMA, ties to the lowest
+    k; dist2[i] = sum_d (x_id - c_label,d)^2 from the differences.  x (N, D), centers (K, D), row-strided views are passed as they
+    are.  No (N, K) scores exist on the device."""
+    xr, cr = _kmeans_pair(x, centers)
+    (N, D), K = xr.shape, cr.shape[0]
+    label = torch.empty(N, device=xr.device, dtype=torch.int32)
+    dist2 = torch.empty(N, device=xr.device, dtype=F32)
+    ws = _ws(query("tag_kmeans_assign_ws_bytes", N, K, D), xr)
+    call("tag_kmeans_assign", ptr(xr), xr.stride(0), ptr(cr), cr.stride(0), ptr(label), ptr(dist2), N, K, D, ptr(ws))
+    return label, dist2
+
+
+def kmeans_update(x, label, centers, check_labels=True):
+    """(sums fp64 (K, D), count int64 (K,)); ``centers`` (K, D) is updated IN PLACE: row k = sums[k] / count[k] where count[k] > 0,
+    untouched otherwise.  label (N,) int32 in [0, K) (check_labels: one torch min / max with a host read).  The same bits on
+    every run."""
+    xr = _phrase_sim_rows(x, "x")
+    if not centers.is_cuda:
+        _chk(centers, "centers")
+    (N, D) = xr.shape
+    if (centers.dtype != F32 or centers.dim() != 2 or centers.shape[0] < 1 or centers.shape[1] != D or centers.stride(1) != 1
+            or centers.stride(0) < D or centers.device != xr.device):
+        raise RuntimeError(f"centers: expected a float32 (K >= 1, {D}) matrix with unit column stride on {xr.device} (it is written "
+                           f"in place), got {centers.dtype} {tuple(centers.shape)} strides {tuple(centers.stride())} on "
+                           f"{centers.device}")
+    K = centers.shape[0]
+    lab = _kmeans_vec(label, "label", torch.int32, N, xr)
+    if check_labels:
+        lo, hi = (int(v) for v in torch.stack((lab.min(), lab.max())).tolist())
+        if lo < 0 or hi >= K:
+            raise RuntimeError(f"label: values must lie in [0, {K}), got min {lo}, max {hi}")
+    sums = torch.empty(K, D, device=xr.device, dtype=torch.float64)
+    count = torch.empty(K, device=xr.device, dtype=torch.int64)
+    ws = _ws(query("tag_kmeans_update_ws_bytes", N, K, D), xr)
+    call("tag_kmeans_update", ptr(xr), xr.stride(0), ptr(lab), ptr(sums), ptr(count), ptr(centers), centers.stride(0), N, K, D,
+         ptr(ws))
+    return sums, count
+
+
+def kmeans_seed_step(x, pick, closest, first=False):
+    """closest[i] = min(closest[i], ||x_i - x_p||^2) in place, p = pick (one int64 ON THE DEVICE: no host round trip in the
+    k-means++ loop); first: write the distance without the min.  Returns closest."""
+    xr = _phrase_sim_rows(x, "x")
+    N, D = xr.shape
+    if not pick.is_cuda:
+        _chk(pick, "pick")
+    if pick.dtype != torch.int64 or pick.numel() != 1 or pick.device != xr.device:
+        raise RuntimeError(f"pick: expected one int64 on {xr.device}, got {pick.dtype} {tuple(pick.shape)} on {pick.device}")
+    if not closest.is_cuda:
+        _chk(closest, "closest")
+    if closest.dtype != F32 or closest.shape != (N,) or not closest.is_contiguous() or closest.device != xr.device:
+        raise RuntimeError(f"closest: expected contiguous float32 ({N},) on {xr.device} (it is written in place), got "
+                           f"{closest.dtype} {tuple(closest.shape)} on {closest.device}")
+    call("tag_kmeans_seed_step", ptr(xr), xr.stride(0), ptr(pick), ptr(closest), int(bool(first)), N, D)
+    return closest

@@ -236,6 +236,11 @@ _SIGS = {
     "tag_clip_bce_backward": (c_int, [P, P, P, c_long, c_int, c_double, c_double, c_double, P, P, P]),
     "tag_phrase_sim_count_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tag_phrase_sim_count": (c_int, [P, c_int, P, c_int, P, c_float, P, c_int, c_int, c_int, P, P]),
+    "tag_kmeans_assign_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "tag_kmeans_assign": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, P]),
+    "tag_kmeans_update_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "tag_kmeans_update": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "tag_kmeans_seed_step": (c_int, [P, c_int, P, P, c_int, c_int, c_int, P]),
 }
 
 _lib = None

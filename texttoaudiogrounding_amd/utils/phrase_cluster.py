@@ -1,0 +1,244 @@
+"""k-means over phrase embeddings on the device: what python_scripts/clustering/kmeans_emb.py of the reference does with sklearn
+on the host.  It makes the ``cluster_map`` JSON that ``AudioSamplePhrasesDataset(neg_samp_stratg="clustering")`` reads and the
+cluster model that ``KmeansMappingDataset`` / ``KmeansMappingEvalDataset`` turn phrases into class indices with.
+
+``KMeans`` runs Lloyd's algorithm on three entry points of csrc/kmeans.hip (``ops.kmeans_assign`` / ``kmeans_update`` /
+``kmeans_seed_step``): no (N, K) matrix exists on the device and two fits from the same start give the same bits.  The stopping
+rules are sklearn's: stop when the labels equal the previous iteration's, or when sum ||delta c||^2 <= tol * mean(var(x, axis 0))
+(then one more assignment so that ``labels_`` match the centres); ``n_iter_`` counts completed iterations.  An empty cluster
+takes the row with the largest squared distance to its centre (several empty clusters: the largest first), and that row
+leaves its donor cluster's sum and count before the division.
+
+Deviations from sklearn: ``"k-means++"`` is plain D^2 sampling with one candidate per step (no greedy multi-trial), x is not
+mean-centred before the fit, and the arithmetic is fp32 with fp64 cluster sums.
+"""
+import os
+from typing import Dict, List, Mapping, Optional, Sequence
+
+import numpy as np
+import torch
+
+
+def cluster_map_from_labels(phrases: Sequence[str], labels) -> Dict[str, List[str]]:
+    """{str(label): [phrases ...]} with keys in order of first appearance: the reference's ``result``."""
+    result: Dict[str, List[str]] = {}
+    for phrase, label in zip(phrases, labels):
+        result.setdefault(str(int(label)), []).append(phrase)
+    return result
+
+
+def load_cluster_centers(path) -> np.ndarray:
+    """The (K, D) fp32 centres of a cluster model file: an ``.npz`` written by ``KMeans.save`` is read natively; any other suffix is
+    tried through joblib and the object's ``cluster_centers_`` taken, so a checkpoint of the reference's script still loads."""
+    path = os.fspath(path)
+    if path.endswith(".npz"):
+        with np.load(path) as f:
+            return np.ascontiguousarray(f["cluster_centers"], dtype=np.float32)
+    try:
+        import joblib
+    except ImportError:
+        raise RuntimeError(f"{path}: only .npz cluster models (KMeans.save) are read natively; any other file is taken for a "
+                           "joblib checkpoint of sklearn's KMeans, and joblib is not importable here") from None
+    return np.ascontiguousarray(joblib.load(path).cluster_centers_, dtype=np.float32)
+
+
+class KMeans:
+    """sklearn-shaped k-means on the device.  ``init``: "k-means++" or a (K, D) array; ``n_init`` > 1 (k-means++ only) keeps the
+    run with the lowest inertia.  After ``fit``: ``cluster_centers_`` (numpy fp32), ``labels_`` (numpy int32), ``inertia_`` (the
+    fp64 sum of the squared distances), ``n_iter_``."""
+
+    def __init__(self, n_clusters, init="k-means++", n_init=1, max_iter=300, tol=1e-4, random_state=None, device="cuda:0"):
+        self.n_clusters = int(n_clusters)
+        self.init = init
+        self.n_init = int(n_init)
+        self.max_iter = int(max_iter)
+        self.tol = float(tol)
+        self.random_state = random_state
+        self.device = device
+        if self.n_clusters < 1 or self.n_init < 1 or self.max_iter < 1:
+            raise ValueError(f"n_clusters, n_init and max_iter must be >= 1 (got {n_clusters}, {n_init}, {max_iter})")
+        if isinstance(init, str) and init != "k-means++":
+            raise ValueError(f"init: expected 'k-means++' or a (K, D) array, got {init!r}")
+        self.cluster_centers_: Optional[np.ndarray] = None
+        self.labels_: Optional[np.ndarray] = None
+        self.inertia_: Optional[float] = None
+        self.n_iter_: Optional[int] = None
+        self._centers_dev = None
+
+    # ---- plumbing ----
+    def _rows(self, x):
+        """(N, D) fp32 on self.device; a device tensor is taken as it is."""
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
+        x = x.to(device=self.device, dtype=torch.float32)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"x: expected a (N >= 1, D >= 1) matrix, got {tuple(x.shape)}")
+        return x
+
+    def _centers(self, D=None):
+        if self.cluster_centers_ is None:
+            raise RuntimeError("this KMeans has no centres yet: call fit or KMeans.load first")
+        if self._centers_dev is None or str(self._centers_dev.device) != str(torch.device(self.device)):
+            self._centers_dev = torch.from_numpy(self.cluster_centers_).to(self.device)
+        if D is not None and self._centers_dev.shape[1] != D:
+            raise ValueError(f"x has D = {D}, the centres have D = {self._centers_dev.shape[1]}")
+        return self._centers_dev
+
+    # ---- seeding ----
+    def seed_picks(self, x, rs) -> torch.Tensor:
+        """k-means++ by plain D^2 sampling -> the (K,) int64 row indices, on the device.  The uniforms come from ``rs`` (a
+        numpy RandomState) on the host, ``randint(N)`` then ``random_sample(K - 1)``; pick j is the first row whose fp64 prefix
+        sum of ``closest`` reaches u_j times the total.  Nothing is read back inside the loop."""
+        from .. import ops
+        N, K = x.shape[0], self.n_clusters
+        first = int(rs.randint(N))
+        u = torch.from_numpy(np.asarray(rs.random_sample(K - 1), dtype=np.float64)).to(x.device)
+        picks = torch.empty(K, device=x.device, dtype=torch.int64)
+        picks[0] = first
+        closest = torch.empty(N, device=x.device, dtype=torch.float32)
+        for j in range(1, K):
+            ops.kmeans_seed_step(x, picks[j - 1:j], closest, first=(j == 1))
+            cs = torch.cumsum(closest.double(), 0)
+            picks[j] = torch.searchsorted(cs, (u[j - 1] * cs[-1]).reshape(1)).clamp_(max=N - 1)[0]
+        return picks
+
+    # ---- Lloyd ----
+    def _lloyd(self, x, centers, tol_abs):
+        """One run from ``centers`` (K, D) fp32 on the device, updated in place -> (labels int32, dist2 fp32, n_iter)."""
+        from .. import ops
+        N = x.shape[0]
+        prev = torch.full((N,), -1, device=x.device, dtype=torch.int32)
+        strict, n_iter = False, 0
+        for it in range(self.max_iter):
+            label, dist2 = ops.kmeans_assign(x, centers)
+            old = centers.clone()
+            sums, count = ops.kmeans_update(x, label, centers, check_labels=False)
+            empty = count == 0
+            shift = ((centers.double() - old.double()) ** 2).sum()
+            same, n_empty, small = torch.stack(((label == prev).all().double(), empty.sum().double(),
+                                                (shift <= tol_abs).double())).tolist()       # the iteration's one host read
+            if n_empty:
+                self._relocate(x, label, dist2, sums, count, centers, torch.nonzero(empty).flatten().tolist())
+                small = bool(((centers.double() - old.double()) ** 2).sum() <= tol_abs)
+            n_iter = it + 1
+            if same:
+                strict = True
+                break
+            if small:
+                break
+            prev = label
+        if not strict:
+            label, dist2 = ops.kmeans_assign(x, centers)
+        return label, dist2, n_iter
+
+    @staticmethod
+    def _relocate(x, label, dist2, sums, count, centers, empty):
+        """sklearn's rule for empty clusters (rare: plain torch indexing on the fp64 sums): they take the rows with the largest
+        dist2, the largest first; each such row leaves its donor cluster before the division."""
+        far = torch.argsort(dist2, descending=True, stable=True)[:len(empty)].tolist()
+        touched = set()
+        for k, i in zip(empty, far):
+            donor = int(label[i])
+            row = x[i].double()
+            sums[donor] -= row
+            count[donor] -= 1
+            sums[k] = row
+            count[k] = 1
+            touched.update((donor, k))
+        for k in sorted(touched):
+            if int(count[k]) > 0:
+                centers[k] = (sums[k] / count[k].double()).float()
+
+    def fit(self, x):
+        x = self._rows(x)
+        N, D = x.shape
+        K = self.n_clusters
+        if K > N:
+            raise ValueError(f"n_samples={N} should be >= n_clusters={K}")
+        explicit = not isinstance(self.init, str)
+        if explicit:
+            init = self._rows(self.init)
+            if tuple(init.shape) != (K, D):
+                raise ValueError(f"init: expected a ({K}, {D}) array, got {tuple(init.shape)}")
+        tol_abs = self.tol * x.double().var(dim=0, unbiased=False).mean()
+        rs = np.random.RandomState(self.random_state)
+        best = None
+        for _ in range(1 if explicit else self.n_init):
+            centers = init.clone().contiguous() if explicit else x[self.seed_picks(x, rs)].contiguous()
+            label, dist2, n_iter = self._lloyd(x, centers, tol_abs)
+            inertia = float(dist2.double().sum())
+            if best is None or inertia < best[0]:
+                best = (inertia, centers, label, n_iter)
+        self.inertia_, self._centers_dev, label, self.n_iter_ = best
+        self.cluster_centers_ = self._centers_dev.cpu().numpy()
+        self.labels_ = label.cpu().numpy()
+        return self
+
+    def fit_predict(self, x):
+        return self.fit(x).labels_
+
+    def _assign(self, x):
+        from .. import ops
+        x = self._rows(x)
+        return ops.kmeans_assign(x, self._centers(x.shape[1]))
+
+    def predict(self, x) -> np.ndarray:
+        return self._assign(x)[0].cpu().numpy()
+
+    def min_distance(self, x) -> np.ndarray:
+        """sqrt(dist2): what ``transform(x).min(1)`` gives, without the (N, K) matrix."""
+        return torch.sqrt(self._assign(x)[1]).cpu().numpy()
+
+    def predict_min_distance(self, x):
+        """(labels, distances to the assigned centre) from ONE assignment call."""
+        label, dist2 = self._assign(x)
+        return label.cpu().numpy(), torch.sqrt(dist2).cpu().numpy()
+
+    def transform(self, x) -> np.ndarray:
+        """(N, K) Euclidean distances (interface parity; the one place an N x K array exists): ||x||^2 + ||c||^2 - 2 x . c with
+        the products from ops.gemm, clamped at 0 before the root."""
+        from .. import ops
+        x = self._rows(x).contiguous()
+        c = self._centers(x.shape[1])
+        N, D = x.shape
+        xc = ops.gemm(x, c, N, c.shape[0], D, transB=True)
+        d2 = (x * x).sum(1, keepdim=True) + (c * c).sum(1)[None, :] - 2.0 * xc
+        return torch.sqrt(d2.clamp_(min=0.0)).cpu().numpy()
+
+    # ---- files ----
+    def save(self, path):
+        """An ``.npz`` holding the centres and the constructor settings (``load_cluster_centers`` / ``KMeans.load`` read it)."""
+        if self.cluster_centers_ is None:
+            raise RuntimeError("this KMeans has no centres yet: call fit first")
+        np.savez(path, cluster_centers=self.cluster_centers_, n_clusters=self.n_clusters, n_init=self.n_init, max_iter=self.max_iter,
+                 tol=self.tol, random_state=-1 if self.random_state is None else int(self.random_state),
+                 has_random_state=self.random_state is not None, inertia=np.nan if self.inertia_ is None else self.inertia_,
+                 n_iter=-1 if self.n_iter_ is None else self.n_iter_)
+
+    @classmethod
+    def load(cls, path, device="cuda:0"):
+        with np.load(path) as f:
+            km = cls(int(f["n_clusters"]), n_init=int(f["n_init"]), max_iter=int(f["max_iter"]), tol=float(f["tol"]),
+                     random_state=int(f["random_state"]) if bool(f["has_random_state"]) else None, device=device)
+            km.cluster_centers_ = np.ascontiguousarray(f["cluster_centers"], dtype=np.float32)
+            km.inertia_ = None if np.isnan(f["inertia"]) else float(f["inertia"])
+            km.n_iter_ = None if int(f["n_iter"]) < 0 else int(f["n_iter"])
+        return km
+
+    @classmethod
+    def from_centers(cls, centers, device="cuda:0"):
+        """A model that only predicts: the (K, D) centres of ``load_cluster_centers``."""
+        centers = np.ascontiguousarray(centers, dtype=np.float32)
+        km = cls(centers.shape[0], device=device)
+        km.cluster_centers_ = centers
+        return km
+
+
+def kmeans_cluster_map(phrase_to_emb: Mapping[str, np.ndarray], n_clusters: int, **kw):
+    """The reference's ``KmeansClustering().kmeans`` on a {phrase: embedding} table -> {"score": inertia, "model": the fitted
+    KMeans, "result": {str(label): [phrases ...]}}; ``kw`` goes to ``KMeans``."""
+    phrases = list(phrase_to_emb)
+    embs = np.stack([np.asarray(phrase_to_emb[p], dtype=np.float32).reshape(-1) for p in phrases])
+    model = KMeans(n_clusters, **kw)
+    labels = model.fit_predict(embs)
+    return {"score": model.inertia_, "model": model, "result": cluster_map_from_labels(phrases, labels)}
