@@ -1112,6 +1112,32 @@ int tag_kmeans_update(const float* x, int ldx, const int* label, double* sums, l
                       int K, int D, void* ws, void* stream);
 int tag_kmeans_seed_step(const float* x, int ldx, const long long* pick, float* closest, int first, int N, int D, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device DBSCAN (dbscan.hip; python_scripts/clustering/dbscan_emb.py of the reference runs sklearn's DBSCAN(metric="precomputed")
+ * on an N x N float matrix on the host).  The graph is a BIT matrix adj (N x W int32 words, W = tag_dbscan_words(N) =
+ * 4 ceil(N / 128): whole 128-column tiles, 16-byte aligned rows; bit j % 32 of word j / 32 of row i is the pair (i, j)),
+ * caller-owned: N^2 / 8 bytes, and no other device memory scales with N^2.  core_bits (W words) is one such row.
+ *
+ * tag_dbscan_words: W, or 0 for an N the calls would refuse.
+ * tag_dbscan_graph: adj[i][j] = [sum_d x[i,d] * x[j,d] >= threshold], the products fp32 on the exact-fp32 MFMA (operands not
+ *   rounded; phrase_sim.hip's marching kernel with q = bank = x, rows taken as given: the caller normalises them), x (N, D) with
+ *   row stride ldx >= D in floats.  The diagonal is computed like any other pair.  EVERY word of adj is written, and bits at
+ *   columns >= N are 0.  degree[i] (int32) = popcount of row i (a second launch).  The same bits on every run.
+ * tag_dbscan_core: core_bits = the flags degree[i] >= min_samples, bits at rows >= N are 0.
+ * tag_dbscan_hook: one FastSV pass on the parent array f (int32, N; 0 .. N - 1 before the first pass, every value a row index):
+ *   with gf = f_in[f_in] and m_i = min of gf[j] over the core neighbours j of core row i,  f_out[f_in[i]] = min(.., m_i) and
+ *   f_out[i] = min(.., m_i, gf[i]),  f_out starting as a copy of f_in (f_out != f_in).  The scatter-min is an integer atomicMin:
+ *   the result does not depend on the order.  *changed (device int32) = 1 if f_out differs from f_in, else 0.  At the fixed
+ *   point f[i] is the lowest index of core row i's component of the core-core graph.
+ * tag_dbscan_roots: root[i] (int32) = f[i] for a core row, otherwise the smallest f[j] over the core neighbours j of row i, or -1.
+ * TAG_EINVAL before any launch, the numbers named in tag_last_error: N or D < 1, ldx < D, a null pointer, N above 2^31 - 129.
+ */
+int tag_dbscan_words(int N);
+int tag_dbscan_graph(const float* x, int ldx, float threshold, int* adj, int* degree, int N, int D, void* stream);
+int tag_dbscan_core(const int* degree, int min_samples, int* core_bits, int N, void* stream);
+int tag_dbscan_hook(const int* adj, const int* core_bits, const int* f_in, int* f_out, int* changed, int N, void* stream);
+int tag_dbscan_roots(const int* adj, const int* core_bits, const int* f, int* root, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

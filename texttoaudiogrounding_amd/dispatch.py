@@ -2324,3 +2324,95 @@ def kmeans_seed_step(x, pick, closest, first=False):
                            f"{closest.dtype} {tuple(closest.shape)} on {closest.device}")
     call("tag_kmeans_seed_step", ptr(xr), xr.stride(0), ptr(pick), ptr(closest), int(bool(first)), N, D)
     return closest
+
+
+# ------------------------------------------------------------------------------------------------
+# device DBSCAN (python_scripts/clustering/dbscan_emb.py in the reference runs sklearn on an N x N float matrix), dbscan.hip
+# ------------------------------------------------------------------------------------------------
+
+def dbscan_words(N):
+    """32-bit words per row of the adjacency bit matrix of N rows: 4 * ceil(N / 128)."""
+    W = query("tag_dbscan_words", int(N))
+    if W < 1:
+        raise RuntimeError(f"dbscan: N = {N} rows: expected 1 <= N <= {2**31 - 129}")
+    return W
+
+
+def _dbscan_ints(t, name, shape, like, what=""):
+    if not t.is_cuda:
+        _chk(t, name)
+    if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or (like is not None and t.device != like.device):
+        on = f" on {like.device}" if like is not None else ""
+        raise RuntimeError(f"{name}: expected contiguous int32 {shape}{on}{what}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _dbscan_graph_args(adj, core_bits):
+    if not adj.is_cuda:
+        _chk(adj, "adj")
+    if adj.dim() != 2 or adj.shape[0] < 1:
+        raise RuntimeError(f"adj: expected the int32 (N, W) bit matrix of dbscan_graph, got {adj.dtype} {tuple(adj.shape)}")
+    N = adj.shape[0]
+    W = dbscan_words(N)
+    _dbscan_ints(adj, "adj", (N, W), None, " (W = 4 * ceil(N / 128))")
+    _dbscan_ints(core_bits, "core_bits", (W,), adj)
+    return N, W
+
+
+def dbscan_graph(x, eps=0.5, normalize=True):
+    """(adj int32 (N, W), degree int32 (N,)): bit j % 32 of adj[i, j // 32] = [x_i . x_j >= 1 - eps] on the exact-fp32 MFMA, W =
+    4 * ceil(N / 128), bits at columns >= N are 0; degree = the row popcounts.  normalize: rows through x / max(||x||, 1e-12)
+    first, so that the products are cosines and the test is sklearn's 1 - cos <= eps (an all-zero row stays zero: no neighbour,
+    not even itself).  x (N, D); a row-strided view is passed as it is.  adj is the only device memory that scales with N^2."""
+    eps = float(eps)
+    if not 0.0 < eps <= 2.0:
+        raise ValueError(f"eps: expected a cosine distance in (0, 2], got {eps}")
+    xr = _phrase_sim_rows(x, "x")
+    N, D = xr.shape
+    W = dbscan_words(N)
+    if normalize:
+        xr = _unit_rows(xr.contiguous(), N, D)
+    adj = torch.empty(N, W, device=xr.device, dtype=torch.int32)
+    degree = torch.empty(N, device=xr.device, dtype=torch.int32)
+    call("tag_dbscan_graph", ptr(xr), xr.stride(0), 1.0 - eps, ptr(adj), ptr(degree), N, D)
+    return adj, degree
+
+
+def dbscan_core(degree, min_samples):
+    """core_bits int32 (W,): bit i % 32 of word i // 32 = [degree[i] >= min_samples]."""
+    if not degree.is_cuda:
+        _chk(degree, "degree")
+    if degree.dim() != 1 or degree.shape[0] < 1:
+        raise RuntimeError(f"degree: expected int32 (N >= 1,), got {degree.dtype} {tuple(degree.shape)}")
+    N = degree.shape[0]
+    _dbscan_ints(degree, "degree", (N,), None)
+    core_bits = torch.empty(dbscan_words(N), device=degree.device, dtype=torch.int32)
+    call("tag_dbscan_core", ptr(degree), int(min_samples), ptr(core_bits), N)
+    return core_bits
+
+
+def dbscan_hook(adj, core_bits, f_in, f_out, changed, check=True):
+    """One FastSV pass on the parent array: f_out (written in place) from f_in, both int32 (N,) and distinct; ``changed`` (one
+    int32 on the device) becomes 1 if f_out differs from f_in, else 0.  Every value of f_in must be a row index (check: one torch
+    min / max with a host read).  Returns f_out."""
+    N, _ = _dbscan_graph_args(adj, core_bits)
+    _dbscan_ints(f_in, "f_in", (N,), adj)
+    _dbscan_ints(f_out, "f_out", (N,), adj, " (it is written in place)")
+    _dbscan_ints(changed, "changed", (1,), adj, " (it is written in place)")
+    if f_in.data_ptr() == f_out.data_ptr():
+        raise RuntimeError("f_out: expected a buffer other than f_in (a pass reads f_in only)")
+    if check:
+        lo, hi = (int(v) for v in torch.stack((f_in.min(), f_in.max())).tolist())
+        if lo < 0 or hi >= N:
+            raise RuntimeError(f"f_in: values must lie in [0, {N}), got min {lo}, max {hi}")
+    call("tag_dbscan_hook", ptr(adj), ptr(core_bits), ptr(f_in), ptr(f_out), ptr(changed), N)
+    return f_out
+
+
+def dbscan_roots(adj, core_bits, f):
+    """root int32 (N,): f[i] for a core row; for any other row the smallest f[j] over its core neighbours j, or -1 (noise)."""
+    N, _ = _dbscan_graph_args(adj, core_bits)
+    _dbscan_ints(f, "f", (N,), adj)
+    root = torch.empty(N, device=adj.device, dtype=torch.int32)
+    call("tag_dbscan_roots", ptr(adj), ptr(core_bits), ptr(f), ptr(root), N)
+    return root

@@ -241,6 +241,11 @@ _SIGS = {
     "tag_kmeans_update_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tag_kmeans_update": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "tag_kmeans_seed_step": (c_int, [P, c_int, P, P, c_int, c_int, c_int, P]),
+    "tag_dbscan_words": (c_int, [c_int]),
+    "tag_dbscan_graph": (c_int, [P, c_int, c_float, P, P, c_int, c_int, P]),
+    "tag_dbscan_core": (c_int, [P, c_int, P, c_int, P]),
+    "tag_dbscan_hook": (c_int, [P, P, P, P, P, c_int, P]),
+    "tag_dbscan_roots": (c_int, [P, P, P, P, c_int, P]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
-"""k-means over phrase embeddings on the device: what python_scripts/clustering/kmeans_emb.py of the reference does with sklearn
-on the host.  It makes the ``cluster_map`` JSON that ``AudioSamplePhrasesDataset(neg_samp_stratg="clustering")`` reads and the
-cluster model that ``KmeansMappingDataset`` / ``KmeansMappingEvalDataset`` turn phrases into class indices with.
+"""k-means and DBSCAN over phrase embeddings on the device: what python_scripts/clustering/kmeans_emb.py and dbscan_emb.py of the
+reference do with sklearn on the host.  ``DBSCAN`` / ``dbscan_cluster_map`` (csrc/dbscan.hip) are described at the class; their
+cluster map feeds the same ``neg_samp_stratg="clustering"`` and ``SpectralMappingDataset`` / ``SpectralMappingEvalDataset``.
+k-means makes the ``cluster_map`` JSON that ``AudioSamplePhrasesDataset(neg_samp_stratg="clustering")`` reads and the cluster model that ``KmeansMappingDataset`` / ``KmeansMappingEvalDataset`` turn phrases into class indices with.
 
 ``KMeans`` runs Lloyd's algorithm on three entry points of csrc/kmeans.hip (``ops.kmeans_assign`` / ``kmeans_update`` /
 ``kmeans_seed_step``): no (N, K) matrix exists on the device and two fits from the same start give the same bits.  The stopping
@@ -242,3 +243,73 @@ def kmeans_cluster_map(phrase_to_emb: Mapping[str, np.ndarray], n_clusters: int,
     model = KMeans(n_clusters, **kw)
     labels = model.fit_predict(embs)
     return {"score": model.inertia_, "model": model, "result": cluster_map_from_labels(phrases, labels)}
+
+
+class DBSCAN:
+    """sklearn-shaped DBSCAN over the cosine distance on the device: what python_scripts/clustering/dbscan_emb.py of the reference
+    does with ``DBSCAN(metric="precomputed")`` on ``(1 - cosine_similarity).clip(0)``, without the N x N float matrix (the graph
+    is N^2 / 8 bytes of bits, csrc/dbscan.hip).  The labels are sklearn's own, not merely the same partition:
+
+    * neighbours: ``u_i . u_j >= 1 - eps`` with ``u = x / max(||x||, 1e-12)``, the diagonal computed like any pair (an all-zero
+      row has no neighbour, not even itself: noise);
+    * a row is core when it has at least ``min_samples`` neighbours; the clusters are the connected components of the core-core
+      graph (FastSV hooking on a parent array, ``n_passes_`` passes of ``ops.dbscan_hook`` with one host read each);
+    * a row that is not core takes the cluster with the lowest root (= lowest core index) among its core neighbours -- sklearn
+      grows its clusters one at a time in that order --, or -1 without one;
+    * the clusters are numbered in ascending order of their roots.
+
+    After ``fit``: ``labels_`` (numpy int64, -1 = noise), ``core_sample_indices_`` (numpy int64), ``n_passes_``.  ``sample_weight``
+    and other metrics are not offered."""
+
+    def __init__(self, eps=0.5, min_samples=5, device=None):
+        self.eps = float(eps)
+        self.min_samples = int(min_samples)
+        self.device = "cuda:0" if device is None else device
+        if not 0.0 < self.eps <= 2.0:
+            raise ValueError(f"eps: expected a cosine distance in (0, 2], got {eps}")
+        if self.min_samples < 1:
+            raise ValueError(f"min_samples must be >= 1 (got {min_samples})")
+        self.labels_: Optional[np.ndarray] = None
+        self.core_sample_indices_: Optional[np.ndarray] = None
+        self.n_passes_: Optional[int] = None
+
+    def fit(self, x):
+        from .. import ops
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.array(x, dtype=np.float32, order="C"))       # (a copy: the caller's array may be read-only)
+        x = x.to(device=self.device, dtype=torch.float32)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"x: expected a (N >= 1, D >= 1) matrix, got {tuple(x.shape)}")
+        N = x.shape[0]
+        adj, degree = ops.dbscan_graph(x, eps=self.eps, normalize=True)
+        core_bits = ops.dbscan_core(degree, self.min_samples)
+        f = torch.arange(N, device=x.device, dtype=torch.int32)
+        g = torch.empty_like(f)
+        changed = torch.empty(1, device=x.device, dtype=torch.int32)
+        passes = 0
+        while True:
+            ops.dbscan_hook(adj, core_bits, f, g, changed, check=False)
+            f, g = g, f
+            passes += 1
+            if not int(changed):                    # the pass's one host read
+                break
+        root = ops.dbscan_roots(adj, core_bits, f).long()
+        roots = torch.unique(root[root >= 0])       # ascending
+        labels = torch.where(root >= 0, torch.searchsorted(roots, root.clamp(min=0)), torch.full_like(root, -1))
+        self.labels_ = labels.cpu().numpy()
+        self.core_sample_indices_ = torch.nonzero(degree >= self.min_samples).flatten().cpu().numpy()
+        self.n_passes_ = passes
+        return self
+
+    def fit_predict(self, x):
+        return self.fit(x).labels_
+
+
+def dbscan_cluster_map(phrase_to_emb: Mapping[str, np.ndarray], eps: float = 0.5, min_samples: int = 5, device=None):
+    """The reference's ``Runner().dbscan`` on a {phrase: embedding} table -> {"result": {str(label): [phrases ...]} with the keys
+    in order of first appearance and noise under "-1", "model": the fitted DBSCAN}."""
+    phrases = list(phrase_to_emb)
+    embs = np.stack([np.asarray(phrase_to_emb[p], dtype=np.float32).reshape(-1) for p in phrases])
+    model = DBSCAN(eps=eps, min_samples=min_samples, device=device)
+    labels = model.fit_predict(embs)
+    return {"result": cluster_map_from_labels(phrases, labels), "model": model}
