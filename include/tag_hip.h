@@ -1138,6 +1138,24 @@ int tag_dbscan_core(const int* degree, int min_samples, int* core_bits, int N, v
 int tag_dbscan_hook(const int* adj, const int* core_bits, const int* f_in, int* f_out, int* changed, int N, void* stream);
 int tag_dbscan_roots(const int* adj, const int* core_bits, const int* f, int* root, int N, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Operating-point counts of the grounding evaluation (grounding_eval.hip; utils/eval_util.py:296-330 and :136-225 of the
+ * reference, as utils/grounding_eval.py restates them on the host): one launch behind tag_segments, one wave per
+ * (clip, threshold) pair.  regions (B,NT,max_regions,2) int64 rows [onset, offset) in frames and counts (B,NT) int32 are
+ * tag_segments' outputs; gt (B,max_gt,2) double [onset, offset] in seconds, gt_count (B) int32 rows in use per clip.
+ * out (B,NT,4) int32 = {tp_preds, tp_refs, psds_tp, psds_fp} of the pair taken as one file: the integers that
+ * evaluate_detections (tp_preds, tp_refs) and psds_operating_point (psds_tp, psds_fp) of utils/grounding_eval.py add up, with
+ * det = regions * time_resolution in fp64 -- EXACTLY theirs: fp64 with IEEE division and numpy's order of additions (the
+ * file's header states the rule; no floating-point value crosses lanes).  No detection: all four 0; no ground truth:
+ * psds_fp = the number of detections, the rest 0.  EVERY entry of out is written.  counts[b][t] > max_regions and
+ * gt_count[b] > max_gt (or negative values) are clamped, never read out of bounds.  Rows beyond the counts are not read.
+ * TAG_EINVAL before any launch: a null pointer (gt may be null when max_gt == 0), B or NT < 1, B * NT above 2^31 - 1,
+ * max_regions outside 1 .. 32768, max_gt outside 0 .. 128, time_resolution <= 0, dtc or gtc outside [0, 1].
+ * ------------------------------------------------------------------------------------------- */
+int tag_grounding_counts(const int64_t* regions, const int32_t* counts, int max_regions, const double* gt,
+                         const int32_t* gt_count, int max_gt, int B, int NT, double time_resolution, double dtc, double gtc,
+                         int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

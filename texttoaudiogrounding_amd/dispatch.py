@@ -2416,3 +2416,57 @@ def dbscan_roots(adj, core_bits, f):
     root = torch.empty(N, device=adj.device, dtype=torch.int32)
     call("tag_dbscan_roots", ptr(adj), ptr(core_bits), ptr(f), ptr(root), N)
     return root
+
+
+# ------------------------------------------------------------------------------------------------
+# operating-point counts of the grounding evaluation (utils/grounding_eval.py on the host), grounding_eval.hip
+# ------------------------------------------------------------------------------------------------
+
+def _grounding_tensor(t, name, dtype, shape, like, what):
+    """A device tensor as it is, a host tensor or array copied over (the ground truth comes from the dataset, on the host)."""
+    t = torch.as_tensor(t)
+    if t.dtype != dtype or tuple(t.shape) != shape:
+        raise RuntimeError(f"{name}: expected {dtype} {shape}{what}, got {t.dtype} {tuple(t.shape)}")
+    return t.to(like.device).contiguous()
+
+
+def grounding_counts(regions, counts, gt, gt_count, time_resolution, dtc=0.5, gtc=0.5, out=None, check=True):
+    """``segments``' outputs + the clips' ground truths -> (B, NT, 4) int32 ``{tp_preds, tp_refs, psds_tp, psds_fp}`` per (clip,
+    threshold): the integers utils.grounding_eval.evaluate_detections and psds_operating_point add up for that clip as one file,
+    exactly (fp64, numpy's order of additions; grounding_eval.hip).  regions (B,NT,maxK,2) int64 and counts (B,NT) int32 on the
+    device; gt (B,Gmax,2) float64 [onset, offset] seconds and gt_count (B,) int32 rows in use, on the device or on the host
+    (utils.device_eval.ground_truth_arrays), Gmax <= 128 (0: no clip has a ground truth).  Every entry of ``out`` (given or
+    new) is written.  check: refuse gt_count outside [0, Gmax] and counts outside [0, maxK] (ONE host read); the kernel clamps
+    them either way."""
+    if not regions.is_cuda:
+        _chk(regions, "regions")
+    if regions.dtype != torch.int64 or regions.dim() != 4 or regions.shape[3] != 2 or not regions.is_contiguous():
+        raise RuntimeError(f"regions: expected the contiguous int64 (B,NT,maxK,2) of ops.segments, got {regions.dtype} "
+                           f"{tuple(regions.shape)}")
+    B, NT, maxk, _ = regions.shape
+    counts = _grounding_tensor(counts, "counts", torch.int32, (B, NT), regions, " (ops.segments)")
+    gt = torch.as_tensor(gt)
+    if gt.dim() != 3 or gt.shape[2] != 2:
+        raise RuntimeError(f"gt: expected float64 ({B},Gmax,2), got {gt.dtype} {tuple(gt.shape)}")
+    max_gt = gt.shape[1]
+    if B < 1 or NT < 1:
+        raise RuntimeError(f"grounding_counts: expected B, NT >= 1, got {B}, {NT}")
+    gt_count = torch.as_tensor(gt_count)
+    if gt_count.dtype != torch.int32 or tuple(gt_count.shape) != (B,):
+        raise RuntimeError(f"gt_count: expected {torch.int32} ({B},), got {gt_count.dtype} {tuple(gt_count.shape)}")
+    if check:
+        ends = [counts.min(), counts.max()] + ([gt_count.min(), gt_count.max()] if gt_count.is_cuda else [])
+        lo_c, hi_c, *g_ends = torch.stack(ends).tolist()
+        lo_g, hi_g = g_ends or (int(gt_count.min()), int(gt_count.max()))
+        if lo_g < 0 or hi_g > max_gt or lo_c < 0 or hi_c > maxk:
+            raise RuntimeError(f"grounding_counts: gt_count must lie in [0, {max_gt}] and counts in [0, {maxk}], got "
+                               f"[{lo_g}, {hi_g}] and [{lo_c}, {hi_c}]")
+    gt = _grounding_tensor(gt, "gt", torch.float64, (B, max_gt, 2), regions, "")
+    gt_count = gt_count.to(regions.device).contiguous()
+    if out is None:
+        out = torch.empty(B, NT, 4, device=regions.device, dtype=torch.int32)
+    elif not out.is_cuda or out.dtype != torch.int32 or tuple(out.shape) != (B, NT, 4) or not out.is_contiguous():
+        raise RuntimeError(f"out: expected contiguous int32 ({B},{NT},4) on the device, got {out.dtype} {tuple(out.shape)}")
+    call("tag_grounding_counts", ptr(regions), ptr(counts), maxk, ptr(gt) if max_gt else None, ptr(gt_count), max_gt, B, NT,
+         float(time_resolution), float(dtc), float(gtc), ptr(out))
+    return out

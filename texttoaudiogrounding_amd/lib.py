@@ -246,6 +246,7 @@ _SIGS = {
     "tag_dbscan_core": (c_int, [P, c_int, P, c_int, P]),
     "tag_dbscan_hook": (c_int, [P, P, P, P, P, c_int, P]),
     "tag_dbscan_roots": (c_int, [P, P, P, P, c_int, P]),
+    "tag_grounding_counts": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, c_double, P, P]),
 }
 
 _lib = None

@@ -11,11 +11,13 @@ from __future__ import annotations
 import os
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import ops
 from .losses import ClipBceLoss, ClipMaskedFrameBceLoss, FrameBceLoss, MaxMarginRankingLoss
+from .utils import device_eval, eval_util
 from .utils.train_util import init_obj_from_str
 
 #: batch entries that hold token ids or masks (DictTokenizer's ``text``, HuggingFaceTokenizer's ``input_ids`` / ``attention_mask``):
@@ -329,6 +331,41 @@ class StrongRunner:
         ops.check_async_errors()
         return v
 
+    def _eval_frame_sim(self, output: Dict, batch: Dict) -> torch.Tensor:
+        """The (B, T) scores ``evaluate`` segments: one row per (clip, phrase) pair of the batch."""
+        return output["frame_sim"]
+
+    def evaluate(self, batches, ground_truth: Dict, durations: Dict, eval_config: Dict) -> Dict:
+        """Runner.eval_inference + compute_th_auc / compute_psds of run_strong.py:171-276 with the metric arithmetic on the
+        device (utils/device_eval.py): the model in eval() under no_grad over ``batches`` (dicts with ``audiocap_id`` and
+        ``start_index`` beside the model's inputs), every pair keyed ``f"{audiocap_id}_{start_index}"``.  ground_truth: {key:
+        [[onset, offset], ...]} seconds; a pair whose key has no row left after the (0, 0) rows are dropped is left out, as
+        :223-224 leaves it out.  durations: {key: seconds of audio}, summed over the keys of ``ground_truth`` for the PSDS.
+        eval_config: ``n_thresholds``, ``window_size`` and ``time_resolution``, optionally ``dtc_threshold``, ``gtc_threshold``,
+        ``max_efpr``, ``beta``, ``min_threshold``, ``max_threshold``.  One host read at the end.  Returns
+        GroundingEvaluator.compute's dict; counts summed over this rank's batches only."""
+        ev = device_eval.GroundingEvaluator(eval_util.eval_thresholds(int(eval_config.get("n_thresholds", 50))),
+                                            int(eval_config.get("window_size", 1)), float(eval_config["time_resolution"]),
+                                            dtc=eval_config.get("dtc_threshold", 0.5), gtc=eval_config.get("gtc_threshold", 0.5),
+                                            device=self.device)
+        self.model.eval()
+        with torch.no_grad():
+            for batch in batches:
+                keys = [f"{a}_{s}" for a, s in zip(batch["audiocap_id"], batch["start_index"])]
+                gt, gt_count = device_eval.ground_truth_arrays([ground_truth.get(k, ()) for k in keys])
+                keep = np.flatnonzero(gt_count)
+                if keep.size == 0:
+                    continue
+                frame_sim = self._eval_frame_sim(self.forward(batch, training=False), batch)
+                if keep.size != len(keys):
+                    frame_sim = frame_sim.index_select(0, torch.as_tensor(keep).to(frame_sim.device))
+                ev.update(frame_sim, gt[keep], gt_count[keep])
+        result = ev.compute(float(sum(durations[k] for k in ground_truth)), max_efpr=eval_config.get("max_efpr"),
+                            beta=eval_config.get("beta", 1.0), min_threshold=eval_config.get("min_threshold", 0.0),
+                            max_threshold=eval_config.get("max_threshold", 1.0))
+        ops.check_async_errors()
+        return result
+
 
 class ClassMappingRunner(StrongRunner):
     """Training-step driver of the class-mapping baseline (Runner.forward of python_scripts/training/mapping_to_class/
@@ -358,6 +395,11 @@ class ClassMappingRunner(StrongRunner):
                 output.update({"frame_sim": frame_sim, "strong_label": strong_label,
                                "length": torch.clamp(output["length"], 1, tt)})
         return output
+
+    def _eval_frame_sim(self, output: Dict, batch: Dict) -> torch.Tensor:
+        """mapping_to_class/run_strong.py:209: ``frame_sim[idx, :, text_idx]``, the scores of each pair's queried class (the
+        range check of the class indices is a host read per batch)."""
+        return eval_util.class_frame_sim(output["frame_sim"], batch["text_idx"])
 
 
 class WeakSentenceRunner(StrongRunner):

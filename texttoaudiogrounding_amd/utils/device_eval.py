@@ -1,0 +1,107 @@
+"""Grounding evaluation with the operating-point arithmetic on the device: the counterpart of Runner.eval_inference +
+compute_th_auc / compute_psds of the reference (python_scripts/training/run_strong.py:171-276, utils/eval_util.py:136-330).
+
+``eval_util.segments_for_thresholds`` -> ``grounding_eval.tables_from_segments`` -> ``compute_th_auc`` / ``psds_intersection``
+is the host path: it copies every segment of every (clip, threshold) pair to the host and walks files x thresholds in Python.
+Here ``ops.segments`` and ``ops.grounding_counts`` (csrc/grounding_eval.hip) leave four integers per pair on the device, a batch
+adds them into ONE (NT, 6) int64 tensor, and ``compute`` reads that tensor once.  The host functions of grounding_eval.py stay
+the yardstick: the counts are theirs exactly, so precision, recall, th-AUC and PSDS are equal as floats.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import ops
+from . import eval_util
+from .grounding_eval import EPS, GroundingPrecisionRecall, psd_roc, staircase_auc
+
+MAX_GROUND_TRUTHS = 128          # rows per (clip, phrase) pair tag_grounding_counts takes
+
+
+def ground_truth_arrays(items: Sequence[Sequence[Sequence[float]]]):
+    """A batch's ground truths, a list over the pairs of ``[[onset, offset], ...]`` seconds -> (gt (B, Gmax, 2) float64 padded
+    with zeros, gt_count (B,) int32), on the host.  ``(0, 0)`` rows are dropped as run_strong.py:186-187 drops them; more than
+    128 rows for one pair raise."""
+    rows = [[(float(on), float(off)) for on, off in item if not (on == 0 and off == 0)] for item in items]
+    gmax = max((len(r) for r in rows), default=0)
+    if gmax > MAX_GROUND_TRUTHS:
+        raise ValueError(f"ground_truth_arrays: a pair has {gmax} ground-truth rows; the device evaluation takes at most "
+                         f"{MAX_GROUND_TRUTHS}")
+    gt = np.zeros((len(rows), gmax, 2), dtype=np.float64)
+    for b, r in enumerate(rows):
+        if r:
+            gt[b, :len(r)] = r
+    return gt, np.array([len(r) for r in rows], dtype=np.int32)
+
+
+class GroundingEvaluator:
+    """Accumulates the operating points of ``thresholds`` over batches on the device and turns them into th-AUC and PSDS.
+
+    ``counts`` is an (NT, 6) int64 device tensor: tp_preds, tp_refs, psds_tp, psds_fp, n_preds, n_refs per threshold, summed
+    over every pair passed to ``update`` (a data-parallel caller all-reduces it before ``compute``).  A pair is one file of the
+    host tables, so the sums are what ``evaluate_detections`` and ``psds_operating_point`` count over a table that holds every
+    pair once and whose ground-truth table holds exactly those pairs.
+
+    Thresholds must be strictly ascending.  The reference's ``add_operating_point`` (restated in
+    ``GroundingPrecisionRecall.add_operating_point``) does not evaluate a detection table equal to ANY earlier one: it appends a
+    copy of the LAST row.  With ascending thresholds that cannot change a value: binarize (score > threshold), the median
+    filter of a 0/1 sequence and connect_clusters are monotone, so the active frames at a higher threshold are a subset of
+    those at a lower one; the sets between two equal tables are squeezed between equal sets, so a table equal to an earlier one
+    equals the one immediately before it, whose row is the last row -- the copy is the value the evaluation would give.  Plain
+    per-threshold evaluation, which is what the counts are, therefore gives the reference's th-AUC.
+    """
+
+    def __init__(self, thresholds, window_size: int, time_resolution: float, dtc: float = 0.5, gtc: float = 0.5, device="cuda"):
+        th = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+        if th.size == 0 or not np.all(np.diff(th) > 0):
+            raise ValueError("GroundingEvaluator: thresholds must be strictly ascending (and not empty)")
+        if not 0.0 <= dtc <= 1.0 or not 0.0 <= gtc <= 1.0:
+            raise ValueError("GroundingEvaluator: dtc and gtc must be between 0 and 1")
+        if not time_resolution > 0:
+            raise ValueError("GroundingEvaluator: time_resolution must be positive")
+        self.thresholds = th
+        self.window_size, self.time_resolution = int(window_size), float(time_resolution)
+        self.n_connect = eval_util.n_connect_for(self.time_resolution)
+        self.dtc, self.gtc = float(dtc), float(gtc)
+        self.device = torch.device(device)
+        self._th = torch.as_tensor(th).to(self.device)
+        self.counts = torch.zeros(th.size, 6, device=self.device, dtype=torch.int64)
+
+    def reset(self):
+        self.counts.zero_()
+
+    def update(self, frame_sim: torch.Tensor, gt, gt_count):
+        """frame_sim (B, T) float32 on the device; gt, gt_count as ``ground_truth_arrays`` returns them (host arrays are
+        checked here and copied over; device tensors are taken as they are).  No host read."""
+        gt, gt_count = torch.as_tensor(gt), torch.as_tensor(gt_count)
+        if not gt_count.is_cuda and gt_count.numel() and (int(gt_count.min()) < 0 or int(gt_count.max()) > gt.shape[1]):
+            raise ValueError(f"gt_count must lie in [0, {gt.shape[1]}]")
+        gt_count = gt_count.to(self.device)
+        regions, counts = ops.segments(frame_sim, self._th, self.window_size, self.n_connect)
+        out = ops.grounding_counts(regions, counts, gt, gt_count, self.time_resolution, self.dtc, self.gtc, check=False)
+        self.counts[:, :4] += out.sum(0)
+        self.counts[:, 4] += counts.sum(0)
+        self.counts[:, 5] += gt_count.sum()
+
+    def compute(self, total_duration_s: float, max_efpr: Optional[float] = None, beta: float = 1.0, min_threshold: float = 0.0,
+                max_threshold: float = 1.0) -> dict:
+        """ONE host read of ``counts`` -> {"th_auc", "psds", "precision" (NT), "recall" (NT), "thresholds"}: the expressions of
+        ``evaluate_detections``, ``GroundingPrecisionRecall.th_auc``, ``psds_operating_point`` and ``psds_intersection`` on the
+        summed integers.  total_duration_s: seconds of audio of the evaluated files (the PSDS metadata)."""
+        rows = self.counts.cpu().tolist()
+        ev = GroundingPrecisionRecall(self.dtc, self.gtc, {})
+        points = []
+        for th, (tp_preds, tp_refs, psds_tp, psds_fp, n_preds, n_refs) in zip(self.thresholds, rows):
+            ev.operating_points.append({"precision": tp_preds / max(n_preds, EPS), "recall": tp_refs / max(n_refs, EPS),
+                                        "threshold": float(th)})
+            points.append((psds_tp / max(n_refs, EPS), psds_fp / (total_duration_s / 3600.0)))
+        x, y = psd_roc(points)
+        if max_efpr is None:
+            max_efpr = float(x.max())
+        psds = float(y.max()) if max_efpr <= 0 else staircase_auc(x, y, max_efpr) / max_efpr
+        return {"th_auc": ev.th_auc(beta=beta, low_th=min_threshold, high_th=max_threshold), "psds": psds,
+                "precision": np.array([r["precision"] for r in ev.operating_points]),
+                "recall": np.array([r["recall"] for r in ev.operating_points]), "thresholds": self.thresholds.copy()}
