@@ -200,7 +200,9 @@ __global__ __launch_bounds__(64 * logmel_waves<NFFT>()) void logmel_kernel(const
         const float* x = wave + (size_t)b * S;
         const int start = t * hop - NFFT / 2;
         c32 v[NB0][R0];
-        if (start >= 0 && start + NFFT <= S && ((((size_t)b * S + start) & 1) == 0)) {
+        // 8-byte loads only where the ADDRESS is 8-byte aligned: the base pointer may itself be only 4-byte aligned (a
+        // contiguous view at an odd element offset), so the parity of the index says nothing
+        if (start >= 0 && start + NFFT <= S && (reinterpret_cast<uintptr_t>(x + start) & 7) == 0) {
             const float2* x2 = reinterpret_cast<const float2*>(x + start);
 #pragma unroll
             for (int bb = 0; bb < NB0; ++bb)

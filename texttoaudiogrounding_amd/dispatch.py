@@ -43,6 +43,15 @@ def waveform_f16_to_f32_padded(clips, device, length=None):
 
 def logmel(wave, n_fft, win_length, hop, window, fb, want_power=False):
     wave = _chk(wave, "waveform")
+    window, fb = _chk(window, "window"), _chk(fb, "fb")      # the kernel reads both as dense row-major tables
+    if wave.dim() != 2:
+        raise RuntimeError(f"logmel: waveform must be (B, S), got {tuple(wave.shape)}")
+    if window.numel() != win_length:
+        raise RuntimeError(f"logmel: window must hold win_length = {win_length} values, got {tuple(window.shape)}")
+    if fb.dim() != 2 or fb.shape[0] != n_fft // 2 + 1:
+        raise RuntimeError(f"logmel: fb must be (n_fft // 2 + 1, n_mels) = ({n_fft // 2 + 1}, n_mels), got {tuple(fb.shape)}")
+    if hop <= 0:
+        raise RuntimeError(f"logmel: hop must be positive, got {hop}")
     B, S = wave.shape
     Fr = S // hop + 1
     n_mels = fb.shape[1]
