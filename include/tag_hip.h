@@ -1139,6 +1139,42 @@ int tag_dbscan_hook(const int* adj, const int* core_bits, const int* f_in, int* 
 int tag_dbscan_roots(const int* adj, const int* core_bits, const int* f, int* root, int N, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Device average-linkage clustering over the cosine distance (agc.hip; python_scripts/clustering/agc_emb.py of the reference runs
+ * sklearn's AgglomerativeClustering(linkage="average") on the N x N float matrix 1 - cosine_similarity on the host).  For unit rows
+ * the average distance of two clusters is 1 - m_A . m_B, m = (sum of the cluster's rows) / size, so a cluster is its fp64 sum
+ * vector and its fp32 mean, and all reciprocal-nearest-neighbour pairs of a round merge at once (average linkage is reducible:
+ * the dendrogram is the serial one).  A fit is rounds of tag_agc_nearest + tag_agc_merge on M = N, ..., 1 clusters.  Device memory
+ * of a fit at (N, D): two (N, D) fp64 sum buffers and one (N, D) fp32 mean buffer (20 N D bytes), two sets of sizes (int64) and
+ * node ids (int32), nn, dist, the log (16 (N - 1) bytes) and the two workspaces (at most 8 x 23 N and 8 N bytes): nothing scales
+ * with N^2.  Every *_ws_bytes is a function of the shape alone (0 for a shape the call would refuse); ws is never zeroed; no
+ * atomics, no cooperative launch, no device-side waiting: the same bits on every run.
+ *
+ * tag_agc_nearest: m (M, D) fp32 with row stride ldm >= D (floats).  nn[i] (int32) = the j != i with the largest m_i . m_j,
+ *   dist[i] (fp32) = 1 - m_i . m_nn[i]; the products fp32 on the exact-fp32 MFMA with unrounded operands, the D tail zero-filled.
+ *   Ties go to the lowest j; a column >= M and the diagonal never win.  The scores are BIT-SYMMETRIC: score(i, j) == score(j, i)
+ *   (the same chain of k-steps in the same order for both, a product is commutative and nothing else scales a score), so the
+ *   lowest row that attains the largest score of the call and its nn name each other: every round of a fit merges a pair.
+ *   A workgroup owns 128 rows and one slice of the column tiles and leaves (score, index) per row and slice in ws; a second
+ *   launch folds the slices in slice order on (score, index).  The slice count depends on M alone.  No (M, M) array exists.
+ *   M = 1 writes nn = -1, dist = +inf; so does a row all of whose scores are NaN.
+ * tag_agc_merge: one round's bookkeeping.  Row a is the left half of a pair when b = nn[a] lies in [0, M), b != a, nn[b] == a and
+ *   a < b; with P pairs the output has M - P rows: the M - 2 P survivors in their relative order, then the merged clusters in
+ *   ascending a with sum = sum_a + sum_b (fp64, dense (M, D)), size = size_a + size_b (int64) and node id next_id + rank (int32).
+ *   means_out[o] = (float)(sum / size) is written for EVERY output row (row stride ldm); a pair of rank r writes
+ *   log_dist[log_off + r] = dist[a] and log_ids[log_off + r] = {id_a, id_b, next_id + r} (log_ids is (log_rows, 3) int32).
+ *   counts (2 x int32 on the device) = {P, M - P}: the round's one host read.  The *_out buffers differ from the inputs (rows
+ *   move); means_out may be the buffer nearest read.
+ * TAG_EINVAL before any launch, the numbers named in tag_last_error: M or D < 1, ldm < D, a null pointer, M above 2^31 - 129,
+ * an output that aliases its input, log_off or next_id negative or above 2^31 - 1 - M, log_off + M / 2 > log_rows.
+ */
+size_t tag_agc_nearest_ws_bytes(int M, int D);
+int tag_agc_nearest(const float* m, int ldm, int* nn, float* dist, int M, int D, void* ws, void* stream);
+size_t tag_agc_merge_ws_bytes(int M, int D);
+int tag_agc_merge(const int* nn, const float* dist, const double* sums_in, const long long* sizes_in, const int* ids_in,
+                  double* sums_out, long long* sizes_out, int* ids_out, float* means_out, int ldm, float* log_dist, int* log_ids,
+                  int log_rows, int log_off, int next_id, int* counts, int M, int D, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Operating-point counts of the grounding evaluation (grounding_eval.hip; utils/eval_util.py:296-330 and :136-225 of the
  * reference, as utils/grounding_eval.py restates them on the host): one launch behind tag_segments, one wave per
  * (clip, threshold) pair.  regions (B,NT,max_regions,2) int64 rows [onset, offset) in frames and counts (B,NT) int32 are

@@ -2428,6 +2428,91 @@ def dbscan_roots(adj, core_bits, f):
 
 
 # ------------------------------------------------------------------------------------------------
+# device average-linkage clustering (python_scripts/clustering/agc_emb.py in the reference runs sklearn on an N x N float
+# matrix), agc.hip
+# ------------------------------------------------------------------------------------------------
+
+def _agc_buf(t, name, dtype, shape, like, what=""):
+    if not t.is_cuda:
+        _chk(t, name)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or (like is not None and t.device != like.device):
+        on = f" on {like.device}" if like is not None else ""
+        raise RuntimeError(f"{name}: expected contiguous {dtype} {tuple(shape)}{on}{what}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def agc_nearest(means):
+    """(nn int32 (M,), dist fp32 (M,)): nn[i] = the j != i with the largest means[i] . means[j] on the exact-fp32 MFMA, ties to the
+    lowest j; dist[i] = 1 - that product.  means (M, D); a row-strided view is passed as it is.  The scores are bit-symmetric
+    (score(i, j) == score(j, i)).  M = 1 gives nn = -1, dist = +inf.  No (M, M) scores exist on the device."""
+    mr = _phrase_sim_rows(means, "means")
+    M, D = mr.shape
+    nn = torch.empty(M, device=mr.device, dtype=torch.int32)
+    dist = torch.empty(M, device=mr.device, dtype=F32)
+    ws = _ws(query("tag_agc_nearest_ws_bytes", M, D), mr)
+    call("tag_agc_nearest", ptr(mr), mr.stride(0), ptr(nn), ptr(dist), M, D, ptr(ws))
+    return nn, dist
+
+
+def agc_merge(nn, dist, sums, sizes, ids, sums_out, sizes_out, ids_out, means_out, log_dist, log_ids, counts, log_off, next_id):
+    """One round's bookkeeping on the first M = nn.shape[0] rows: row a is the left half of a pair when nn[nn[a]] == a and
+    a < nn[a].  The survivors go to the front of the ``*_out`` buffers in their relative order, the merged clusters follow in
+    ascending a with sum_a + sum_b (fp64), size_a + size_b (int64) and node id ``next_id + rank`` (int32); ``means_out`` rows
+    (fp32, row-strided or not) = sum / size for every output row; pair r writes ``log_dist[log_off + r] = dist[a]`` and
+    ``log_ids[log_off + r] = (id_a, id_b, next_id + r)``.  ``counts`` (2 int32 on the device) = (pairs, new M).  The buffers hold
+    at least M rows and are written in place; the ``*_out`` buffers differ from the inputs.  Returns counts (no host read)."""
+    if not nn.is_cuda:
+        _chk(nn, "nn")
+    if nn.dim() != 1 or nn.shape[0] < 1:
+        raise RuntimeError(f"nn: expected int32 (M >= 1,), got {nn.dtype} {tuple(nn.shape)}")
+    M = nn.shape[0]
+    _agc_buf(nn, "nn", torch.int32, (M,), None)
+    _agc_buf(dist, "dist", F32, (M,), nn)
+    for t, name in ((sums, "sums"), (sums_out, "sums_out")):
+        if not t.is_cuda:
+            _chk(t, name)
+        if (t.dtype != torch.float64 or t.dim() != 2 or t.shape[0] < M or t.shape[1] < 1 or not t.is_contiguous()
+                or t.device != nn.device):
+            raise RuntimeError(f"{name}: expected contiguous float64 (rows >= {M}, D >= 1) on {nn.device}, got {t.dtype} "
+                               f"{tuple(t.shape)} on {t.device}")
+    D = sums.shape[1]
+    if sums_out.shape[1] != D:
+        raise RuntimeError(f"sums_out: expected D = {D}, got {tuple(sums_out.shape)}")
+    for t, name, dtype in ((sizes, "sizes", torch.int64), (sizes_out, "sizes_out", torch.int64), (ids, "ids", torch.int32),
+                           (ids_out, "ids_out", torch.int32)):
+        if not t.is_cuda:
+            _chk(t, name)
+        if t.dtype != dtype or t.dim() != 1 or t.shape[0] < M or not t.is_contiguous() or t.device != nn.device:
+            raise RuntimeError(f"{name}: expected contiguous {dtype} (rows >= {M},) on {nn.device}, got {t.dtype} {tuple(t.shape)} on "
+                               f"{t.device}")
+    if not means_out.is_cuda:
+        _chk(means_out, "means_out")
+    if (means_out.dtype != F32 or means_out.dim() != 2 or means_out.shape[0] < M or means_out.shape[1] != D
+            or means_out.stride(1) != 1 or means_out.stride(0) < D or means_out.device != nn.device):
+        raise RuntimeError(f"means_out: expected a float32 (rows >= {M}, {D}) matrix with unit column stride on {nn.device} (it is "
+                           f"written in place), got {means_out.dtype} {tuple(means_out.shape)} strides {tuple(means_out.stride())} on "
+                           f"{means_out.device}")
+    if sums.data_ptr() == sums_out.data_ptr() or sizes.data_ptr() == sizes_out.data_ptr() or ids.data_ptr() == ids_out.data_ptr():
+        raise RuntimeError("sums_out, sizes_out, ids_out: expected buffers other than the inputs (rows move)")
+    if not log_dist.is_cuda:
+        _chk(log_dist, "log_dist")
+    if log_dist.dim() != 1:
+        raise RuntimeError(f"log_dist: expected float32 (rows,), got {log_dist.dtype} {tuple(log_dist.shape)}")
+    rows = log_dist.shape[0]
+    _agc_buf(log_dist, "log_dist", F32, (rows,), nn, " (it is written in place)")
+    _agc_buf(log_ids, "log_ids", torch.int32, (rows, 3), nn, " (it is written in place)")
+    _agc_buf(counts, "counts", torch.int32, (2,), nn, " (it is written in place)")
+    log_off, next_id = int(log_off), int(next_id)
+    if log_off < 0 or next_id < 0 or log_off + M // 2 > rows:
+        raise RuntimeError(f"log_off = {log_off}, next_id = {next_id}: expected both >= 0 and room for {M // 2} pairs in a log of "
+                           f"{rows} rows")
+    ws = _ws(query("tag_agc_merge_ws_bytes", M, D), nn)
+    call("tag_agc_merge", ptr(nn), ptr(dist), ptr(sums), ptr(sizes), ptr(ids), ptr(sums_out), ptr(sizes_out), ptr(ids_out),
+         ptr(means_out), means_out.stride(0), ptr(log_dist), ptr(log_ids), rows, log_off, next_id, ptr(counts), M, D, ptr(ws))
+    return counts
+
+
+# ------------------------------------------------------------------------------------------------
 # operating-point counts of the grounding evaluation (utils/grounding_eval.py on the host), grounding_eval.hip
 # ------------------------------------------------------------------------------------------------
 

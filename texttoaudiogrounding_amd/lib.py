@@ -246,6 +246,10 @@ _SIGS = {
     "tag_dbscan_core": (c_int, [P, c_int, P, c_int, P]),
     "tag_dbscan_hook": (c_int, [P, P, P, P, P, c_int, P]),
     "tag_dbscan_roots": (c_int, [P, P, P, P, c_int, P]),
+    "tag_agc_nearest_ws_bytes": (c_size_t, [c_int, c_int]),
+    "tag_agc_nearest": (c_int, [P, c_int, P, P, c_int, c_int, P, P]),
+    "tag_agc_merge_ws_bytes": (c_size_t, [c_int, c_int]),
+    "tag_agc_merge": (c_int, [P, P, P, P, P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, P, c_int, c_int, P, P]),
     "tag_grounding_counts": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, c_double, P, P]),
 }
 

@@ -1,5 +1,5 @@
-"""k-means and DBSCAN over phrase embeddings on the device: what python_scripts/clustering/kmeans_emb.py and dbscan_emb.py of the
-reference do with sklearn on the host.  ``DBSCAN`` / ``dbscan_cluster_map`` (csrc/dbscan.hip) are described at the class; their
+"""k-means, DBSCAN and average-linkage clustering over phrase embeddings on the device: what python_scripts/clustering/kmeans_emb.py,
+dbscan_emb.py and agc_emb.py of the reference do with sklearn on the host.  ``DBSCAN`` / ``dbscan_cluster_map`` (csrc/dbscan.hip) are described at the class; their
 cluster map feeds the same ``neg_samp_stratg="clustering"`` and ``SpectralMappingDataset`` / ``SpectralMappingEvalDataset``.
 k-means makes the ``cluster_map`` JSON that ``AudioSamplePhrasesDataset(neg_samp_stratg="clustering")`` reads and the cluster model that ``KmeansMappingDataset`` / ``KmeansMappingEvalDataset`` turn phrases into class indices with.
 
@@ -9,6 +9,12 @@ rules are sklearn's: stop when the labels equal the previous iteration's, or whe
 (then one more assignment so that ``labels_`` match the centres); ``n_iter_`` counts completed iterations.  An empty cluster
 takes the row with the largest squared distance to its centre (several empty clusters: the largest first), and that row
 leaves its donor cluster's sum and count before the division.
+
+``AgglomerativeClustering`` / ``agc_cluster_map`` (csrc/agc.hip) are python_scripts/clustering/agc_emb.py: average linkage over the
+cosine distance without the N x N matrix.  A cluster is the fp64 sum of its unit rows (the average distance of two clusters is
+1 - mean_A . mean_B), every round merges all reciprocal nearest neighbours at once (``ops.agc_nearest`` + ``ops.agc_merge``, one
+host read per round), and the host half (``agc_tree`` / ``agc_cut``, plain numpy, no GPU) orders the merges and cuts the tree as
+sklearn does; the class states when the labels are sklearn's own.
 
 Deviations from sklearn: ``"k-means++"`` is plain D^2 sampling with one candidate per step (no greedy multi-trial), x is not
 mean-centred before the fit, and the arithmetic is fp32 with fp64 cluster sums.
@@ -311,5 +317,169 @@ def dbscan_cluster_map(phrase_to_emb: Mapping[str, np.ndarray], eps: float = 0.5
     phrases = list(phrase_to_emb)
     embs = np.stack([np.asarray(phrase_to_emb[p], dtype=np.float32).reshape(-1) for p in phrases])
     model = DBSCAN(eps=eps, min_samples=min_samples, device=device)
+    labels = model.fit_predict(embs)
+    return {"result": cluster_map_from_labels(phrases, labels), "model": model}
+
+
+def agc_tree(heights, id_a, id_b, n_leaves):
+    """The host half of the agglomerative fit, numpy only: the merge log in the order the rounds wrote it (row r made node
+    ``n_leaves + r`` out of nodes ``id_a[r]`` and ``id_b[r]`` at ``heights[r]``) -> (children (N - 1, 2) int64, distances (N - 1,)
+    float64) as scipy / sklearn number a dendrogram: merges sorted by height, stably, node ``n_leaves + rank``, children as
+    (min, max).  Average linkage has no inversions, but a rounded height may fall an ulp below a child's: the sort key of a node
+    is the largest height on its subtree (``distances`` holds that key), so a child always precedes its parent."""
+    h = np.asarray(heights, dtype=np.float64).reshape(-1)
+    a = np.asarray(id_a, dtype=np.int64).reshape(-1)
+    b = np.asarray(id_b, dtype=np.int64).reshape(-1)
+    N = int(n_leaves)
+    if not (h.size == a.size == b.size == N - 1):
+        raise ValueError(f"a tree over {N} leaves has {N - 1} merges, got {h.size}, {a.size}, {b.size} log rows")
+    both = np.concatenate([a, b])
+    if N > 1 and not np.array_equal(np.sort(both), np.arange(2 * N - 2)):
+        raise ValueError("the merge log is not a binary tree: every node but the root must be merged exactly once")
+    if np.any(np.maximum(a, b) >= N + np.arange(N - 1)):
+        raise ValueError("the merge log is out of order: a row merges a node that a later row makes")
+    key = h.copy()
+    for r in np.flatnonzero(np.maximum(a, b) >= N):             # (leaf-leaf merges keep their height)
+        for c in (a[r], b[r]):
+            if c >= N and key[c - N] > key[r]:
+                key[r] = key[c - N]
+    order = np.argsort(key, kind="stable")
+    rank = np.empty(N - 1, dtype=np.int64)
+    rank[order] = np.arange(N - 1)
+
+    def renumber(ids):
+        return np.where(ids >= N, N + rank[np.clip(ids - N, 0, max(N - 2, 0))], ids) if N > 1 else ids
+
+    ca, cb = renumber(a)[order], renumber(b)[order]
+    return np.stack([np.minimum(ca, cb), np.maximum(ca, cb)], axis=1).reshape(N - 1, 2), key[order]
+
+
+def agc_cut(children, n_leaves, n_clusters):
+    """The flat clustering sklearn's ``_hc_cut`` reads off a tree: a heap of negated node ids that starts at the root and
+    ``n_clusters - 1`` times replaces its largest node by that node's two children; label i goes to the leaves under the i-th
+    entry of the heap's list.  -> (n_leaves,) int64."""
+    import heapq
+    N, K = int(n_leaves), int(n_clusters)
+    if not 1 <= K <= N:
+        raise ValueError(f"n_clusters = {K}: expected 1 .. {N} for a tree with {N} leaves")
+    children = np.asarray(children, dtype=np.int64).reshape(N - 1, 2)
+    labels = np.zeros(N, dtype=np.int64)
+    if N == 1:
+        return labels
+    nodes = [-(2 * N - 2)]
+    for _ in range(K - 1):
+        left, right = children[-nodes[0] - N]
+        heapq.heappush(nodes, -int(left))
+        heapq.heappushpop(nodes, -int(right))
+    for i, node in enumerate(nodes):
+        stack = [-node]
+        while stack:
+            n = stack.pop()
+            if n < N:
+                labels[n] = i
+            else:
+                stack.extend(children[n - N].tolist())
+    return labels
+
+
+class AgglomerativeClustering:
+    """sklearn-shaped average-linkage clustering over the cosine distance on the device: what python_scripts/clustering/agc_emb.py of
+    the reference does with ``AgglomerativeClustering(n_clusters, linkage="average", affinity="precomputed")`` on
+    ``1 - cosine_similarity``, without the N x N float matrix (csrc/agc.hip; device memory about 20 N D bytes).
+
+    * rows: ``u = x / max(||x||, 1e-12)``; a cluster is the fp64 sum of its rows and its fp32 mean, and the distance of two
+      clusters is ``1 - mean_A . mean_B`` in fp32 (error about (D + 6) 2^-24);
+    * a round merges every pair of clusters that are each other's nearest (``ops.agc_nearest``, ``ops.agc_merge``); average
+      linkage is reducible, so the set of merges and their heights are those of the serial algorithm; ``n_rounds_`` rounds with
+      one host read each, and the merge log is read once;
+    * the merges are sorted by height, numbered and cut as scipy and sklearn do (``agc_tree``, ``agc_cut``).
+
+    The labels are sklearn's own, element for element, where the top ``n_clusters`` merge heights are separated by more than the
+    fp32 error of a height.  Under exact ties (duplicate phrases, say) the result is still a valid average-linkage cut, but the
+    order of tied merges is scipy's nearest-neighbour-chain order, which is not reproduced, so labels may be permuted or tied
+    merges resolved differently.
+
+    Only ``linkage="average"`` is offered (anything else raises ValueError).  After ``fit``: ``labels_`` (numpy int64),
+    ``children_`` ((N - 1, 2) int64), ``distances_`` ((N - 1,) float64, ascending), ``n_leaves_``, ``n_rounds_``;
+    ``labels_for(k)`` re-cuts the stored tree."""
+
+    def __init__(self, n_clusters=2, linkage="average", device=None):
+        if linkage != "average":
+            raise ValueError(f"linkage: only 'average' over the cosine distance is offered, got {linkage!r}")
+        self.n_clusters = int(n_clusters)
+        if self.n_clusters < 1:
+            raise ValueError(f"n_clusters must be >= 1 (got {n_clusters})")
+        self.linkage = linkage
+        self.device = "cuda:0" if device is None else device
+        self.labels_: Optional[np.ndarray] = None
+        self.children_: Optional[np.ndarray] = None
+        self.distances_: Optional[np.ndarray] = None
+        self.n_leaves_: Optional[int] = None
+        self.n_rounds_: Optional[int] = None
+
+    def _set_tree(self, heights, id_a, id_b, n_leaves, n_rounds):
+        """The host half: from a merge log to the fitted attributes (no GPU)."""
+        if self.n_clusters > n_leaves:
+            raise ValueError(f"n_samples={n_leaves} should be >= n_clusters={self.n_clusters}")
+        self.children_, self.distances_ = agc_tree(heights, id_a, id_b, n_leaves)
+        self.n_leaves_, self.n_rounds_ = int(n_leaves), int(n_rounds)
+        self.labels_ = self.labels_for(self.n_clusters)
+        return self
+
+    def labels_for(self, n_clusters) -> np.ndarray:
+        """The labels of another ``n_clusters`` from the stored tree, without a fit."""
+        if self.children_ is None:
+            raise RuntimeError("this AgglomerativeClustering has no tree yet: call fit first")
+        return agc_cut(self.children_, self.n_leaves_, n_clusters)
+
+    def fit(self, x):
+        from .. import ops
+        from ..dispatch import _unit_rows
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.array(x, dtype=np.float32, order="C"))       # (a copy: the caller's array may be read-only)
+        x = x.to(device=self.device, dtype=torch.float32)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"x: expected a (N >= 1, D >= 1) matrix, got {tuple(x.shape)}")
+        N, D = x.shape
+        if self.n_clusters > N:
+            raise ValueError(f"n_samples={N} should be >= n_clusters={self.n_clusters}")
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError("x holds NaN or infinite values: such a row has no nearest cluster")
+        if N == 1:
+            return self._set_tree(np.zeros(0), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), 1, 0)
+        dev = x.device
+        means = _unit_rows(x.contiguous(), N, D)                    # a cluster of one row: sum = mean = the row
+        sums, sizes, ids = means.double(), torch.ones(N, device=dev, dtype=torch.int64), torch.arange(N, device=dev, dtype=torch.int32)
+        sums2, sizes2, ids2 = torch.empty_like(sums), torch.empty_like(sizes), torch.empty_like(ids)
+        log_dist = torch.empty(N - 1, device=dev, dtype=torch.float32)
+        log_ids = torch.empty(N - 1, 3, device=dev, dtype=torch.int32)
+        counts = torch.empty(2, device=dev, dtype=torch.int32)
+        M, rounds = N, 0
+        while M > 1:                                                # every round merges at least one pair: at most N - 1 rounds
+            nn, dist = ops.agc_nearest(means[:M])
+            ops.agc_merge(nn, dist, sums, sizes, ids, sums2, sizes2, ids2, means, log_dist, log_ids, counts, log_off=N - M,
+                          next_id=2 * N - M)
+            pairs, new_m = counts.tolist()                          # the round's one host read
+            if pairs < 1 or new_m != M - pairs:
+                raise RuntimeError(f"round {rounds + 1} at {M} clusters merged {pairs} pairs: no two clusters are each other's "
+                                   "nearest, which the bit-symmetric scores of agc_nearest rule out for finite rows")
+            sums, sums2, sizes, sizes2, ids, ids2 = sums2, sums, sizes2, sizes, ids2, ids
+            M = new_m
+            rounds += 1
+        log = log_ids.cpu().numpy()
+        if not np.array_equal(log[:, 2], N + np.arange(N - 1)):
+            raise RuntimeError("the merge log does not number its nodes N, N + 1, ...")
+        return self._set_tree(log_dist.cpu().numpy(), log[:, 0], log[:, 1], N, rounds)
+
+    def fit_predict(self, x):
+        return self.fit(x).labels_
+
+
+def agc_cluster_map(phrase_to_emb: Mapping[str, np.ndarray], n_clusters: int, device=None):
+    """The reference's ``Runner().agc`` on a {phrase: embedding} table -> {"result": {str(label): [phrases ...]} with the keys in
+    order of first appearance, "model": the fitted AgglomerativeClustering}."""
+    phrases = list(phrase_to_emb)
+    embs = np.stack([np.asarray(phrase_to_emb[p], dtype=np.float32).reshape(-1) for p in phrases])
+    model = AgglomerativeClustering(n_clusters, device=device)
     labels = model.fit_predict(embs)
     return {"result": cluster_map_from_labels(phrases, labels), "model": model}
