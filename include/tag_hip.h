@@ -1175,6 +1175,40 @@ int tag_agc_merge(const int* nn, const float* dist, const double* sums_in, const
                   int log_rows, int log_off, int next_id, int* counts, int M, int D, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Device spectral clustering over the cosine affinity (spectral.hip; python_scripts/clustering/spectral_emb.py of the reference runs
+ * sklearn's SpectralClustering(affinity="precomputed") on the dense N x N fp64 matrix (cos + 1) / 2 on the host).  With unit rows u
+ * and W = [u | 1] the affinity is W W^T / 2, rank D + 1, and sklearn's operator is M = Y Y^T - diag(e) with Y = diag(s) W / sqrt 2,
+ * s = deg^-1/2, e = a_ii / deg, a_ii = (u_i . u_i + 1) / 2, deg_i = W_i . (W^T 1) / 2 - a_ii (the Laplacian ignores the diagonal).
+ * All tensors fp32 with row strides in floats unless stated; ws is never zeroed; no atomics: the same bits on every run.
+ *
+ * tag_spectral_gram: out (p x q, fp64, row stride ldo >= q in doubles) = sum_i w_i P[i][a] Q[i][b] over N rows; P (N, p), Q (N, q),
+ *   w (N) or null (w = 1).  The rows are cut into slices of TAG_SPECTRAL_CHAIN rows whatever the shape is.  Inside a slice the
+ *   products are fp32 on the exact-fp32 MFMA (operands not rounded; w_i P[i][a] is one fp32 product) on two alternating
+ *   accumulator sets, so a term passes through at most TAG_SPECTRAL_CHAIN / 2 + 3 roundings; the slices' partials go to ws and a
+ *   second launch adds them in fp64 in slice order:  |err_ab| <= TAG_SPECTRAL_CHAIN 2^-24 sum_i |w_i P[i][a] Q[i][b]| (+ the fp64
+ *   rounding of that sum) for every N.  P == Q with ldp == ldq and p == q: only tiles on or above the diagonal are computed and
+ *   element (min(a, b), max(a, b)) serves both (a, b) and (b, a): out is bit-symmetric.  tag_spectral_gram_ws_bytes =
+ *   4 ceil(N / TAG_SPECTRAL_CHAIN) p q, a function of the shape alone (0 for a shape the call would refuse).
+ * tag_spectral_rows: u (N, D) unit rows (a zero row is fine), t (D, fp64) = sum_i u_i.  Per row, in fp64:
+ *   deg = (u_i . t + N) / 2 - a_ii;  s[i] = deg^-1/2, e[i] = a_ii / deg and Y[i] = s_i / sqrt 2 * [u_i, 1] (D + 1 columns, ldy >=
+ *   D + 1) are rounded to fp32 once.  A row whose deg is <= 0 or not finite is reported: s[i] = e[i] = 0 and a zero row of Y (a
+ *   valid row has s > 0).
+ * tag_spectral_apply: out (N, b) = Y T - e * X:  Y (N, Dp), T (Dp, b), e (N), X (N, b); the products as above with k = the column
+ *   of Y in ascending order, the epilogue acc - e[i] * X[i][j] in fp32: |err| <= (Dp + 2) 2^-24 (|Y||T| + |e * X|).  out may be X.
+ *   No workspace.
+ * TAG_EINVAL before any launch, the numbers named in tag_last_error: a size < 1, a row stride below the width, a null pointer
+ *   (w excepted), N above 2^31 - 1 - TAG_SPECTRAL_CHAIN (gram) or 2^31 - 129 (apply), p or q above 32768, a grid above 2^31 - 1.
+ */
+#define TAG_SPECTRAL_CHAIN 256
+int tag_spectral_chain(void);
+size_t tag_spectral_gram_ws_bytes(int N, int p, int q);
+int tag_spectral_gram(const float* P, int ldp, const float* Q, int ldq, const float* w, double* out, int ldo, int N, int p, int q,
+                      void* ws, void* stream);
+int tag_spectral_rows(const float* u, int ldu, const double* t, float* Y, int ldy, float* s, float* e, int N, int D, void* stream);
+int tag_spectral_apply(const float* Y, int ldy, const float* T, int ldt, const float* e, const float* X, int ldx, float* out,
+                       int ldo, int N, int Dp, int b, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Operating-point counts of the grounding evaluation (grounding_eval.hip; utils/eval_util.py:296-330 and :136-225 of the
  * reference, as utils/grounding_eval.py restates them on the host): one launch behind tag_segments, one wave per
  * (clip, threshold) pair.  regions (B,NT,max_regions,2) int64 rows [onset, offset) in frames and counts (B,NT) int32 are

@@ -15,8 +15,8 @@ Label JSON: a list of clips ``{"audio_id", "audiocap_id", "tokens", "phrases": [
 * ``KmeansMappingEvalDataset``  one item per (clip, phrase): the clip's fields plus ``text_idx`` (the phrase's cluster),
   ``start_index`` and ``end_index``.
 * ``SpectralMappingDataset`` / ``SpectralMappingEvalDataset``  the same items from a ``cluster_map`` JSON ``{str(cluster index):
-  [phrases ...]}`` of ANY clustering method (tools/kmeans_emb.py, tools/dbscan_emb.py, the reference's spectral and agglomerative
-  scripts): host-only, no model, no embeddings and no distance filter.  As in the reference ``classes_num`` is the number of
+  [phrases ...]}`` of ANY clustering method (tools/kmeans_emb.py, tools/dbscan_emb.py, tools/agc_emb.py and tools/spectral_emb.py,
+  the script the classes are named after, or the reference's own scripts): host-only, no model, no embeddings and no distance filter.  As in the reference ``classes_num`` is the number of
   keys, a DBSCAN map's ``"-1"`` key included, and the phrases under ``"-1"`` index class -1 (the last column).
 
 Differences from the reference: waveforms come through ``WaveformStore``; ``cluster_model`` is read by

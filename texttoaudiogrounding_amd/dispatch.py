@@ -2513,6 +2513,84 @@ def agc_merge(nn, dist, sums, sizes, ids, sums_out, sizes_out, ids_out, means_ou
 
 
 # ------------------------------------------------------------------------------------------------
+# device spectral clustering (python_scripts/clustering/spectral_emb.py in the reference runs sklearn on an N x N fp64 matrix),
+# spectral.hip
+# ------------------------------------------------------------------------------------------------
+
+#: rows per slice of spectral_gram's fp32 partial sums (= TAG_SPECTRAL_CHAIN of include/tag_hip.h, tag_spectral_chain()): the
+#: length that bounds an fp32 chain whatever N is
+SPECTRAL_CHAIN = 256
+
+
+def _spectral_vec(t, name, n, like):
+    if not t.is_cuda:
+        _chk(t, name)
+    if t.dtype != F32 or tuple(t.shape) != (n,) or t.device != like.device:
+        raise RuntimeError(f"{name}: expected float32 ({n},) on {like.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t.contiguous()
+
+
+def spectral_gram(P, Q, w=None):
+    """out (p, q) fp64 = sum_i w_i P[i, a] Q[i, b] over the N rows of P (N, p) and Q (N, q); w (N,) fp32 or None for ones.  Rows are
+    cut into slices of SPECTRAL_CHAIN rows: inside a slice the products are fp32 on the exact-fp32 MFMA, the slices are added in
+    fp64, so |err| <= SPECTRAL_CHAIN 2^-24 sum_i |w_i P_ia Q_ib| for every N.  ``P is Q`` computes the tiles on or above the
+    diagonal only and returns a bit-symmetric matrix.  Row-strided views are passed as they are.  The same bits on every run."""
+    same = P is Q
+    pr = _phrase_sim_rows(P, "P")
+    qr = pr if same else _phrase_sim_rows(Q, "Q")
+    if qr.device != pr.device or qr.shape[0] != pr.shape[0]:
+        raise RuntimeError(f"Q {tuple(qr.shape)} on {qr.device}: expected P's device {pr.device} and N = {pr.shape[0]} rows")
+    (N, p), q = pr.shape, qr.shape[1]
+    wv = None if w is None else _spectral_vec(w, "w", N, pr)
+    nws = query("tag_spectral_gram_ws_bytes", N, p, q)
+    if nws == 0:
+        raise RuntimeError(f"spectral_gram: N = {N}, p = {p}, q = {q}: expected N <= {2**31 - 1 - SPECTRAL_CHAIN}, p and q <= 32768")
+    out = torch.empty(p, q, device=pr.device, dtype=torch.float64)
+    ws = _ws(nws, pr)
+    call("tag_spectral_gram", ptr(pr), pr.stride(0), ptr(qr), qr.stride(0), ptr(wv), ptr(out), q, N, p, q, ptr(ws))
+    return out
+
+
+def spectral_rows(u, t):
+    """(Y fp32 (N, D + 1), s fp32 (N,), e fp32 (N,)) of the normalised cosine affinity (u_i . u_j + 1) / 2 over unit rows u (N, D),
+    t (D,) fp64 = the column sums of u.  Per row in fp64: deg = (u_i . t + N) / 2 - a_ii, a_ii = (u_i . u_i + 1) / 2 (the degree
+    without the diagonal), s = deg^-1/2, e = a_ii / deg, Y[i] = s_i / sqrt 2 * [u_i, 1].  Y has 16-byte aligned rows: a (N, D + 1)
+    view of a buffer whose row stride is a multiple of 4.  A row with deg <= 0 is reported as s[i] == 0 (e and Y's row zero)."""
+    ur = _phrase_sim_rows(u, "u")
+    N, D = ur.shape
+    if not t.is_cuda:
+        _chk(t, "t")
+    if t.dtype != torch.float64 or tuple(t.shape) != (D,) or t.device != ur.device:
+        raise RuntimeError(f"t: expected float64 ({D},) on {ur.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    Y = torch.empty(N, (D + 4) // 4 * 4, device=ur.device, dtype=F32)[:, :D + 1]
+    s = torch.empty(N, device=ur.device, dtype=F32)
+    e = torch.empty(N, device=ur.device, dtype=F32)
+    call("tag_spectral_rows", ptr(ur), ur.stride(0), ptr(t.contiguous()), ptr(Y), Y.stride(0), ptr(s), ptr(e), N, D)
+    return Y, s, e
+
+
+def spectral_apply(Y, T, e, X, out=None):
+    """out (N, b) fp32 = Y @ T - e[:, None] * X: the operator M = Y Y^T - diag(e) applied to a block X once T = Y^T X is known.
+    Y (N, Dp), T (Dp, b), e (N,), X (N, b); one MFMA launch with the row epilogue fused, |err| <= (Dp + 2) 2^-24 (|Y||T| + |e X|).
+    Row-strided views are passed as they are; ``out`` (given or new) may be X."""
+    yr, tr, xr = _phrase_sim_rows(Y, "Y"), _phrase_sim_rows(T, "T"), _phrase_sim_rows(X, "X")
+    (N, Dp), b = yr.shape, tr.shape[1]
+    if tr.shape[0] != Dp or tuple(xr.shape) != (N, b) or tr.device != yr.device or xr.device != yr.device:
+        raise RuntimeError(f"spectral_apply: Y {tuple(yr.shape)} needs T ({Dp}, b) and X ({N}, b) on {yr.device}, got T "
+                           f"{tuple(tr.shape)} on {tr.device}, X {tuple(xr.shape)} on {xr.device}")
+    ev = _spectral_vec(e, "e", N, yr)
+    if out is None:
+        out = torch.empty(N, b, device=yr.device, dtype=F32)
+    elif (not out.is_cuda or out.dtype != F32 or tuple(out.shape) != (N, b) or out.stride(1) != 1 or out.stride(0) < b
+          or out.device != yr.device):
+        raise RuntimeError(f"out: expected a float32 ({N}, {b}) matrix with unit column stride on {yr.device} (it is written in "
+                           f"place), got {out.dtype} {tuple(out.shape)} strides {tuple(out.stride())} on {out.device}")
+    call("tag_spectral_apply", ptr(yr), yr.stride(0), ptr(tr), tr.stride(0), ptr(ev), ptr(xr), xr.stride(0), ptr(out),
+         out.stride(0), N, Dp, b)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # operating-point counts of the grounding evaluation (utils/grounding_eval.py on the host), grounding_eval.hip
 # ------------------------------------------------------------------------------------------------
 

@@ -250,6 +250,11 @@ _SIGS = {
     "tag_agc_nearest": (c_int, [P, c_int, P, P, c_int, c_int, P, P]),
     "tag_agc_merge_ws_bytes": (c_size_t, [c_int, c_int]),
     "tag_agc_merge": (c_int, [P, P, P, P, P, P, P, P, P, c_int, P, P, c_int, c_int, c_int, P, c_int, c_int, P, P]),
+    "tag_spectral_chain": (c_int, []),
+    "tag_spectral_gram_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "tag_spectral_gram": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "tag_spectral_rows": (c_int, [P, c_int, P, P, c_int, P, P, c_int, c_int, P]),
+    "tag_spectral_apply": (c_int, [P, c_int, P, c_int, P, P, c_int, P, c_int, c_int, c_int, c_int, P]),
     "tag_grounding_counts": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, c_double, P, P]),
 }
 

@@ -1,5 +1,5 @@
-"""k-means, DBSCAN and average-linkage clustering over phrase embeddings on the device: what python_scripts/clustering/kmeans_emb.py,
-dbscan_emb.py and agc_emb.py of the reference do with sklearn on the host.  ``DBSCAN`` / ``dbscan_cluster_map`` (csrc/dbscan.hip) are described at the class; their
+"""k-means, DBSCAN, average-linkage and spectral clustering over phrase embeddings on the device: what python_scripts/clustering/kmeans_emb.py,
+dbscan_emb.py, agc_emb.py and spectral_emb.py of the reference do with sklearn on the host.  ``DBSCAN`` / ``dbscan_cluster_map`` (csrc/dbscan.hip) are described at the class; their
 cluster map feeds the same ``neg_samp_stratg="clustering"`` and ``SpectralMappingDataset`` / ``SpectralMappingEvalDataset``.
 k-means makes the ``cluster_map`` JSON that ``AudioSamplePhrasesDataset(neg_samp_stratg="clustering")`` reads and the cluster model that ``KmeansMappingDataset`` / ``KmeansMappingEvalDataset`` turn phrases into class indices with.
 
@@ -15,6 +15,12 @@ cosine distance without the N x N matrix.  A cluster is the fp64 sum of its unit
 1 - mean_A . mean_B), every round merges all reciprocal nearest neighbours at once (``ops.agc_nearest`` + ``ops.agc_merge``, one
 host read per round), and the host half (``agc_tree`` / ``agc_cut``, plain numpy, no GPU) orders the merges and cuts the tree as
 sklearn does; the class states when the labels are sklearn's own.
+
+``SpectralClustering`` / ``spectral_cluster_map`` (csrc/spectral.hip) are python_scripts/clustering/spectral_emb.py: sklearn's
+spectral embedding of the affinity (cos + 1) / 2 without the N x N matrix.  The affinity has rank D + 1, so the normalised
+operator is applied through two tall-skinny products (``ops.spectral_gram`` / ``spectral_rows`` / ``spectral_apply``), a block
+subspace iteration with a host Rayleigh-Ritz step (``spectral_start`` / ``spectral_ritz`` / ``spectral_sign_flip``, plain numpy, no
+GPU) finds the leading eigenvectors, and the device ``KMeans`` labels the rows of the embedding.
 
 Deviations from sklearn: ``"k-means++"`` is plain D^2 sampling with one candidate per step (no greedy multi-trial), x is not
 mean-centred before the fit, and the arithmetic is fp32 with fp64 cluster sums.
@@ -483,3 +489,193 @@ def agc_cluster_map(phrase_to_emb: Mapping[str, np.ndarray], n_clusters: int, de
     model = AgglomerativeClustering(n_clusters, device=device)
     labels = model.fit_predict(embs)
     return {"result": cluster_map_from_labels(phrases, labels), "model": model}
+
+
+def spectral_block(n_rows, dim, n_clusters, block=None):
+    """Columns of the iterated block: ``n_clusters`` plus guard columns, ``min(D + 1, 2 k)`` by default (a block of exactly k columns
+    converges at the rate lambda_(k+1) / lambda_k, which is close to 1 when two eigenvalues are close), never more than the rank
+    bound ``min(N, D + 1)`` of the affinity."""
+    k, cap = int(n_clusters), min(int(n_rows), int(dim) + 1)
+    b = min(cap, 2 * k) if block is None else int(block)
+    if not k <= b <= cap:
+        raise ValueError(f"block = {b}: expected n_clusters = {k} <= block <= min(N, D + 1) = {cap}")
+    return b
+
+
+def spectral_start(gram, block):
+    """The host half of the start, numpy fp64: the (D + 1)^2 Gram matrix Y^T Y -> (mu (block,) descending, coef (D + 1, block)) with
+    X0 = Y coef = Y Q mu^-1/2, orthonormal eigenvectors of Y Y^T.  M differs from Y Y^T by diag(e) = O(2 / N), so X0 already has
+    a residual near 1e-4.  An eigenvalue at the rounding level of the largest has no direction to start from and raises."""
+    G = np.asarray(gram, dtype=np.float64)
+    G = 0.5 * (G + G.T)
+    mu, Q = np.linalg.eigh(G)
+    top = np.argsort(-mu, kind="stable")[:int(block)]
+    mu, Q = mu[top], Q[:, top]
+    if not np.all(np.isfinite(mu)) or mu[-1] <= 1e-10 * mu[0]:
+        raise ValueError(f"the affinity has fewer than {int(block)} independent directions (eigenvalues of Y^T Y: {mu[0]:.3g} down "
+                         f"to {mu[-1]:.3g}): the embeddings span a lower dimension, choose a smaller n_clusters / block")
+    return mu, np.ascontiguousarray(Q / np.sqrt(mu))            # (Q[:, top] is column-major: the device reads row-major)
+
+
+def spectral_ritz(S, H):
+    """The Rayleigh-Ritz step, numpy fp64: S = X^T X and H = X^T M X of a block X -> (lam (b,) descending, C (b, b)) with
+    H C = S C diag(lam) and C^T S C = I (Cholesky of S, a symmetric eigenproblem, back-substitution): X C are the Ritz vectors."""
+    S = np.asarray(S, dtype=np.float64)
+    H = np.asarray(H, dtype=np.float64)
+    S, H = 0.5 * (S + S.T), 0.5 * (H + H.T)
+    try:
+        Lc = np.linalg.cholesky(S)
+    except np.linalg.LinAlgError:
+        raise ValueError("the block lost rank (X^T X is not positive definite): choose a smaller block") from None
+    A = np.linalg.solve(Lc, np.linalg.solve(Lc, H).T)
+    lam, V = np.linalg.eigh(0.5 * (A + A.T))
+    order = np.argsort(-lam, kind="stable")
+    return lam[order], np.ascontiguousarray(np.linalg.solve(Lc.T, V[:, order]))
+
+
+def _to_device(a, dev):
+    """A host fp64 matrix as a row-major fp32 tensor on the device (the kernels take a pointer and a row stride)."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+
+
+def spectral_sign_flip(maps):
+    """sklearn's ``_deterministic_vector_sign_flip`` on the columns of an (N, k) embedding: the entry of largest magnitude of every
+    vector (the first one on ties) becomes positive."""
+    maps = np.array(maps)
+    rows = np.argmax(np.abs(maps), axis=0)
+    sign = np.sign(maps[rows, np.arange(maps.shape[1])])
+    sign[sign == 0] = 1
+    return maps * sign.astype(maps.dtype)
+
+
+class SpectralClustering:
+    """sklearn-shaped spectral clustering over the cosine affinity on the device: what python_scripts/clustering/spectral_emb.py of
+    the reference does with ``SpectralClustering(n_clusters, affinity="precomputed", random_state=seed)`` on the dense matrix
+    ``(cosine_similarity + 1) / 2``, without the N x N matrix (csrc/spectral.hip).
+
+    * rows: ``u = x / max(||x||, 1e-12)``, ``W = [u | 1]``; the affinity is ``W W^T / 2``, rank D + 1.  scipy's Laplacian ignores
+      the diagonal: ``deg_i = W_i . (W^T 1) / 2 - a_ii``; with ``s = deg^-1/2``, ``e = a_ii / deg``, ``Y = diag(s) W / sqrt 2``
+      (``ops.spectral_rows``) sklearn's eigenproblem is the k largest pairs of ``M = Y Y^T - diag(e)``, and
+      ``M X = Y (Y^T X) - e * X`` is two tall-skinny products (``ops.spectral_gram``, ``ops.spectral_apply``);
+    * solver: block subspace iteration with Rayleigh-Ritz on ``block`` columns (``spectral_block``: ``min(D + 1, 2 k)``), started
+      from the eigenvectors of ``Y Y^T`` (``spectral_start``).  An iteration applies M, forms ``X^T X`` and ``X^T M X`` in fp64 on
+      the device, solves the small problem on the host (``spectral_ritz``, numpy fp64), rotates both blocks with ``ops.gemm`` and
+      continues from ``(M + sigma I) X C / (lambda + sigma)`` with ``sigma = max e``: ``M + diag(e) = Y Y^T`` is positive
+      semi-definite, so the shifted operator has no negative eigenvalue and its dominant vectors are the largest of M for every N
+      (e is O(2 / N); at a handful of rows M has eigenvalues near -e that exceed lambda_k in magnitude).  The residual
+      ``max_j<k ||M x_j - lambda_j x_j||`` is taken from the rotated vectors themselves and is read with the NEXT iteration's Gram
+      matrices: one host read per iteration and one at the end.  The loop ends one iteration after the residual is at most
+      ``tol`` or no longer halves, or at ``max_iter``;
+    * ``maps_`` = the Ritz vectors times s after sklearn's sign flip (``spectral_sign_flip``): sklearn's ``spectral_embedding`` in
+      descending order of the eigenvalue; ``labels_`` = the device ``KMeans(n_clusters, n_init=n_init, random_state=random_state)``
+      on its rows.  sklearn seeds k-means with its greedy k-means++, so the labels are its PARTITION where the clusters of the
+      embedding are separated, not its numbering.
+
+    ``tol`` defaults to 2e-7, two to five times the measured fp32 floor of the residual (docs/experiments_spectral.md).  After ``fit``:
+    ``labels_`` (numpy int64), ``maps_`` ((N, k) fp32), ``eigenvalues_`` ((k,) fp64, of M: sklearn's Laplacian has 1 - these),
+    ``residuals_`` (one per iteration), ``n_iter_``, ``block_``.  ``n_clusters`` above ``min(N, D + 1)`` is refused: the affinity
+    has no more eigenvectors than that."""
+
+    def __init__(self, n_clusters=8, n_init=10, random_state=None, block=None, max_iter=10, tol=None, device=None):
+        self.n_clusters = int(n_clusters)
+        self.n_init = int(n_init)
+        self.random_state = random_state
+        self.block = None if block is None else int(block)
+        self.max_iter = int(max_iter)
+        self.tol = 2e-7 if tol is None else float(tol)
+        self.device = "cuda:0" if device is None else device
+        if self.n_clusters < 1 or self.n_init < 1 or self.max_iter < 1:
+            raise ValueError(f"n_clusters, n_init and max_iter must be >= 1 (got {n_clusters}, {n_init}, {max_iter})")
+        if not self.tol > 0.0:
+            raise ValueError(f"tol must be > 0 (got {tol})")
+        self.labels_: Optional[np.ndarray] = None
+        self.maps_: Optional[np.ndarray] = None
+        self.eigenvalues_: Optional[np.ndarray] = None
+        self.residuals_: Optional[List[float]] = None
+        self.n_iter_: Optional[int] = None
+        self.block_: Optional[int] = None
+
+    def _check_shape(self, N, D):
+        """-> the block size; the refusals that need no GPU."""
+        if self.n_clusters > min(N, D + 1):
+            raise ValueError(f"n_clusters={self.n_clusters} should be <= min(n_samples, D + 1) = min({N}, {D + 1}): the affinity "
+                             f"(cos + 1) / 2 of {D}-dimensional rows has rank D + 1, it has no more eigenvectors than that")
+        return spectral_block(N, D, self.n_clusters, self.block)
+
+    def _embed(self, x, b):
+        """(Ritz vectors (N, k) on the device, s (N,), eigenvalues) of the fitted block of b columns."""
+        from .. import ops
+        from ..dispatch import _unit_rows
+        N, D = x.shape
+        k, dev = self.n_clusters, x.device
+        u = _unit_rows(x.contiguous(), N, D)
+        t = ops.spectral_gram(u, torch.ones(N, 1, device=dev))[:, 0].contiguous()
+        Y, s, e = ops.spectral_rows(u, t)
+        G = ops.spectral_gram(Y, Y)
+        host = torch.cat((G.flatten(), e.max().double().reshape(1), (s <= 0).sum().double().reshape(1))).cpu().numpy()
+        sigma = float(host[-2])                                          # (the start's one host read: G, max e, the rows reported)
+        if host[-1]:
+            row = int(torch.nonzero(s <= 0)[0])
+            raise ValueError(f"row {row} has degree <= 0 in the affinity (cos + 1) / 2 without its diagonal (every other row is "
+                             "opposite to it): the normalised Laplacian does not exist")
+        G = host[:-2].reshape(D + 1, D + 1)
+        _, coef = spectral_start(G, b)
+        X = ops.gemm(Y, _to_device(coef, dev), N, b, D + 1, lda=Y.stride(0))
+        self.residuals_, resid = [], None
+        for it in range(1, self.max_iter + 1):
+            MX = ops.spectral_apply(Y, ops.spectral_gram(Y, X).float(), e, X)
+            S, H = ops.spectral_gram(X, X), ops.spectral_gram(X, MX)
+            parts = [S.flatten(), H.flatten()] + ([resid] if resid is not None else [])
+            host = torch.cat(parts).cpu().numpy()                       # the iteration's one host read
+            done = False
+            if resid is not None:
+                self.residuals_.append(float(host[2 * b * b:].max()))
+                r = self.residuals_
+                done = r[-1] <= self.tol or (len(r) > 1 and r[-1] > 0.5 * r[-2])
+            lam, C = spectral_ritz(host[:b * b].reshape(b, b), host[b * b:2 * b * b].reshape(b, b))
+            Cd = _to_device(C, dev)
+            lam_d = torch.from_numpy(lam).to(dev)
+            Xn, MXn = ops.gemm(X, Cd, N, b, b), ops.gemm(MX, Cd, N, b, b)
+            resid = ((MXn[:, :k].double() - Xn[:, :k].double() * lam_d[:k]) ** 2).sum(0).sqrt()
+            self.n_iter_ = it
+            if done:
+                break
+            scale = lam_d + sigma
+            X = (MXn + sigma * Xn) / torch.where(scale > 1e-30, scale, torch.ones_like(scale)).float()
+        self.residuals_.append(float(resid.max()))
+        return Xn[:, :k], s, lam[:k]
+
+    def fit(self, x):
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.array(x, dtype=np.float32, order="C"))       # (a copy: the caller's array may be read-only)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"x: expected a (N >= 1, D >= 1) matrix, got {tuple(x.shape)}")
+        N, D = x.shape
+        b = self._check_shape(N, D)
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError("x holds NaN or infinite values: such a row has no affinity")
+        self.block_ = b
+        if N == 1:                                                      # (one row: one cluster, nothing to embed)
+            self.labels_, self.maps_ = np.zeros(1, dtype=np.int64), np.ones((1, 1), dtype=np.float32)
+            self.eigenvalues_, self.residuals_, self.n_iter_ = np.zeros(1), [], 0
+            return self
+        x = x.to(device=self.device, dtype=torch.float32)
+        vec, s, lam = self._embed(x, b)
+        self.maps_ = spectral_sign_flip((vec * s[:, None]).cpu().numpy())
+        self.eigenvalues_ = np.asarray(lam, dtype=np.float64)
+        km = KMeans(self.n_clusters, n_init=self.n_init, random_state=self.random_state, device=self.device)
+        self.labels_ = km.fit_predict(self.maps_).astype(np.int64)
+        return self
+
+    def fit_predict(self, x):
+        return self.fit(x).labels_
+
+
+def spectral_cluster_map(phrase_to_emb: Mapping[str, np.ndarray], n_clusters: int, seed=0, device=None):
+    """The reference's ``Spectral().spectral_sklearn`` on a {phrase: embedding} table -> {"model": the fitted SpectralClustering,
+    "result": {str(label): [phrases ...]} with the keys in order of first appearance}."""
+    phrases = list(phrase_to_emb)
+    embs = np.stack([np.asarray(phrase_to_emb[p], dtype=np.float32).reshape(-1) for p in phrases])
+    model = SpectralClustering(n_clusters, random_state=seed, device=device)
+    labels = model.fit_predict(embs)
+    return {"model": model, "result": cluster_map_from_labels(phrases, labels)}
