@@ -450,6 +450,14 @@ int tag_gru_timed_out(const void* host_copy_of_err_word);
  * (agent scope) instead of L2-resident on one XCD -- the fast form depends on gfx950 cache behaviour (SPX partition mode,
  * MTYPE_RW) beyond the HIP memory model; a stale granule can only show as a timeout.  Returns the previous setting. */
 int tag_gru_disable_xcd_fast(void);
+/* Debug query for tests and tools (host only, launches nothing): the recurrence form that the last successful tag_gru_forward
+ * (backward = 0) / tag_gru_backward (backward != 0) of this process launched: 0 = none yet, 1 = one launch per step,
+ * 2 = 16-row persistent, 3 = 4-row persistent.  Recorded after the launch succeeded: a refused cooperative launch that fell
+ * back reports the fallback.
+ * Hidden sizes (pinned by tests/test_gpu_gru_sweep.py): tag_gru_forward takes every H >= 16 with H % 16 == 0; tag_gru_backward
+ * also needs (3 H) % 32 == 0, i.e. H % 32 == 0 -- H = 16, 48, 80, ... run forward (inference) and are REFUSED by backward with
+ * TAG_EINVAL before anything is written, so a model of such a width cannot be trained. */
+int tag_gru_last_form(int backward);
 
 /* ---------------------------------------------------------------------------------------------
  * T3: row-local GRU recurrence of the text side, PyTorch gate order (r,z,n), h0 = 0, ALL L padded positions, one launch

@@ -497,8 +497,13 @@ __device__ __forceinline__ bool p4_group_shares_xcd(u64* xid, int grp, int m, in
 // Gate functions of the 4-row forward kernel.  The recurrence is a chain of T dependent steps run by ONE wave per SIMD, so
 // the ~100 dependent instructions of the library expf / tanhf / full-precision divide are paid in full on every step
 // (measured: 410 of 3200 clocks per step).  Hardware forms instead: v_exp_f32 + v_rcp_f32 (1 ulp each); tanh switches to
-// its odd series below |x| = 0.2, where 1 - 2 / (1 + e^2x) would cancel.  |error| <= 3e-7 absolute / 4e-7 relative on
-// outputs in (0,1) / (-1,1) -- fp32 rounding class (the library forms are within 1-2 ulp = 1.2e-7).
+// its odd series below |x| = 0.2, where 1 - 2 / (1 + e^2x) would cancel.  |error| <= 3e-7 absolute on outputs in (0,1) /
+// (-1,1) -- fp32 rounding class (the library forms are within 1-2 ulp = 1.2e-7); measured on an MI355X over the sample points of
+// tests/gru_ref.py: 7.9e-8 (sigmoid), 1.6e-7 (tanh).  The RELATIVE error is larger than the 4e-7 this comment used to claim: the
+// argument x log2(e) of v_exp_f32 is rounded to fp32, which alone is |x| 2^-24 of e^x (1.2e-6 at |x| = 20), so the small tail of
+// the sigmoid is within 2e-6 of itself for |x| <= 20 (measured 7.7e-7; 9.2e-7 at x = -44), and just above the series switch
+// 1 - 0.803 cancels to 0.197, which turns the absolute error into 6.2e-7 of tanh x (measured at x = -0.2000006).  Both bounds
+// (3e-7 absolute everywhere, 2e-6 relative for |x| <= 20) are asserted by tests/test_gpu_gru_sweep.py.
 __device__ __forceinline__ float sigmoid_hw(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanh_hw(float x) {
     const float t = x * x;
@@ -868,6 +873,10 @@ hipError_t gru_launch_persistent(K kernel, dim3 grid, void** args, hipStream_t s
 
 }  // namespace
 
+// which recurrence form the last successful tag_gru_forward [0] / tag_gru_backward [1] of this process launched (host-side
+// bookkeeping for tag_gru_last_form; written after the launch succeeded, so a refused cooperative launch reports its fallback)
+static int g_gru_last_form[2] = {0, 0};
+
 // ws layout: [ 6*H*H floats: transposed recurrent weights | exchange granules 2*2*Bpad*3H u64 | err word ]
 static size_t gru_ws_layout(int B, int H, size_t* off_x, size_t* off_err) {
     const size_t Bpad = (size_t)((B + 15) / 16) * 16;
@@ -910,7 +919,7 @@ extern "C" int tag_gru_forward(const float* gi, const float* w_hh, const float* 
             if (hipMemsetAsync(hx, 0, off_err - off_x, st) != hipSuccess) { tag_set_error("memset failed"); return TAG_ELAUNCH; }
             const hipError_t e = H == 256 ? gru_launch_persistent(gru_fwd_p4_kernel<256>, g4, args, st)
                                           : gru_launch_persistent(gru_fwd_p4_kernel<128>, g4, args, st);
-            if (e == hipSuccess) return 0;
+            if (e == hipSuccess) { g_gru_last_form[0] = 3; return 0; }
         }
     }
     // the 16-row persistent kernels and the per-step kernels read the transposed recurrent weights
@@ -927,7 +936,7 @@ extern "C" int tag_gru_forward(const float* gi, const float* w_hh, const float* 
             if (hipMemsetAsync(hx, 0, off_err - off_x, st) != hipSuccess) { tag_set_error("memset failed"); return TAG_ELAUNCH; }
             const hipError_t e = H == 256 ? gru_launch_persistent(gru_fwd_persistent_kernel<256>, grid, args, st)
                                           : gru_launch_persistent(gru_fwd_persistent_kernel<128>, grid, args, st);
-            if (e == hipSuccess) return 0;
+            if (e == hipSuccess) { g_gru_last_form[0] = 2; return 0; }
         }
     }
     for (int s = 0; s < T; ++s) {
@@ -939,6 +948,7 @@ extern "C" int tag_gru_forward(const float* gi, const float* w_hh, const float* 
             hipLaunchKernelGGL(gru_fwd_step_kernel<0>, grid, dim3(256), 0, st, gi, wt, b_hh, y, gates, B, T, H, s);
     }
     TAG_LAUNCH_CHECK();
+    g_gru_last_form[0] = 1;
     return 0;
 }
 
@@ -946,7 +956,7 @@ extern "C" int tag_gru_forward(const float* gi, const float* w_hh, const float* 
 extern "C" int tag_gru_backward(const float* dy, const float* y, const float* gates, const float* w_hh, float* dgi,
                                 float* dgh, float* hprev, void* scratch, int B, int T, int H, void* stream) {
     TAG_CHECK_ARG(dy && y && gates && w_hh && dgi && dgh && hprev && scratch && B > 0 && T > 0);
-    TAG_CHECK_ARG(H % 16 == 0 && (3 * H) % 32 == 0);
+    TAG_CHECK_ARG(H >= 16 && H % 16 == 0 && (3 * H) % 32 == 0);   // (H >= 16: H = 0 and negative H used to reach the launch)
     hipStream_t st = as_stream(stream);
     const dim3 grid(H / 16, (B + 15) / 16, 2);
     const int nblk = (int)(grid.x * grid.y * grid.z);
@@ -966,7 +976,7 @@ extern "C" int tag_gru_backward(const float* dy, const float* y, const float* ga
             if (hipMemsetAsync(gx, 0, off_err - off_x, st) != hipSuccess) { tag_set_error("memset failed"); return TAG_ELAUNCH; }
             const hipError_t e = H == 256 ? gru_launch_persistent(gru_bwd_p4_kernel<256>, g4, args, st)
                                           : gru_launch_persistent(gru_bwd_p4_kernel<128>, g4, args, st);
-            if (e == hipSuccess) return 0;
+            if (e == hipSuccess) { g_gru_last_form[1] = 3; return 0; }
         }
     }
     if ((H == 256 || H == 128) && T > 1) {
@@ -982,7 +992,7 @@ extern "C" int tag_gru_backward(const float* dy, const float* y, const float* ga
             if (hipMemsetAsync(gx, 0, off_err - off_x, st) != hipSuccess) { tag_set_error("memset failed"); return TAG_ELAUNCH; }
             const hipError_t e = H == 256 ? gru_launch_persistent(gru_bwd_persistent_kernel<256>, grid, args, st)
                                           : gru_launch_persistent(gru_bwd_persistent_kernel<128>, grid, args, st);
-            if (e == hipSuccess) return 0;
+            if (e == hipSuccess) { g_gru_last_form[1] = 2; return 0; }
         }
     }
     float* dhbuf = static_cast<float*>(scratch);
@@ -998,6 +1008,7 @@ extern "C" int tag_gru_backward(const float* dy, const float* y, const float* ga
                                dhbuf, B, T, H, s);
     }
     TAG_LAUNCH_CHECK();
+    g_gru_last_form[1] = 1;
     return 0;
 }
 
@@ -1012,3 +1023,6 @@ extern "C" int tag_gru_disable_xcd_fast(void) {
 extern "C" int tag_gru_timed_out(const void* ws_host_copy_of_err_word) {
     return ws_host_copy_of_err_word && *static_cast<const unsigned*>(ws_host_copy_of_err_word) != 0;
 }
+
+// debug query (host only, no launch): 0 = none yet, 1 = per-step kernels, 2 = 16-row persistent, 3 = 4-row persistent
+extern "C" int tag_gru_last_form(int backward) { return g_gru_last_form[backward ? 1 : 0]; }

@@ -123,6 +123,7 @@ _SIGS = {
     "tag_gru_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tag_gru_timed_out": (c_int, [P]),
     "tag_gru_disable_xcd_fast": (c_int, []),
+    "tag_gru_last_form": (c_int, [c_int]),
     "tag_gru_forward": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "tag_gru_backward": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "tag_text_gru_forward": (c_int, [P] * 7 + [c_int] * 4 + [P]),
