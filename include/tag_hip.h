@@ -1234,6 +1234,36 @@ int tag_grounding_counts(const int64_t* regions, const int32_t* counts, int max_
                          const int32_t* gt_count, int max_gt, int B, int NT, double time_resolution, double dtc, double gtc,
                          int32_t* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Phrase-to-label cosine map (label_map.hip; ASMapping*Dataset of datasets/class_mapping_dataset.py in the reference call
+ * sklearn's cosine_similarity(phrase, label_embs) on the host per item).  x (N, D) phrases with row stride ldx, e (C, D) labels
+ * with row stride lde (both >= D, in floats), all fp32.  ws (tag_label_map_ws_bytes = 4 (N + C), a function of the shape alone,
+ * 0 for a shape the call would refuse) is never zeroed; no atomics: the same bits on every run.
+ *
+ * tag_label_map: s[i][c] = x_i . e_c / (||x_i|| ||e_c||) in fp32, a zero row's norm taken as 1 (its s is exactly 0): the
+ *   products on the exact-fp32 MFMA (operands not rounded), 1 / ||row|| once per call into ws (from an fp64 sum of squares),
+ *   s = (x_i . e_c * 1/||x_i||) * 1/||e_c||:  |s - exact| <= (D + 8) 2^-24.  Label c is in the WINDOW of row i when
+ *   th0 <= s <= th1 && s != 0 (fp32 comparisons).  Written for every row:
+ *     best[i] (int32) = argmax_c s, ties to the lowest c;  best_sim[i] (fp32) that value;  min_sim[i] (fp32) = min_c s;
+ *     win_best[i] (int32) = the argmax over the window, ties to the lowest c, -1 for an empty window;  win_count[i] (int32) = the
+ *     window's size;  win_bits (N x ceil(C / 32) uint32, dense): bit c % 32 of word c / 32 is set exactly for the window members,
+ *     bits past C are 0;
+ *     sim (N, C) fp32 with row stride lds >= C, or NULL: then no (N, C) array exists anywhere.
+ *   Every selection is made on the very values sim receives, and every other output has the same bits with and without sim.
+ *   Identical label rows score identically bit for bit.  A column past C never wins, is in no window and is never written.
+ *   A NaN input may give any selection (best stays inside [0, C)), never an access out of bounds.
+ * tag_label_map_topk: idx (N x k int32, dense) = the window members of each row of sim (as tag_label_map wrote it, same th0 and
+ *   th1) in descending s, ties to the lowest c, padded with -1; column 0 is win_best.  1 <= k <= TAG_LABEL_MAP_MAX_TOPK.
+ * TAG_EINVAL before any launch, the numbers named in tag_last_error: N, C or D < 1, a row stride below the width, a null pointer
+ * (sim of tag_label_map excepted), N or C above 2^31 - 129, k outside its range.
+ */
+#define TAG_LABEL_MAP_MAX_TOPK 32
+size_t tag_label_map_ws_bytes(int N, int C, int D);
+int tag_label_map(const float* x, int ldx, const float* e, int lde, float th0, float th1, int* best, float* best_sim,
+                  float* min_sim, int* win_best, int* win_count, unsigned* win_bits, float* sim, int lds, int N, int C, int D,
+                  void* ws, void* stream);
+int tag_label_map_topk(const float* sim, int lds, float th0, float th1, int* idx, int N, int C, int k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,29 @@ Differences from the reference: waveforms come through ``WaveformStore``; ``clus
 joblib is importable); labels and distances come from ONE assignment call on the device (``device`` keyword, csrc/kmeans.hip)
 instead of ``predict`` plus ``transform(...).min(1)``; the distinct phrases are taken in order of first appearance (the
 reference's ``list(set(...))`` order changes nothing it computes).
+
+The AudioSet class-mapping datasets (mirror of ``ASMappingEvalDataset``, ``ASMappingWeakDataset``, ``ASMappingEvalLabelSimDataset``
+and ``ASMappingStrongDataset``, class_mapping_dataset.py:15-293 in the reference): a phrase becomes AudioSet class indices through
+the cosine similarity of its embedding (``phrase_embed`` pickle) to the label embeddings (``as_label_embed`` pickle, taken in
+insertion order), inside the ``thresholds`` window.  Same constructor keywords plus ``device``, same item keys and dtypes.
+
+* ``ASMappingEvalDataset``  one item per (clip, phrase): ``text_idx`` is the most similar label.
+* ``ASMappingEvalLabelSimDataset``  the same items with ``label_sim``, the float32 similarities to all labels.
+* ``ASMappingWeakDataset``  one item per clip: ``label`` (classes_num,) set at the labels of every phrase of at most
+  ``max_phrase_words`` words and, with ``use_audioset_label``, at the clip's AudioSet labels (``audioset_label`` TSV, names joined
+  by ``;``, indexed by ``label_encoder``: a pickle of anything with ``.classes_`` or a JSON list of names).  ``min_sim_percent``
+  replaces ``thresholds`` by [that percentile of the best similarities of ALL phrases of ``phrase_embed``, 1.0].
+* ``ASMappingStrongDataset``  ``weak_label``, ``strong_label`` (n_frame, classes_num) and ``strong_label_mask`` (classes_num,), the
+  classes some phrase of the clip labels (the input of ``MaskedFrameBceLoss``); ``max_audio_length`` is accepted and, as in the
+  reference, does not crop.
+
+Differences from the reference: the reference calls sklearn's ``cosine_similarity`` for one phrase in every ``__getitem__``;
+here ALL device work happens in ``__init__``, one ``utils.label_map.LabelMap`` call over the distinct phrases (csrc/label_map.hip),
+and ``__getitem__`` is host-only lookups, so loader workers never open the GPU.  A phrase labels ONLY members of its window
+(thresholds[0] <= sim <= thresholds[1], sim != 0), at most ``topk`` of them, in both datasets: the reference's
+``np.argsort(sim)[::-1][:topk]`` also picks zero-valued entries, in an order that depends on numpy's sort, when fewer than
+``topk`` labels lie in the window and, in the Strong dataset (which lacks the Weak one's guard), when none does.  The number of
+label embeddings must equal ``classes_num`` (``ValueError``).
 """
 import json
 import math
@@ -32,7 +55,8 @@ import random
 
 import numpy as np
 
-from .waveform_store import WaveformStore
+from ..utils.label_map import LabelMap, stack_embeddings
+from .waveform_store import WaveformStore, load_dict_from_csv
 
 
 class _MappingBase:
@@ -194,3 +218,179 @@ class SpectralMappingDataset(_MappingBase):
 
     def __len__(self):
         return len(self.data)
+
+
+class _ASMappingBase:
+    """The files all four AudioSet mapping datasets read and their (clip, phrase) index."""
+
+    def _read(self, waveform, label, phrase_embed, as_label_embed, device):
+        self.store = waveform if isinstance(waveform, WaveformStore) else WaveformStore(waveform)
+        with open(label) as f:
+            self.data = json.load(f)
+        with open(phrase_embed, "rb") as f:
+            self.phrase_to_emb = pickle.load(f)
+        with open(as_label_embed, "rb") as f:
+            self.label_to_emb = pickle.load(f)
+        self.label_embs = stack_embeddings(self.label_to_emb)
+        self.label_map = LabelMap(self.label_embs, device=device)
+
+    def generate_index(self):
+        self.idxs = [(a, p) for a, item in enumerate(self.data) for p in range(len(item["phrases"]))]
+
+    def _distinct_phrases(self, max_words=None):
+        phrases = dict.fromkeys(p["phrase"] for item in self.data for p in item["phrases"])
+        return [p for p in phrases if max_words is None or len(p.split()) <= max_words]
+
+    def _map_phrases(self, phrases, thresholds=None, topk=1, want_sim=False):
+        if not phrases:
+            return None
+        embs = np.stack([np.asarray(self.phrase_to_emb[p], dtype=np.float32).reshape(-1) for p in phrases])
+        return self.label_map.map(embs, thresholds, topk, want_sim=want_sim)
+
+    def __len__(self):
+        return len(self.idxs)
+
+
+class ASMappingEvalDataset(_ASMappingBase):
+    def __init__(self, waveform, label: str, phrase_embed: str, as_label_embed: str, device="cuda:0"):
+        self._read(waveform, label, phrase_embed, as_label_embed, device)
+        self.generate_index()
+        phrases = self._distinct_phrases()
+        mapped = self._map_phrases(phrases)
+        self.phrase_to_label = dict(zip(phrases, mapped.best)) if phrases else {}
+
+    def __getitem__(self, index):
+        audio_idx, phrase_idx = self.idxs[index]
+        item = self.data[audio_idx]
+        phrase_item = item["phrases"][phrase_idx]
+        return {
+            "audio_id": item["audio_id"],
+            "audiocap_id": item["audiocap_id"],
+            "start_index": phrase_item["start_index"],
+            "end_index": phrase_item["end_index"],
+            "waveform": self.store[item["audio_id"]],
+            "text": item["tokens"],
+            "text_idx": self.phrase_to_label[phrase_item["phrase"]],
+        }
+
+
+class ASMappingEvalLabelSimDataset(_ASMappingBase):
+    def __init__(self, waveform, label: str, phrase_embed: str, as_label_embed: str, device="cuda:0"):
+        self._read(waveform, label, phrase_embed, as_label_embed, device)
+        self.generate_index()
+        phrases = self._distinct_phrases()
+        mapped = self._map_phrases(phrases, want_sim=True)
+        self.phrase_to_sim = dict(zip(phrases, mapped.sim)) if phrases else {}
+
+    def __getitem__(self, index):
+        audio_idx, phrase_idx = self.idxs[index]
+        item = self.data[audio_idx]
+        phrase_item = item["phrases"][phrase_idx]
+        return {
+            "audiocap_id": item["audiocap_id"],
+            "start_index": phrase_item["start_index"],
+            "end_index": phrase_item["end_index"],
+            "waveform": self.store[item["audio_id"]],
+            "label_sim": self.phrase_to_sim[phrase_item["phrase"]],
+        }
+
+
+def _read_classes(label_encoder):
+    """The class names of a label encoder: a JSON list of names, or a pickle of anything with ``.classes_``."""
+    if str(label_encoder).endswith(".json"):
+        with open(label_encoder) as f:
+            return list(json.load(f))
+    with open(label_encoder, "rb") as f:
+        return list(pickle.load(f).classes_)
+
+
+class ASMappingWeakDataset(_ASMappingBase):
+    def __init__(self, waveform, label: str, audioset_label: str, phrase_embed: str, as_label_embed: str, label_encoder: str,
+                 thresholds=(0.5, 1.0), min_sim_percent: float = None, use_audioset_label: bool = True, topk: int = 1,
+                 max_phrase_words: int = 10, max_audio_length: float = None, sample_rate: int = 32000, device="cuda:0"):
+        self._read(waveform, label, phrase_embed, as_label_embed, device)
+        self.thresholds = thresholds
+        self.min_sim_percent = min_sim_percent
+        self.topk = topk
+        self.max_phrase_words = max_phrase_words
+        self.classes = _read_classes(label_encoder)
+        self.classes_num = len(self.classes)
+        if len(self.label_embs) != self.classes_num:
+            raise ValueError(f"as_label_embed holds {len(self.label_embs)} label embeddings, label_encoder {self.classes_num} classes")
+        self.label_to_idx = {lbl: idx for idx, lbl in enumerate(self.classes)}
+        self.aid_to_aslabel = load_dict_from_csv(audioset_label, ("audio_id", "event_labels"))
+        self.use_audioset_label = use_audioset_label
+        self.max_audio_len = None if max_audio_length is None else int(max_audio_length * sample_rate)
+        self.sample_rate = sample_rate
+
+        msg = "either one of 'thresholds' or 'min_sim_percent' can be set"
+        if min_sim_percent is not None:
+            assert thresholds is None, msg
+            assert topk == 1, "currently only support topk = 1 when setting similarity percent"
+            self.calc_thresholds()
+        if thresholds is not None:
+            assert min_sim_percent is None, msg
+        self.prepare_phrase_label()
+
+    def calc_thresholds(self):
+        sims = self.label_map.map(stack_embeddings(self.phrase_to_emb)).best_sim
+        self.thresholds = [np.percentile(sims, self.min_sim_percent), 1.0]
+
+    def prepare_phrase_label(self):
+        phrases = self._distinct_phrases(self.max_phrase_words)
+        mapped = self._map_phrases(phrases, self.thresholds, self.topk)
+        self.phrase_to_labels = dict(zip(phrases, mapped.labels)) if phrases else {}
+
+    def _kept(self, item):
+        return [p for p in item["phrases"] if len(p["phrase"].split()) <= self.max_phrase_words]
+
+    def _add_audioset_label(self, item, label):
+        if self.use_audioset_label:
+            for as_label in self.aid_to_aslabel[item["audio_id"]].split(";"):
+                label[self.label_to_idx[as_label]] = 1
+
+    def __getitem__(self, index):
+        item = self.data[index]
+        waveform = self.store[item["audio_id"]]
+        if self.max_audio_len is not None and waveform.shape[0] > self.max_audio_len:
+            start = random.randint(0, waveform.shape[0] - self.max_audio_len)
+            waveform = waveform[start: start + self.max_audio_len]
+        label = np.zeros(self.classes_num)
+        for phrase_item in self._kept(item):
+            label[self.phrase_to_labels[phrase_item["phrase"]]] = 1
+        self._add_audioset_label(item, label)
+        return {"audiocap_id": item["audiocap_id"], "audio_id": item["audio_id"], "text": item["tokens"], "waveform": waveform,
+                "label": label}
+
+    def __len__(self):
+        return len(self.data)
+
+
+class ASMappingStrongDataset(ASMappingWeakDataset):
+    def __init__(self, waveform, label: str, audioset_label: str, phrase_embed: str, as_label_embed: str, label_encoder: str,
+                 time_resolution: float = 0.02, sample_rate: int = 32000, thresholds=(0.5, 1.0), use_audioset_label: bool = True,
+                 topk: int = 1, max_phrase_words: int = 10, max_audio_length: float = None, device="cuda:0"):
+        super().__init__(waveform=waveform, label=label, audioset_label=audioset_label, phrase_embed=phrase_embed,
+                         as_label_embed=as_label_embed, label_encoder=label_encoder, thresholds=thresholds, min_sim_percent=None,
+                         use_audioset_label=use_audioset_label, topk=topk, max_phrase_words=max_phrase_words,
+                         max_audio_length=max_audio_length, sample_rate=sample_rate, device=device)
+        self.time_resolution = time_resolution
+
+    def __getitem__(self, index):
+        item = self.data[index]
+        waveform = self.store[item["audio_id"]]
+        weak_label = np.zeros(self.classes_num)
+        n_frame = math.floor(waveform.shape[0] / self.sample_rate / self.time_resolution) + 1
+        strong_label = np.zeros((n_frame, self.classes_num))
+        strong_label_mask = np.zeros(self.classes_num)
+        for phrase_item in self._kept(item):
+            indices = self.phrase_to_labels[phrase_item["phrase"]]
+            weak_label[indices] = 1
+            strong_label_mask[indices] = 1
+            for start, end in phrase_item["segments"]:
+                onset = round(start / self.time_resolution)
+                offset = round(end / self.time_resolution)
+                strong_label[onset: offset, indices] = 1
+        self._add_audioset_label(item, weak_label)
+        return {"audiocap_id": item["audiocap_id"], "audio_id": item["audio_id"], "text": item["tokens"], "waveform": waveform,
+                "weak_label": weak_label, "strong_label": strong_label, "strong_label_mask": strong_label_mask}

@@ -5,6 +5,7 @@ the current HIP stream; there is no eager fallback -- a CPU tensor or a missing 
 """
 from __future__ import annotations
 
+import collections
 import math
 from typing import Optional
 
@@ -2642,3 +2643,52 @@ def grounding_counts(regions, counts, gt, gt_count, time_resolution, dtc=0.5, gt
     call("tag_grounding_counts", ptr(regions), ptr(counts), maxk, ptr(gt) if max_gt else None, ptr(gt_count), max_gt, B, NT,
          float(time_resolution), float(dtc), float(gtc), ptr(out))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# phrase-to-label cosine map of the ASMapping datasets (sklearn's cosine_similarity per item on the host in the reference),
+# label_map.hip
+# ------------------------------------------------------------------------------------------------
+
+#: the largest k of tag_label_map_topk (= TAG_LABEL_MAP_MAX_TOPK of include/tag_hip.h)
+LABEL_MAP_MAX_TOPK = 32
+
+LabelMapResult = collections.namedtuple("LabelMapResult", "best best_sim min_sim win_best win_count win_bits sim idx")
+
+
+def label_map(x, e, th0, th1, topk=1, want_sim=False):
+    """The cosine map of phrases x (N, D) onto labels e (C, D), one march on the exact-fp32 MFMA: s = x_i . e_c / (||x_i|| ||e_c||)
+    in fp32 (a zero row's norm taken as 1), the WINDOW of a row = the labels with th0 <= s <= th1 and s != 0, th0 / th1 compared as
+    float32.  -> LabelMapResult of device tensors:
+
+    best (N,) int32 argmax_c s (ties to the lowest c), best_sim (N,) fp32, min_sim (N,) fp32; win_best (N,) int32 the argmax over
+    the window or -1, win_count (N,) int32, win_bits (N, ceil(C / 32)) int32 (bit c % 32 of word c // 32; bits past C are 0);
+    sim (N, C) fp32 when want_sim, else None (no (N, C) array exists unless topk >= 2 needs one); idx (N, min(topk, C)) int32,
+    the window members in descending s padded with -1, when topk >= 2, else None (win_best is the topk == 1 answer, win_bits the
+    topk <= 0 one).  Row-strided views of x and e are passed as they are.  The same bits on every run."""
+    xr, er = _phrase_sim_rows(x, "x"), _phrase_sim_rows(e, "e")
+    if er.device != xr.device or er.shape[1] != xr.shape[1]:
+        raise RuntimeError(f"e {tuple(er.shape)} on {er.device}: expected x's device {xr.device} and D = {xr.shape[1]}")
+    (N, D), C = xr.shape, er.shape[0]
+    th0, th1, topk = float(th0), float(th1), int(topk)
+    if math.isnan(th0) or math.isnan(th1):
+        raise ValueError(f"label_map: thresholds must be numbers, got {th0}, {th1}")
+    k = min(topk, C)
+    if k > LABEL_MAP_MAX_TOPK:
+        raise ValueError(f"label_map: topk = {topk} over {C} labels exceeds {LABEL_MAP_MAX_TOPK}; topk <= 0 gives the whole window")
+    nws = query("tag_label_map_ws_bytes", N, C, D)
+    if nws == 0:
+        raise RuntimeError(f"label_map: N = {N}, C = {C}, D = {D}: expected N and C <= {2**31 - 129}")
+    dev = xr.device
+    best, win_best, win_count = (torch.empty(N, device=dev, dtype=torch.int32) for _ in range(3))
+    best_sim, min_sim = torch.empty(N, device=dev, dtype=F32), torch.empty(N, device=dev, dtype=F32)
+    win_bits = torch.empty(N, (C + 31) // 32, device=dev, dtype=torch.int32)
+    sim = torch.empty(N, C, device=dev, dtype=F32) if (want_sim or k >= 2) else None
+    ws = _ws(nws, xr)
+    call("tag_label_map", ptr(xr), xr.stride(0), ptr(er), er.stride(0), th0, th1, ptr(best), ptr(best_sim), ptr(min_sim),
+         ptr(win_best), ptr(win_count), ptr(win_bits), ptr(sim), C, N, C, D, ptr(ws))
+    idx = None
+    if k >= 2:
+        idx = torch.empty(N, k, device=dev, dtype=torch.int32)
+        call("tag_label_map_topk", ptr(sim), C, th0, th1, ptr(idx), N, C, k)
+    return LabelMapResult(best, best_sim, min_sim, win_best, win_count, win_bits, sim if want_sim else None, idx)
