@@ -90,7 +90,7 @@ int tag_bn_stats(const float* x, long rows, int C, int pre_op, const float* gamm
                  float* invstd, float* scale, float* shift, void* ws, void* stream);
 /* the same outputs from the partial statistics a conv kernel wrote in its epilogue (P rows; layout: see
  * tag_conv3x3_forward).  A row's pivot is any value near its pixels (the tile mean rounded to fp32 in conv.hip / conv_x3.hip,
- * the first output of the row in conv_wino.hip and the Cin = 1 conv); the rows are merged in fp64 (Chan et al.) about the pivot of
+ * the first output of the row in conv_wino.hip, conv_wino_fused.hip and the Cin = 1 conv); the rows are merged in fp64 (Chan et al.) about the pivot of
  * ROW 0, whatever its count, so row 0 must not be empty.  Every conv epilogue keeps that: its row 0 belongs to the first tile, strip or M group of clip 0, which starts at
  * pixel (0, 0) of that clip and so holds at least one pixel (conv.hip, conv_x3.hip, conv_rows.hip: h0 = 0 < H; conv_wino.hip,
  * conv_wino_fused.hip: tile 0, output (0, 0)).  Rows with count 0 occur only further down (tile halves past H, padding rows
@@ -213,14 +213,18 @@ int tag_conv3x3_dgrad_bnsums(const float* dy, const float* wpack, float* da, con
 /* Winograd F(2x2,3x3) form of the same convolution, all fp32: the A1 ConvBlock convs of models/panns.py:29-38,49-50 with 2.25 x
  * fewer MFMA FLOP than tag_conv3x3_forward.  Drop-in for tag_conv3x3_forward(stats) / tag_conv3x3_dgrad_bnsums / _dgrad_poolsums /
  * _forward_bnrelu_pool_eval / tag_conv3x3_wgrad.  Error vs an fp64 convolution: at or below the direct fp32 kernel's.
- *   Channel counts that are multiples of 64 (every Cnn8Rnn layer but the Cin = 1 conv): ONE kernel per launch (round 6,
- *   csrc/conv_wino_fused.hip) -- the input transform B^T d B (producer BatchNorm+ReLU prologue and zero padding applied on load) is
+ *   Cout % 64 == 0 with Cin % 8 == 0 (of the shapes tag_conv3x3_wino_ok serves: Cin = 32 too, besides the multiples of 64; every
+ *   Cnn8Rnn layer but the Cin = 1 conv): ONE kernel per launch (round 6, csrc/conv_wino_fused.hip) -- the input transform B^T d B (producer BatchNorm+ReLU prologue and zero padding applied on load) is
  *   formed on the way into LDS, the 16 products (tiles x Cin).(Cin x Cout) run on the exact-fp32 MFMA into 16 accumulator sets that
  *   stay in registers, the output transform A^T m A and the epilogue (BatchNorm statistics rows [K | r | q][Cout] + counts for
  *   tag_bn_stats_from_partials / rows [sum g | sum g*xhat][Cout] for tag_bn_grad_from_partials / pooled inference output) work from
- *   a parked output tile.  No workspace (ws is ignored, tag_conv3x3_wino_ws_bytes = 64); one partial row per 64-tile block.
- *   Other channel counts (32..1024 whose quarter divides 256, Cin % 32 == 0): round 5's plane form (csrc/conv_wino.hip): input
- *   transform -> 16 batched products -> output transform through planes in ws.
+ *   a parked output tile.  No workspace (ws is ignored, tag_conv3x3_wino_ws_bytes = 64); one partial row per 64-tile block
+ *   (tiles in (b, tile row, tile column) order, 2 x 2 outputs each), its pivot the output at pixel (0, 0) of the block's first tile.
+ *   Exactly Cout = 32 (Cin = 32, 64, 128, 256, 512 or 1024): round 5's plane form (csrc/conv_wino.hip): input transform -> 16
+ *   batched products -> output transform through planes in ws, 16 T (Cin + Cout) floats, T = B ceil(H/2) ceil(W/2) tiles; partial
+ *   rows: 32 per 256 tiles (row 32 g + s: tiles 256 g + 32 it + s, it = 0..7; pivot = the output at pixel (0, 0) of the first of
+ *   them; a row without tiles is written as zeros with count 0).
+ *   Served shapes (tag_conv3x3_wino_ok): both counts multiples of 64 up to 1024, or both of 32, 64, 128, 256, 512, 1024.
  *   ufwd / udgrad (16 * Cin * Cout floats each): G g G^T of the filter / of the tap-flipped, channel-swapped filter -- an OPAQUE
  *   pack of tag_pack_conv_weight_wino (fused form: per (64-cout block, 8-channel K chunk) the kernel's LDS image [xi][n 64][k 8];
  *   plane form: [16][Cin][Cout] / [16][Cout][Cin]); P = tag_conv3x3_wino_stats_rows; tag_conv3x3_wino_ok: 1 when the shape is served
@@ -230,19 +234,24 @@ int tag_pack_conv_weight_wino(const float* w /*(Cout,Cin,3,3)*/, float* ufwd, fl
 size_t tag_conv3x3_wino_ws_bytes(int B, int H, int W, int Cin, int Cout);
 int tag_conv3x3_wino_stats_rows(int B, int H, int W, int Cout);
 /* weight gradient in the Winograd domain: dw (Cout,Cin,3,3) = G^T [ sum over tiles (A dY A^T) (.) (B^T prologue(x) B) ] G -- the
- * adjoint of the forward form.  Fused form (channel counts multiples of 64): both transforms at staging, 64 ci x 64 co x 16 xi
- * accumulators per workgroup over one slice of the tile axis, ws = 2 S partial filters folded in a fixed order.  Plane form: 16 x S
- * batched products over K slices.  Drop-in for tag_conv3x3_wgrad on the shapes tag_conv3x3_wino_ok accepts. */
+ * adjoint of the forward form.  Fused form (ONLY when Cin and Cout are both multiples of 64): both transforms at staging, 64 ci x
+ * 64 co x 16 xi accumulators per workgroup over one slice of the tile axis (one transform row x 128 ci x 128 co when both are
+ * multiples of 128), ws = 2 S partial filters folded in a fixed order.  Every other served pair (Cin = 32 or Cout = 32, whatever
+ * form the forward took): plane form, 16 x S batched products over K slices of kc rows, the planes padded with zero rows to
+ * Tpad = S kc.  Drop-in for tag_conv3x3_wgrad on the shapes tag_conv3x3_wino_ok accepts. */
 size_t tag_conv3x3_wino_wgrad_ws_bytes(int B, int H, int W, int Cin, int Cout);
-/* v_saved (optional, plane form only): the transformed input the forward launch of the same convolution left in its v_keep
- * buffer -- the input transform is then not repeated (x may be NULL); allowed when tag_conv3x3_wino_wgrad_can_reuse_v (0 for the
- * fused form, which has no planes). */
+/* v_saved (optional, plane-form weight gradient only): the transformed input the forward launch of the same convolution left
+ * in its v_keep buffer -- the input transform is then not repeated (x may be NULL); allowed when
+ * tag_conv3x3_wino_wgrad_can_reuse_v: 0 for the fused weight gradient, which has no planes, and 0 where the K slices need zero
+ * rows (Tpad > T); otherwise the call is refused. */
 int tag_conv3x3_wino_wgrad_can_reuse_v(int B, int H, int W, int Cin, int Cout);
 int tag_conv3x3_wino_wgrad(const float* x, int prologue, const float* in_scale, const float* in_shift, const float* dy,
                            float* dw /*(Cout,Cin,3,3)*/, int B, int H, int W, int Cin, int Cout, void* ws, const float* v_saved,
                            void* stream);
-/* v_keep (optional, plane form): 16 * T * Cin floats that receive the transformed input instead of ws (which then
- * needs the product planes only: 16 * T * Cout floats) -- kept by the caller for tag_conv3x3_wino_wgrad(v_saved). */
+/* v_keep (optional): 16 * T * Cin floats [16][T][Cin] that receive the transformed input B^T prologue(x) B -- kept by the caller
+ * for tag_conv3x3_wino_wgrad(v_saved).  Plane form: instead of ws (which then needs the product planes only: 16 * T * Cout
+ * floats).  The fused forward honours it too (Cin = 32 -> Cout % 64 == 0 is the pair whose weight gradient is plane form): the
+ * input transform then runs as a side launch, y has the same bits. */
 int tag_conv3x3_wino_forward(const float* x, const float* ufwd, int prologue, const float* in_scale, const float* in_shift,
                              float* y, float* stats, int B, int H, int W, int Cin, int Cout, void* ws, float* v_keep,
                              void* stream);
