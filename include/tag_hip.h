@@ -675,6 +675,22 @@ int tag_segments(const float* sim, int ld, int B, int T, const double* threshold
                  int n_connect, int64_t* regions, int32_t* counts, int max_regions, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * P1 with a double threshold (sed_eval.hip; utils/sed_utils.py:145-198 _double_threshold(..., return_arr=False)): the
+ * contiguous runs of x > low[i] that hold a frame with x > high[i], THEN connect_ (gap <= n_connect) -- a run without a high
+ * frame is dropped before the connection and does not bridge its neighbours.  One (clip, operating point) pair per thread.
+ * sim (B,T) ld; high, low (NT) double, one operating point per entry, high[i] >= low[i] (the caller's duty: the wrapper
+ * refuses other pairs); regions, counts, max_regions >= (T + 1) / 2 exactly as tag_segments writes them, so every consumer of
+ * its outputs takes these unchanged.
+ * COMPARISON PRECISION DIFFERS FROM tag_segments: the reference compares the float32 scores with a Python float here, which
+ * numpy rounds to float32 (np.float32(0.3) > 0.3 is False), so both comparisons are fp32 against (float)high[i] and
+ * (float)low[i]; tag_segments follows run_strong.py, whose np.float64 thresholds promote the scores, and compares in fp64.
+ * TAG_EINVAL before any launch: a null pointer, B, T or NT < 1, ld < T, B * NT above 2^31 - 65, n_connect < 0, max_regions
+ * below (T + 1) / 2.
+ * ------------------------------------------------------------------------------------------- */
+int tag_segments_double(const float* sim, int ld, int B, int T, const double* high, const double* low, int NT, int n_connect,
+                        int64_t* regions, int32_t* counts, int max_regions, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * O1: clip_grad_norm_ + Adam on a flat fp32 buffer (run_strong.py:143-145; torch.optim.Adam).
  * tag_sumsq: out[0] (double) = sum g^2 (zero-filled by the call).  tag_adam_step reads the squared
  * norm from device memory: coef = min(1, max_norm / (sqrt(gnorm_sq) + 1e-6)); max_norm <= 0 disables.
@@ -1242,6 +1258,33 @@ int tag_spectral_apply(const float* Y, int ldy, const float* T, int ldt, const f
 int tag_grounding_counts(const int64_t* regions, const int32_t* counts, int max_regions, const double* gt,
                          const int32_t* gt_count, int max_gt, int B, int NT, double time_resolution, double dtc, double gtc,
                          int32_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Event-based and segment-based counts of the sed_eval protocol (sed_eval.hip; utils/eval_util.py:354-425 compute_sed_eval of
+ * the reference, every (clip, phrase) pair one file with a single label; utils/sed_metrics.py restates the published
+ * definitions on the host and is the yardstick): one launch behind tag_segments / tag_segments_double, one wave per
+ * (clip, operating point) pair.  regions, counts, gt, gt_count as for tag_grounding_counts, det = regions * time_resolution in
+ * fp64 formed the same way.  PRECONDITION: the regions in use of a pair ascend and are disjoint, as tag_segments* write them
+ * (the matching relies on it; other inputs give some count, never an access out of bounds); ground-truth times are >= 0.
+ * out (B,NT,5) int32 = {ev_tp, seg_tp, seg_fp, seg_fn, seg_n} of the pair taken as one file, EXACTLY the host function's:
+ *   ev_tp   the MAXIMUM cardinality of a matching of ground truths and detections (event_matching_type 'optimal'), an edge iff
+ *           fabs(on_g - on_d) <= t_collar and fabs(off_g - off_d) <= max(t_collar, percentage_of_length * (off_g - on_g)), the
+ *           same fp64 operations as on the host.  (Event FP = counts - ev_tp, FN = gt_count - ev_tp: one label, no substitution.)
+ *   seg_*   event rolls at segment_resolution: an event covers segments floor(onset / r) .. ceil(offset / r) - 1 (IEEE fp64
+ *           division), both rolls padded to seg_n = ceil(largest offset of either side / r) segments; per segment TP = both
+ *           active, FP = detection only, FN = reference only.
+ * seg_n is limited to TAG_SED_MAX_SEGMENTS per pair (the time of the word-at-a-time roll, not a buffer).  A pair above it is
+ * never truncated: all five of its entries are -1.  No detection and no ground truth: all 0.  EVERY entry of out is written.
+ * No floating-point value crosses lanes, no atomics.  counts[b][t] > max_regions and gt_count[b] > max_gt (or negative
+ * values) are clamped, never read out of bounds.  Rows beyond the counts are not read.
+ * TAG_EINVAL before any launch: a null pointer (gt may be null when max_gt == 0), B or NT < 1, B * NT above 2^31 - 1,
+ * max_regions outside 1 .. 32768, max_gt outside 0 .. 128, time_resolution or segment_resolution <= 0, t_collar or
+ * percentage_of_length < 0.
+ * ------------------------------------------------------------------------------------------- */
+#define TAG_SED_MAX_SEGMENTS 16384
+int tag_sed_counts(const int64_t* regions, const int32_t* counts, int max_regions, const double* gt, const int32_t* gt_count,
+                   int max_gt, int B, int NT, double time_resolution, double t_collar, double percentage_of_length,
+                   double segment_resolution, int32_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Phrase-to-label cosine map (label_map.hip; ASMapping*Dataset of datasets/class_mapping_dataset.py in the reference call

@@ -2646,6 +2646,97 @@ def grounding_counts(regions, counts, gt, gt_count, time_resolution, dtc=0.5, gt
 
 
 # ------------------------------------------------------------------------------------------------
+# the sed_eval protocol (utils/sed_metrics.py on the host) and the double threshold in front of it, sed_eval.hip
+# ------------------------------------------------------------------------------------------------
+
+#: the most segments of one (clip, operating point) pair tag_sed_counts rolls (= TAG_SED_MAX_SEGMENTS of include/tag_hip.h)
+SED_MAX_SEGMENTS = 16384
+
+
+def segments_double(frame_sim, high, low, n_connect=1):
+    """The double threshold of utils/sed_utils.py:145-198 (``_double_threshold(..., return_arr=False)``) on the device: runs of
+    ``x > low[i]`` that hold a frame with ``x > high[i]``, then ``connect_`` with gap <= n_connect.  high, low: length-NT
+    vectors, one operating point per entry, high[i] >= low[i] (ValueError otherwise, for vectors on the host; vectors already on
+    the device are not read back).  Both are rounded to float32 and compared
+    in float32, as numpy compares a float32 array with a Python float -- ``segments`` compares in float64.  Returns ``segments``'
+    (regions (B,NT,maxK,2) int64, counts (B,NT) int32)."""
+    frame_sim = _chk(frame_sim, "frame_sim")
+    B, T = frame_sim.shape
+    hi = torch.as_tensor(high, dtype=torch.float64).reshape(-1)
+    lo = torch.as_tensor(low, dtype=torch.float64).reshape(-1)
+    NT = hi.numel()
+    if NT < 1 or lo.numel() != NT:
+        raise ValueError(f"segments_double: high and low must be vectors of one length >= 1, got {hi.numel()} and {lo.numel()}")
+    # (host vectors are checked; device vectors are taken as they are -- SedEvaluator checked its pairs once -- so that the
+    #  call reads nothing back: with high < low the kernel keeps the runs of x > low that hold a frame above high, no more)
+    if not (hi.is_cuda or lo.is_cuda) and not bool((hi >= lo).all()):
+        raise ValueError("segments_double: every high threshold must be >= its low threshold (a NaN is neither), got high "
+                         f"{hi.tolist()}, low {lo.tolist()}")
+    hi, lo = hi.to(frame_sim.device), lo.to(frame_sim.device)
+    maxk = (T + 1) // 2
+    regions = torch.zeros(B, NT, maxk, 2, device=frame_sim.device, dtype=torch.int64)
+    counts = torch.zeros(B, NT, device=frame_sim.device, dtype=torch.int32)
+    call("tag_segments_double", ptr(frame_sim), T, B, T, ptr(hi), ptr(lo), NT, int(n_connect), ptr(regions), ptr(counts), maxk)
+    return regions, counts
+
+
+def sed_counts(regions, counts, gt, gt_count, time_resolution, t_collar=0.2, percentage_of_length=0.2, segment_resolution=1.0,
+               out=None, check=True):
+    """``segments`` / ``segments_double`` outputs + the clips' ground truths -> (B, NT, 5) int32 ``{ev_tp, seg_tp, seg_fp, seg_fn,
+    seg_n}`` per (clip, operating point): the integers utils.sed_metrics.event_based_counts (maximum matching inside the
+    collars) and segment_based_counts (event rolls at ``segment_resolution``) give for that clip as one file, exactly
+    (sed_eval.hip).  Arguments as for ``grounding_counts``; the regions in use must ascend and be disjoint, ground-truth times
+    must be >= 0.  A pair may span at most SED_MAX_SEGMENTS segments.  Every entry of ``out`` (given or new) is written.
+    check: refuse gt_count outside [0, Gmax], counts outside [0, maxK] and a pair above the segment limit (ONE host read);
+    without it the kernel clamps the counts and writes -1 into all five entries of a pair above the limit."""
+    if not regions.is_cuda:
+        _chk(regions, "regions")
+    if regions.dtype != torch.int64 or regions.dim() != 4 or regions.shape[3] != 2 or not regions.is_contiguous():
+        raise RuntimeError(f"regions: expected the contiguous int64 (B,NT,maxK,2) of ops.segments, got {regions.dtype} "
+                           f"{tuple(regions.shape)}")
+    B, NT, maxk, _ = regions.shape
+    counts = _grounding_tensor(counts, "counts", torch.int32, (B, NT), regions, " (ops.segments)")
+    gt = torch.as_tensor(gt)
+    if gt.dim() != 3 or gt.shape[2] != 2:
+        raise RuntimeError(f"gt: expected float64 ({B},Gmax,2), got {gt.dtype} {tuple(gt.shape)}")
+    max_gt = gt.shape[1]
+    if B < 1 or NT < 1:
+        raise RuntimeError(f"sed_counts: expected B, NT >= 1, got {B}, {NT}")
+    gt_count = torch.as_tensor(gt_count)
+    if gt_count.dtype != torch.int32 or tuple(gt_count.shape) != (B,):
+        raise RuntimeError(f"gt_count: expected {torch.int32} ({B},), got {gt_count.dtype} {tuple(gt_count.shape)}")
+    time_resolution, segment_resolution = float(time_resolution), float(segment_resolution)
+    gt = _grounding_tensor(gt, "gt", torch.float64, (B, max_gt, 2), regions, "")
+    gt_count = gt_count.to(regions.device).contiguous()
+    if check and max_gt <= 128 and maxk >= 1:                   # (the sizes the library refuses it names itself)
+        # the largest offsets in use, in one read with the ends of the counts (every integer here is exact in fp64)
+        used = torch.arange(maxk, device=regions.device) < counts[..., None]
+        last_frame = torch.where(used, regions[..., 1], 0).max()
+        gt_used = torch.arange(max_gt, device=regions.device) < gt_count[:, None]
+        zero = torch.zeros((), device=regions.device, dtype=torch.float64)
+        last_gt = torch.where(gt_used, gt[..., 1], zero).max() if max_gt else zero
+        ends = [counts.min(), counts.max(), gt_count.min(), gt_count.max(), last_frame, last_gt]
+        lo_c, hi_c, lo_g, hi_g, last_frame, last_gt = torch.stack([e.double() for e in ends]).tolist()
+        if lo_g < 0 or hi_g > max_gt or lo_c < 0 or hi_c > maxk:
+            raise RuntimeError(f"sed_counts: gt_count must lie in [0, {max_gt}] and counts in [0, {maxk}], got "
+                               f"[{int(lo_g)}, {int(hi_g)}] and [{int(lo_c)}, {int(hi_c)}]")
+        if not math.isfinite(last_gt):
+            raise RuntimeError(f"gt: an offset in use is not finite ({last_gt})")
+        if segment_resolution > 0 and time_resolution > 0:
+            n_seg = max(math.ceil(last_frame * time_resolution / segment_resolution), math.ceil(last_gt / segment_resolution))
+            if not n_seg <= SED_MAX_SEGMENTS:
+                raise RuntimeError(f"sed_counts: segment_resolution = {segment_resolution} cuts the longest pair into {n_seg} "
+                                   f"segments; at most {SED_MAX_SEGMENTS} are taken")
+    if out is None:
+        out = torch.empty(B, NT, 5, device=regions.device, dtype=torch.int32)
+    elif not out.is_cuda or out.dtype != torch.int32 or tuple(out.shape) != (B, NT, 5) or not out.is_contiguous():
+        raise RuntimeError(f"out: expected contiguous int32 ({B},{NT},5) on the device, got {out.dtype} {tuple(out.shape)}")
+    call("tag_sed_counts", ptr(regions), ptr(counts), maxk, ptr(gt) if max_gt else None, ptr(gt_count), max_gt, B, NT,
+         time_resolution, float(t_collar), float(percentage_of_length), segment_resolution, ptr(out))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # phrase-to-label cosine map of the ASMapping datasets (sklearn's cosine_similarity per item on the host in the reference),
 # label_map.hip
 # ------------------------------------------------------------------------------------------------

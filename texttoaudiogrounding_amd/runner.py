@@ -348,6 +348,16 @@ class StrongRunner:
                                             int(eval_config.get("window_size", 1)), float(eval_config["time_resolution"]),
                                             dtc=eval_config.get("dtc_threshold", 0.5), gtc=eval_config.get("gtc_threshold", 0.5),
                                             device=self.device)
+        self._update_over_batches(ev, batches, ground_truth)
+        result = ev.compute(float(sum(durations[k] for k in ground_truth)), max_efpr=eval_config.get("max_efpr"),
+                            beta=eval_config.get("beta", 1.0), min_threshold=eval_config.get("min_threshold", 0.0),
+                            max_threshold=eval_config.get("max_threshold", 1.0))
+        ops.check_async_errors()
+        return result
+
+    def _update_over_batches(self, ev, batches, ground_truth: Dict) -> None:
+        """The batch loop ``evaluate`` and ``evaluate_sed`` share: the model in eval() under no_grad, every pair keyed
+        ``f"{audiocap_id}_{start_index}"``, the pairs without a ground-truth row left out, ``ev.update`` on the rest."""
         self.model.eval()
         with torch.no_grad():
             for batch in batches:
@@ -360,9 +370,29 @@ class StrongRunner:
                 if keep.size != len(keys):
                     frame_sim = frame_sim.index_select(0, torch.as_tensor(keep).to(frame_sim.device))
                 ev.update(frame_sim, gt[keep], gt_count[keep])
-        result = ev.compute(float(sum(durations[k] for k in ground_truth)), max_efpr=eval_config.get("max_efpr"),
-                            beta=eval_config.get("beta", 1.0), min_threshold=eval_config.get("min_threshold", 0.0),
-                            max_threshold=eval_config.get("max_threshold", 1.0))
+
+    def evaluate_sed(self, batches, ground_truth: Dict, eval_config: Dict) -> Dict:
+        """The reference's second protocol (python_scripts/evaluation/evaluate_sed_eval.py -> eval_util.compute_sed_eval)
+        with the arithmetic on the device (device_eval.SedEvaluator): event-based and segment-based precision, recall, F and
+        error rate per operating point.  ``batches`` and ``ground_truth`` as for ``evaluate``, the same key rule, and a pair
+        without a ground-truth row is left out (the reference evaluates the files of the ground-truth table).  eval_config:
+        ``time_resolution``, and either ``double_thresholds`` ((high, low) pairs) or ``thresholds`` / ``n_thresholds`` (50) with
+        ``window_size`` (1); optionally ``t_collar`` (0.2), ``percentage_of_length`` (0.2), ``segment_resolution`` (1.0),
+        ``n_connect``.  One host read at the end.  Returns SedEvaluator.compute's dict; counts of this rank's batches only."""
+        double = eval_config.get("double_thresholds")
+        single = None
+        if double is None:
+            single = eval_config.get("thresholds")
+            if single is None:
+                single = eval_util.eval_thresholds(int(eval_config.get("n_thresholds", 50)))
+        ev = device_eval.SedEvaluator(thresholds=single, double_thresholds=double, window_size=int(eval_config.get("window_size", 1)),
+                                      time_resolution=float(eval_config["time_resolution"]),
+                                      t_collar=eval_config.get("t_collar", 0.2),
+                                      percentage_of_length=eval_config.get("percentage_of_length", 0.2),
+                                      segment_resolution=eval_config.get("segment_resolution", 1.0),
+                                      n_connect=eval_config.get("n_connect"), device=self.device)
+        self._update_over_batches(ev, batches, ground_truth)
+        result = ev.compute()
         ops.check_async_errors()
         return result
 

@@ -6,6 +6,10 @@ is the host path: it copies every segment of every (clip, threshold) pair to the
 Here ``ops.segments`` and ``ops.grounding_counts`` (csrc/grounding_eval.hip) leave four integers per pair on the device, a batch
 adds them into ONE (NT, 6) int64 tensor, and ``compute`` reads that tensor once.  The host functions of grounding_eval.py stay
 the yardstick: the counts are theirs exactly, so precision, recall, th-AUC and PSDS are equal as floats.
+
+``SedEvaluator`` does the same for the reference's second protocol (python_scripts/evaluation/evaluate_sed_eval.py ->
+utils/eval_util.py:354-425 compute_sed_eval): ``ops.segments`` or the double threshold ``ops.segments_double``, then
+``ops.sed_counts`` (csrc/sed_eval.hip), whose yardstick is utils/sed_metrics.py.
 """
 from __future__ import annotations
 
@@ -105,3 +109,89 @@ class GroundingEvaluator:
         return {"th_auc": ev.th_auc(beta=beta, low_th=min_threshold, high_th=max_threshold), "psds": psds,
                 "precision": np.array([r["precision"] for r in ev.operating_points]),
                 "recall": np.array([r["recall"] for r in ev.operating_points]), "thresholds": self.thresholds.copy()}
+
+
+class SedEvaluator:
+    """Accumulates the sed_eval protocol (event-based and segment-based F-score / error rate, utils/sed_metrics.py) over
+    batches on the device, for a row of operating points.
+
+    Exactly one of ``thresholds`` (strictly ascending; binarize -> median filter of ``window_size`` -> connect, ``ops.segments``)
+    and ``double_thresholds`` (a sequence of ``(high, low)`` pairs, high >= low; ``ops.segments_double``, which takes no median
+    filter: ``window_size`` is not used) says how frame scores become detections.  ``n_connect`` defaults to
+    ``eval_util.n_connect_for(time_resolution)``.
+
+    ``counts`` is an (NT, 7) int64 device tensor: ev_tp, seg_tp, seg_fp, seg_fn, seg_n, n_sys, n_ref per operating point,
+    summed over every pair passed to ``update`` (a data-parallel caller all-reduces it, and ``overflow``, before ``compute``).
+    A pair is one file of the host tables, so the sums are ``sed_metrics.count_tables`` of a table that holds every pair once.
+    """
+
+    def __init__(self, thresholds=None, double_thresholds=None, window_size: int = 1, time_resolution: float = None,
+                 t_collar: float = 0.2, percentage_of_length: float = 0.2, segment_resolution: float = 1.0, n_connect=None,
+                 device="cuda"):
+        if (thresholds is None) == (double_thresholds is None):
+            raise ValueError("SedEvaluator: give exactly one of thresholds and double_thresholds")
+        if time_resolution is None or not time_resolution > 0:
+            raise ValueError("SedEvaluator: time_resolution (seconds per frame) must be given and positive")
+        if not segment_resolution > 0 or not t_collar >= 0 or not percentage_of_length >= 0:
+            raise ValueError("SedEvaluator: segment_resolution must be positive, t_collar and percentage_of_length not negative")
+        self.device = torch.device(device)
+        if thresholds is not None:
+            th = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+            if th.size == 0 or not np.all(np.diff(th) > 0):
+                raise ValueError("SedEvaluator: thresholds must be strictly ascending (and not empty)")
+            self.thresholds, self.double_thresholds = th, None
+            self._th = torch.as_tensor(th).to(self.device)
+        else:
+            pairs = np.asarray(double_thresholds, dtype=np.float64)
+            if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0 or not np.all(pairs[:, 0] >= pairs[:, 1]):
+                raise ValueError("SedEvaluator: double_thresholds must be (high, low) pairs with high >= low (and not empty)")
+            self.thresholds, self.double_thresholds = None, pairs
+            self._high = torch.as_tensor(np.ascontiguousarray(pairs[:, 0])).to(self.device)
+            self._low = torch.as_tensor(np.ascontiguousarray(pairs[:, 1])).to(self.device)
+        self.window_size, self.time_resolution = int(window_size), float(time_resolution)
+        self.n_connect = eval_util.n_connect_for(self.time_resolution) if n_connect is None else int(n_connect)
+        self.t_collar, self.percentage_of_length = float(t_collar), float(percentage_of_length)
+        self.segment_resolution = float(segment_resolution)
+        n_points = len(self.thresholds if self.thresholds is not None else self.double_thresholds)
+        self.counts = torch.zeros(n_points, 7, device=self.device, dtype=torch.int64)
+        self.overflow = torch.zeros((), device=self.device, dtype=torch.int64)     # pairs above ops.SED_MAX_SEGMENTS segments
+
+    def reset(self):
+        self.counts.zero_()
+        self.overflow.zero_()
+
+    def update(self, frame_sim: torch.Tensor, gt, gt_count):
+        """frame_sim (B, T) float32 on the device; gt, gt_count as ``ground_truth_arrays`` returns them (host arrays are
+        checked here and copied over; device tensors are taken as they are).  No host read."""
+        gt, gt_count = torch.as_tensor(gt), torch.as_tensor(gt_count)
+        if not gt_count.is_cuda and gt_count.numel() and (int(gt_count.min()) < 0 or int(gt_count.max()) > gt.shape[1]):
+            raise ValueError(f"gt_count must lie in [0, {gt.shape[1]}]")
+        gt_count = gt_count.to(self.device)
+        if self.thresholds is not None:
+            regions, counts = ops.segments(frame_sim, self._th, self.window_size, self.n_connect)
+        else:
+            regions, counts = ops.segments_double(frame_sim, self._high, self._low, self.n_connect)
+        out = ops.sed_counts(regions, counts, gt, gt_count, self.time_resolution, self.t_collar, self.percentage_of_length,
+                             self.segment_resolution, check=False)
+        self.overflow += (out[..., 4] < 0).sum()
+        self.counts[:, :5] += out.sum(0)
+        self.counts[:, 5] += counts.sum(0)
+        self.counts[:, 6] += gt_count.sum()
+
+    def compute(self) -> dict:
+        """ONE host read of ``counts`` (and ``overflow``) -> ``sed_metrics.scores_from_counts`` with one entry per operating
+        point: {"event": {...}, "segment": {...}, "counts" (NT, 7) int64, "thresholds" or "double_thresholds"}."""
+        from . import sed_metrics
+        flat = torch.cat([self.counts.reshape(-1), self.overflow.reshape(1)]).cpu().numpy()
+        if flat[-1] != 0:
+            raise RuntimeError(f"SedEvaluator: segment_resolution = {self.segment_resolution} cut {int(flat[-1])} (pair, operating "
+                               f"point) entries into more than {ops.SED_MAX_SEGMENTS} segments; their counts were not taken")
+        counts = flat[:-1].reshape(-1, 7)
+        ev_tp, seg_tp, seg_fp, seg_fn, seg_n, n_sys, n_ref = counts.T
+        out = sed_metrics.scores_from_counts(ev_tp, n_sys, n_ref, seg_tp, seg_fp, seg_fn, seg_n)
+        out["counts"] = counts
+        if self.thresholds is not None:
+            out["thresholds"] = self.thresholds.copy()
+        else:
+            out["double_thresholds"] = self.double_thresholds.copy()
+        return out
