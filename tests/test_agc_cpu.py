@@ -172,7 +172,10 @@ def test_build_plumbing():
     assert re.search(r"^SRCS = .*\bagc\.hip\b", makefile, flags=re.M)
     for s in SYMBOLS:
         assert s in lib.declared_symbols() and re.search(rf"\b{s}\s*\(", header), s
-    src = open(os.path.join(ROOT, "texttoaudiogrounding_amd", "csrc", "agc.hip")).read()
-    code = re.sub(r"//[^\n]*", "", src)
-    assert "atomic" not in code and "cooperative" not in code.lower()
-    assert "__builtin_amdgcn_mfma_f32_32x32x2f32" in code
+    csrc = os.path.join(ROOT, "texttoaudiogrounding_amd", "csrc")
+    # agc.hip's products are the shared exact-fp32 MFMA march of march_f32.h: both files are held to the same rules
+    code, march = (re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read()) for f in ("agc.hip", "march_f32.h"))
+    assert "atomic" not in code + march and "cooperative" not in (code + march).lower()
+    assert '#include "march_f32.h"' in code and re.search(r"\bmarch_tiles<", code)
+    assert "__builtin_amdgcn_mfma_f32_32x32x2f32" in march
+    assert re.search(r"^HDRS = .*\bmarch_f32\.h\b", makefile, flags=re.M)

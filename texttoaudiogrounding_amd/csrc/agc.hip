@@ -10,14 +10,13 @@
 // sum buffers, one (N, D) fp32 mean buffer, O(N) vectors and the workspace below, about 20 N D + 64 N bytes; no (N, N) array.
 //
 // tag_agc_nearest:  nn[i] = the j != i with the largest m_i . m_j, ties to the lowest j, dist[i] = 1 - m_i . m_nn[i].  The products
-//   are the marching kernel of phrase_sim.hip / kmeans.hip (its loop is COPIED here, not shared: the three epilogues differ and the
-//   other files stay as they are): a workgroup owns 128 rows and one SLICE of the 128-column tiles of the same matrix and walks
-//   the slice on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32, operands not rounded, the D tail zero-filled).  When a tile's K loop
+//   are the marching kernel of march_f32.h with A = B = m: a workgroup owns 128 rows and one SLICE of the 128-column tiles of the
+//   same matrix and walks the slice on the exact-fp32 MFMA (operands not rounded, the D tail zero-filled).  When a tile's K loop
 //   ends each lane keeps a running (score, index) pair per row it holds; the diagonal and the columns >= M score -inf.  A lane
 //   meets its columns in ascending order and replaces on > only; at the end of the slice the 64 lanes that share a row fold
 //   through LDS on (score, index) and the row's pair goes to ws[slice][row]; a second launch folds the slices in slice order on
 //   (score, index) and writes nn and dist.  M shrinks from N towards 1 during a fit, so the slice count comes from M alone
-//   (phrase_sim.hip's plan with N = M): few row blocks are cut into many slices and still fill the device.
+//   (the plan with the columns = the rows): few row blocks are cut into many slices and still fill the device.
 //   The scores are BIT-SYMMETRIC, score(i, j) == score(j, i): both are the same chain of k-steps in the same order (k-step e of
 //   a group multiplies the same k in both operands, a product a * b is commutative, and nothing else scales a score).  The fit
 //   loop's progress argument needs it: the lowest row that attains the round's largest score and its nn name each other.
@@ -30,102 +29,34 @@
 //   (float)(sum / size) for EVERY output row, and the merge log row (dist[a], id_a, id_b, new id) at log_off + rank.
 //
 // No atomics, no cooperative launch, no device-side waiting; ws is never zeroed; the same bits on every run.
-#include "tag_common.h"
-#include <limits.h>
+#include "march_f32.h"
 #include <math.h>
 
 namespace {
 
+using namespace march;
+
 // ------------------------------------------------------------------------------------------------------------------------
 // nearest
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int T = 128;            // rows per workgroup, columns per tile
-constexpr int KC = 32;            // K chunk per barrier
-constexpr int LD = KC + 4;        // LDS row stride (144-byte rows: conflict-free b128 reads, as gemm.hip)
-constexpr int SZ = T * LD;        // floats per stage buffer
-constexpr int NL = T * KC / 1024; // float4 per thread, operand and chunk
-constexpr int RQ = KC / 4;        // float4 per row of a chunk
-constexpr int RED_LD = 65;        // row stride of the end-of-slice fold (64 candidates per row + 1 pad)
-constexpr size_t LDS_BYTES = (size_t)4 * SZ * sizeof(float);
+constexpr size_t LDS_BYTES = STAGE_BYTES;
 static_assert((size_t)2 * T * RED_LD * sizeof(float) <= LDS_BYTES, "the fold reuses the stage buffers");
 constexpr int NONE = INT_MAX;     // index of "no candidate yet": loses every tie
 
-// Column slices: phrase_sim.hip's plan with the bank = the rows themselves.  ws = slices x M x (float + int).
-constexpr int FILL_WGS = 512;
-constexpr int SLICES_MIN = 8;
-constexpr int GROUP = 8;          // row blocks that run side by side over the same slices
-struct Plan { int tiles, group, slices, tiles_each; long blocks; };
-Plan make_plan(int M) {
-    Plan p;
-    p.tiles = cdiv(M, T);
-    p.group = p.tiles < GROUP ? p.tiles : GROUP;
-    int want = cdiv(FILL_WGS, p.tiles);
-    if (want < SLICES_MIN) want = SLICES_MIN;
-    if (want > p.tiles) want = p.tiles;
-    p.tiles_each = cdiv(p.tiles, want);
-    p.slices = cdiv(p.tiles, p.tiles_each);
-    p.blocks = (long)cdiv(p.tiles, p.group) * p.group * p.slices;
-    return p;
-}
-
-// FAST: whole tiles, whole K chunks and 16-byte aligned rows (checked by the launcher): plain float4 loads, no tail tests
-template <bool FAST>
-__device__ __forceinline__ void load_rows(f32x4 (&reg)[NL], const float* __restrict__ base, int ld, int r0, int rmax, int k0, int D,
-                                          bool al) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        const int idx = threadIdx.x + 256 * i;
-        const int r = r0 + idx / RQ, k = k0 + (idx % RQ) * 4;
-        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (FAST) {
-            v = *reinterpret_cast<const f32x4*>(base + (size_t)r * ld + k);
-        } else if (r < rmax) {
-            const float* p = base + (size_t)r * ld + k;
-            const int n = D - k;
-            if (n >= 4 && al) {
-                v = *reinterpret_cast<const f32x4*>(p);
-            } else {
-                if (n > 0) v.x = p[0];
-                if (n > 1) v.y = p[1];
-                if (n > 2) v.z = p[2];
-                if (n > 3) v.w = p[3];
-            }
-        }
-        reg[i] = v;
-    }
-}
-
-__device__ __forceinline__ void store_rows(float* s, const f32x4 (&reg)[NL]) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        const int idx = threadIdx.x + 256 * i;
-        *reinterpret_cast<f32x4*>(s + (idx / RQ) * LD + (idx % RQ) * 4) = reg[i];
-    }
-}
+// Column slices: the plan of march_f32.h with the columns = the rows themselves.  ws = slices x M x (float + int).
+Plan plan_of(int M) { return make_plan(cdiv(M, T), cdiv(M, T)); }
 
 template <bool FAST>
 __global__ __launch_bounds__(256, 2) void agc_nearest_kernel(const float* __restrict__ m, int ldm, float* __restrict__ ws_score,
                                                              int* __restrict__ ws_idx, int M, int D, int tiles, int group,
                                                              int slices, int tiles_each, bool al) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;             // [2][SZ]
-    float* Bs = smem + 2 * SZ;    // [2][SZ]
-    // logical order (row group, slice, row block of the group), an XCD taking a contiguous run of it
-    const int L = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x));
-    const int mt = (L / (group * slices)) * group + L % group;
-    const int slice = (L / group) % slices;
-    if (mt >= tiles) return;      // (the last group of row blocks may be short; the whole workgroup leaves)
-    const int m0 = mt * T;
-    const int t_lo = slice * tiles_each;
-    const int t_hi = t_lo + tiles_each < tiles ? t_lo + tiles_each : tiles;
-    const int kiters = (D + KC - 1) / KC;
-    const int total = (t_hi - t_lo) * kiters;
+    const Share sh = plan_share(tiles, group, slices, tiles_each);
+    if (sh.mt >= tiles) return;
+    const int m0 = sh.mt * T, slice = sh.slice;
+    const Lanes l = lanes();
+    const int row0 = m0 + l.wm0 + 4 * l.kl;       // register r of acc[i][.] is row row0 + acc_row(i, r)
 
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wm0 = (wid >> 1) * 64, wn0 = (wid & 1) * 64;
-    const int kl = lane >> 5, ml = lane & 31;
-
-    f32x16 acc[2][2];
     float best[2][16];
     int bidx[2][16];
 #pragma unroll
@@ -134,84 +65,28 @@ __global__ __launch_bounds__(256, 2) void agc_nearest_kernel(const float* __rest
         for (int r = 0; r < 16; ++r) {
             best[i][r] = -INFINITY;
             bidx[i][r] = NONE;
-            acc[i][0][r] = 0.0f;
-            acc[i][1][r] = 0.0f;
         }
 
-    f32x4 ra[NL], rb[NL];
-    int ld_tile = t_lo, ld_k = 0;         // the chunk the next load requests
-    auto load_next = [&]() {
-        load_rows<FAST>(ra, m, ldm, m0, M, ld_k * KC, D, al);
-        load_rows<FAST>(rb, m, ldm, ld_tile * T, M, ld_k * KC, D, al);
-        if (++ld_k == kiters) { ld_k = 0; ++ld_tile; }
-    };
-    load_next();
-    store_rows(As, ra);
-    store_rows(Bs, rb);
-    __syncthreads();
-
-    int tile = t_lo, kc = 0;
-    for (int it = 0; it < total; ++it) {
-        const int buf = it & 1;
-        if (it + 1 < total) load_next();
-        __builtin_amdgcn_sched_barrier(0);
-        const float* a = As + buf * SZ + (wm0 + ml) * LD + kl * 4;
-        const float* b = Bs + buf * SZ + (wn0 + ml) * LD + kl * 4;
-        f32x4 af[2][2], bf[2][2];
+    // This lane meets its columns in ascending order (tile, then j) and replaces on > only; a column past M (zero-filled: score 0,
+    // above every negative real score) and the diagonal never win.
+    march_tiles<FAST, FAST>(smem, Rows{m, ldm, M, al}, Rows{m, ldm, M, al}, m0, sh.t_lo, sh.t_hi, D,
+                            [&](int tile, const f32x16 (&acc)[2][2]) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            af[0][i] = *reinterpret_cast<const f32x4*>(a + i * 32 * LD);
-            bf[0][i] = *reinterpret_cast<const f32x4*>(b + i * 32 * LD);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+        for (int j = 0; j < 2; ++j) {
+            const int n = tile * T + l.wn0 + j * 32 + l.ml;
+            const bool real = n < M;
 #pragma unroll
-        for (int g = 0; g < KC / 8; ++g) {
-            if (g + 1 < KC / 8) {
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    af[(g + 1) & 1][i] = *reinterpret_cast<const f32x4*>(a + i * 32 * LD + 8 * (g + 1));
-                    bf[(g + 1) & 1][i] = *reinterpret_cast<const f32x4*>(b + i * 32 * LD + 8 * (g + 1));
+                for (int r = 0; r < 16; ++r) {
+                    const int row = row0 + acc_row(i, r);
+                    const float s = acc[i][j][r];
+                    const bool take = real && n != row && s > best[i][r];
+                    best[i][r] = take ? s : best[i][r];
+                    bidx[i][r] = take ? n : bidx[i][r];
                 }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g & 1][i][e], bf[g & 1][j][e], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
         }
-        if (it + 1 < total) {
-            store_rows(As + (buf ^ 1) * SZ, ra);
-            store_rows(Bs + (buf ^ 1) * SZ, rb);
-        }
-        if (++kc == kiters) {
-            // the tile's products are complete: register r of acc[i][j] is row m0 + wm0 + 32 i + (r & 3) + 8 (r >> 2) + 4 kl, column
-            // tile * T + wn0 + 32 j + ml.  This lane meets its columns in ascending order (tile, then j) and replaces on > only; a
-            // column past M (zero-filled: score 0, above every negative real score) and the diagonal never win.
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int n = tile * T + wn0 + j * 32 + ml;
-                const bool real = n < M;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl;
-                        const float s = acc[i][j][r];
-                        if (real && n != row && s > best[i][r]) {
-                            best[i][r] = s;
-                            bidx[i][r] = n;
-                        }
-                        acc[i][j][r] = 0.0f;
-                    }
-            }
-            kc = 0;
-            ++tile;
-        }
-        __syncthreads();
-    }
+    });
 
     // fold the 64 lanes (2 waves x 32 columns) that share a row on (score, index); the stage buffers are free after the last barrier
     float* rs = smem;
@@ -220,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void agc_nearest_kernel(const float* __rest
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = (wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl) * RED_LD + (wid & 1) * 32 + ml;
+            const int o = fold_slot(l, i, r);
             rs[o] = best[i][r];
             ri[o] = bidx[i][r];
         }
@@ -265,9 +140,7 @@ __global__ void agc_single_kernel(int* __restrict__ nn, float* __restrict__ dist
     dist[0] = INFINITY;
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
-bool shape_ok(int M, int D) { return M >= 1 && D >= 1 && M <= INT_MAX - T && D <= INT_MAX - KC && make_plan(M).blocks <= INT_MAX; }
+bool shape_ok(int M, int D) { return M >= 1 && D >= 1 && M <= INT_MAX - T && D <= INT_MAX - KC && plan_of(M).blocks <= INT_MAX; }
 
 // tile origins (M + 127) and the chunk origin (D + 31) are ints; the grid is one-dimensional
 int check_shape(const char* fn, int M, int D) {
@@ -275,18 +148,12 @@ int check_shape(const char* fn, int M, int D) {
         tag_set_error("%s: M, D must be >= 1 (got %d, %d)", fn, M, D);
         return TAG_EINVAL;
     }
-    if (M > INT_MAX - T) {
-        tag_set_error("%s: M = %d exceeds %d (row index limit)", fn, M, INT_MAX - T);
-        return TAG_EINVAL;
-    }
-    if (D > INT_MAX - KC) {
-        tag_set_error("%s: D = %d exceeds %d (chunk index limit)", fn, D, INT_MAX - KC);
-        return TAG_EINVAL;
-    }
-    const Plan p = make_plan(M);
+    if (int rc = check_index_limit(fn, "M", M, T, "row")) return rc;
+    if (int rc = check_index_limit(fn, "D", D, KC, "chunk")) return rc;
+    const Plan p = plan_of(M);
     if (p.blocks > INT_MAX) {
         tag_set_error("%s: M = %d needs %ld workgroups (%d row blocks x %d slices), more than the grid limit %d", fn, M, p.blocks,
-                      p.tiles, p.slices, INT_MAX);
+                      p.m_tiles, p.slices, INT_MAX);
         return TAG_EINVAL;
     }
     return 0;
@@ -301,7 +168,7 @@ void launch_nearest(const float* m, int ldm, float* ws_score, int* ws_idx, int M
         attr_set = true;
     }
     hipLaunchKernelGGL(agc_nearest_kernel<FAST>, dim3((unsigned)p.blocks), dim3(256), LDS_BYTES, st, m, ldm, ws_score, ws_idx, M, D,
-                       p.tiles, p.group, p.slices, p.tiles_each, al);
+                       p.m_tiles, p.group, p.slices, p.tiles_each, al);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -424,7 +291,7 @@ __global__ __launch_bounds__(256) void agc_gather_kernel(const int* __restrict__
 
 extern "C" size_t tag_agc_nearest_ws_bytes(int M, int D) {
     if (!shape_ok(M, D)) return 0;
-    return (size_t)make_plan(M).slices * M * (sizeof(float) + sizeof(int));
+    return (size_t)plan_of(M).slices * M * (sizeof(float) + sizeof(int));
 }
 
 extern "C" int tag_agc_nearest(const float* m, int ldm, int* nn, float* dist, int M, int D, void* ws, void* stream) {
@@ -440,7 +307,7 @@ extern "C" int tag_agc_nearest(const float* m, int ldm, int* nn, float* dist, in
         TAG_LAUNCH_CHECK();
         return 0;
     }
-    const Plan p = make_plan(M);
+    const Plan p = plan_of(M);
     float* ws_score = static_cast<float*>(ws);
     int* ws_idx = reinterpret_cast<int*>(ws_score + (size_t)p.slices * M);
     const bool al = aligned16(m) && ldm % 4 == 0;

@@ -253,8 +253,6 @@ void launch_pairsum(const float* g, const float* x, const float* y, float* dx, f
     }
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 // index limits shared by the launchers: row counts and the (M, P) / (B,B,T,N) element count as used by the kernels
 int check_shape(const char* what, int B, int T, int N, int D) {
     if (B < 1 || T < 1 || N < 1 || D < 1) {

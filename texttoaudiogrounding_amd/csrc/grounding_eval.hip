@@ -110,12 +110,6 @@ __device__ __forceinline__ Pair pair_ratios(double on_d, double off_d, double on
     return p;
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 constexpr unsigned char F_DTC = 1, F_RELEVANT = 2;
 
 __global__ __launch_bounds__(64) void grounding_counts_kernel(const long long* __restrict__ regions, const int* __restrict__ counts,

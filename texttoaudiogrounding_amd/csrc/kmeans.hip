@@ -2,9 +2,8 @@
 // the host; utils/phrase_cluster.py drives these three entry points).
 //
 // tag_kmeans_assign:  label[i] = argmin_k (||c_k||^2 - 2 x_i . c_k), ties to the lowest k, and dist2[i] = sum_d (x_id - c_label,d)^2.
-//   The products are phrase_sim.hip's marching kernel: a workgroup owns 128 rows of x and walks ALL 128-column tiles of the
-//   centres on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32, the same row-major LDS image, the K chunks of all tiles one
-//   double-buffered sequence).  When a tile's K loop ends each lane turns its 64 accumulator values into scores and keeps a
+//   The products are the marching kernel of march_f32.h: a workgroup owns 128 rows of x and walks ALL 128-column tiles of the
+//   centres on the exact-fp32 MFMA.  When a tile's K loop ends each lane turns its 64 accumulator values into scores and keeps a
 //   running (score, index) pair per row it holds (32 rows); a column past K scores +inf (a zero-filled centre would score 0 and
 //   beat every positive real score).  A lane sees its columns in ascending order and replaces on < only; at the end the 64 lanes
 //   that share a row fold through LDS on (score, index), so the lowest k wins a tie.  Identical centre rows give bit-identical
@@ -22,77 +21,27 @@
 //
 // tag_kmeans_seed_step:  closest[i] = min(closest[i], ||x_i - x_p||^2) with p read from a device int64 (k-means++ without a host
 //   round trip); first != 0 writes the distance without the min.  Row-wise fp32 differences, one wave per row.
-#include "tag_common.h"
-#include <limits.h>
+#include "march_f32.h"
 #include <math.h>
 
 namespace {
 
+using namespace march;
+
 // ------------------------------------------------------------------------------------------------------------------------
 // assignment
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int T = 128;            // rows of x per workgroup, centres per tile
-constexpr int KC = 32;            // K chunk per barrier
-constexpr int LD = KC + 4;        // LDS row stride (144-byte rows: conflict-free b128 reads, as gemm.hip)
-constexpr int SZ = T * LD;        // floats per stage buffer
-constexpr int NL = T * KC / 1024; // float4 per thread, operand and chunk
-constexpr int RQ = KC / 4;        // float4 per row of a chunk
-constexpr int RED_LD = 65;        // row stride of the end-of-march fold (64 candidates per row + 1 pad)
-constexpr size_t LDS_BYTES = (size_t)4 * SZ * sizeof(float);
+constexpr size_t LDS_BYTES = STAGE_BYTES;
 static_assert((size_t)2 * T * RED_LD * sizeof(float) <= LDS_BYTES, "the fold reuses the stage buffers");
-
-// FAST: whole tiles, whole K chunks and 16-byte aligned rows (checked by the launcher, per operand): plain float4 loads
-template <bool FAST>
-__device__ __forceinline__ void load_rows(f32x4 (&reg)[NL], const float* __restrict__ base, int ld, int r0, int rmax, int k0, int D,
-                                          bool al) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        const int idx = threadIdx.x + 256 * i;
-        const int r = r0 + idx / RQ, k = k0 + (idx % RQ) * 4;
-        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (FAST) {
-            v = *reinterpret_cast<const f32x4*>(base + (size_t)r * ld + k);
-        } else if (r < rmax) {
-            const float* p = base + (size_t)r * ld + k;
-            const int n = D - k;
-            if (n >= 4 && al) {
-                v = *reinterpret_cast<const f32x4*>(p);
-            } else {
-                if (n > 0) v.x = p[0];
-                if (n > 1) v.y = p[1];
-                if (n > 2) v.z = p[2];
-                if (n > 3) v.w = p[3];
-            }
-        }
-        reg[i] = v;
-    }
-}
-
-__device__ __forceinline__ void store_rows(float* s, const f32x4 (&reg)[NL]) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        const int idx = threadIdx.x + 256 * i;
-        *reinterpret_cast<f32x4*>(s + (idx / RQ) * LD + (idx % RQ) * 4) = reg[i];
-    }
-}
 
 template <bool FX, bool FC>
 __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ c,
                                                                int ldc, const float* __restrict__ cnorm, int* __restrict__ label,
                                                                int N, int K, int D, bool x_al, bool c_al) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;             // [2][SZ]
-    float* Bs = smem + 2 * SZ;    // [2][SZ]
     const int m0 = blockIdx.x * T;
-    const int n_tiles = (K + T - 1) / T;
-    const int kiters = (D + KC - 1) / KC;
-    const int total = n_tiles * kiters;
+    const Lanes l = lanes();
 
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wm0 = (wid >> 1) * 64, wn0 = (wid & 1) * 64;
-    const int kl = lane >> 5, ml = lane & 31;
-
-    f32x16 acc[2][2];
     float best[2][16];
     int bidx[2][16];
 #pragma unroll
@@ -101,83 +50,27 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const float* __re
         for (int r = 0; r < 16; ++r) {
             best[i][r] = INFINITY;
             bidx[i][r] = 0;
-            acc[i][0][r] = 0.0f;
-            acc[i][1][r] = 0.0f;
         }
 
-    f32x4 ra[NL], rb[NL];
-    int ld_tile = 0, ld_k = 0;            // the chunk the next load requests
-    auto load_next = [&]() {
-        load_rows<FX>(ra, x, ldx, m0, N, ld_k * KC, D, x_al);
-        load_rows<FC>(rb, c, ldc, ld_tile * T, K, ld_k * KC, D, c_al);
-        if (++ld_k == kiters) { ld_k = 0; ++ld_tile; }
-    };
-    load_next();
-    store_rows(As, ra);
-    store_rows(Bs, rb);
-    __syncthreads();
-
-    int tile = 0, kc = 0;
-    for (int it = 0; it < total; ++it) {
-        const int buf = it & 1;
-        if (it + 1 < total) load_next();
-        __builtin_amdgcn_sched_barrier(0);
-        const float* a = As + buf * SZ + (wm0 + ml) * LD + kl * 4;
-        const float* b = Bs + buf * SZ + (wn0 + ml) * LD + kl * 4;
-        f32x4 af[2][2], bf[2][2];
+    // This lane meets its columns in ascending order (tile, then j) and replaces on < only.
+    march_tiles<FX, FC>(smem, Rows{x, ldx, N, x_al}, Rows{c, ldc, K, c_al}, m0, 0, (K + T - 1) / T, D,
+                        [&](int tile, const f32x16 (&acc)[2][2]) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            af[0][i] = *reinterpret_cast<const f32x4*>(a + i * 32 * LD);
-            bf[0][i] = *reinterpret_cast<const f32x4*>(b + i * 32 * LD);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+        for (int j = 0; j < 2; ++j) {
+            const int n = tile * T + l.wn0 + j * 32 + l.ml;
+            const bool real = n < K;
+            const float cn = real ? cnorm[n] : 0.0f;
 #pragma unroll
-        for (int g = 0; g < KC / 8; ++g) {
-            if (g + 1 < KC / 8) {
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    af[(g + 1) & 1][i] = *reinterpret_cast<const f32x4*>(a + i * 32 * LD + 8 * (g + 1));
-                    bf[(g + 1) & 1][i] = *reinterpret_cast<const f32x4*>(b + i * 32 * LD + 8 * (g + 1));
+                for (int r = 0; r < 16; ++r) {
+                    const float s = real ? cn - 2.0f * acc[i][j][r] : INFINITY;
+                    const bool take = s < best[i][r];
+                    best[i][r] = take ? s : best[i][r];
+                    bidx[i][r] = take ? n : bidx[i][r];
                 }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g & 1][i][e], bf[g & 1][j][e], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
         }
-        if (it + 1 < total) {
-            store_rows(As + (buf ^ 1) * SZ, ra);
-            store_rows(Bs + (buf ^ 1) * SZ, rb);
-        }
-        if (++kc == kiters) {
-            // the tile's products are complete: register r of acc[i][j] is row wm0 + 32 i + (r & 3) + 8 (r >> 2) + 4 kl, column
-            // wn0 + 32 j + ml.  This lane meets its columns in ascending order (tile, then j) and replaces on < only.
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int n = tile * T + wn0 + j * 32 + ml;
-                const bool real = n < K;
-                const float cn = real ? cnorm[n] : 0.0f;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float s = real ? cn - 2.0f * acc[i][j][r] : INFINITY;
-                        if (s < best[i][r]) {
-                            best[i][r] = s;
-                            bidx[i][r] = n;
-                        }
-                        acc[i][j][r] = 0.0f;
-                    }
-            }
-            kc = 0;
-            ++tile;
-        }
-        __syncthreads();
-    }
+    });
 
     // fold the 64 lanes (2 waves x 32 columns) that share a row on (score, index); the stage buffers are free after the last barrier
     float* rs = smem;
@@ -186,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const float* __re
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = (wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl) * RED_LD + (wid & 1) * 32 + ml;
+            const int o = fold_slot(l, i, r);
             rs[o] = best[i][r];
             ri[o] = bidx[i][r];
         }
@@ -392,7 +285,6 @@ __global__ __launch_bounds__(256) void kmeans_update_fold_kernel(const float* __
     }
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 // row and tile origins (N + 127, K + 127, D + 31) are ints; the assign grid is one-dimensional, the update grid's y and z are
 // cluster groups (<= 65535) and slices (<= UPD_WGS)
@@ -402,18 +294,12 @@ int check_shape(const char* fn, int N, int K, int D) {
         tag_set_error("%s: N, K, D must be >= 1 (got %d, %d, %d)", fn, N, K, D);
         return TAG_EINVAL;
     }
-    if (N > INT_MAX - T) {
-        tag_set_error("%s: N = %d exceeds %d (row index limit)", fn, N, INT_MAX - T);
-        return TAG_EINVAL;
-    }
+    if (int rc = check_index_limit(fn, "N", N, T, "row")) return rc;
     if (K > K_MAX) {
         tag_set_error("%s: K = %d exceeds %d (cluster group limit of the launch grid)", fn, K, K_MAX);
         return TAG_EINVAL;
     }
-    if (D > INT_MAX - KC) {
-        tag_set_error("%s: D = %d exceeds %d (chunk index limit)", fn, D, INT_MAX - KC);
-        return TAG_EINVAL;
-    }
+    if (int rc = check_index_limit(fn, "D", D, KC, "chunk")) return rc;
     return 0;
 }
 

@@ -2,77 +2,31 @@
 // which calls sklearn's cosine_similarity(phrase, label_embs) on the host per item; utils/label_map.py drives these entry points).
 //
 // tag_label_map:  s[i][c] = x_i . e_c / (||x_i|| ||e_c||), a zero row's norm taken as 1 (its similarities are exactly 0).  The
-//   products are kmeans.hip's marching kernel: a workgroup owns 128 rows of x and walks ALL 128-column tiles of the labels on the
-//   exact-fp32 MFMA (v_mfma_f32_32x32x2_f32, operands not rounded, the same row-major LDS image, the K chunks of all tiles one
-//   double-buffered sequence).  A first small launch leaves 1 / ||row|| of both operands in ws (N + C floats; the sum of squares in
-//   fp64, so the factor carries one rounding).  When a tile's K loop ends each lane turns its 64 accumulator values into
-//   s = (acc * rx[row]) * re[column], the ONLY value every output is made of:
+//   products are the marching kernel of march_f32.h: a workgroup owns 128 rows of x and walks ALL 128-column tiles of the labels on
+//   the exact-fp32 MFMA (operands not rounded).  A first small launch leaves 1 / ||row|| of both operands in ws (N + C floats; the
+//   sum of squares in fp64, so the factor carries one rounding).  When a tile's K loop ends each lane turns its 64 accumulator
+//   values into s = (acc * rx[row]) * re[column], the ONLY value every output is made of:
 //     - sim (optional) gets s with plain 4-byte vector stores, columns past C and rows past N never;
 //     - a running (max, index) pair, a running minimum and a running (max, index) pair over the window members
 //       (th0 <= s <= th1 && s != 0) per row the lane holds (32 rows).  A lane meets its columns in ascending order and replaces on
 //       > only; at the end the 64 lanes that share a row fold through LDS on (value, index), so the lowest c wins a tie.
 //       Identical label rows give bit-identical s in any column (the same chain of k-steps, the same norm kernel), so that rule is
 //       exact;
-//     - ONE 64-bit ballot of the window predicate per accumulator register is two finished words of win_bits (dbscan.hip's
-//       epilogue): register r of acc[i][j] holds row wm0 + 32 i + (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column wn0 + 32 j +
-//       (lane & 31).  The ballot is ANDed with the ballot of (column < C), its halves go into lane (row - wm0) of a register
-//       (v_writelane_b32), and after the 64 ballots lane l holds the two words of row wm0 + l: it stores those below
-//       ceil(C / 32) and adds their popcounts to the row's window size.
+//     - ONE 64-bit ballot of the window predicate per accumulator register is two finished words of win_bits (ballot_to_words,
+//       as dbscan.hip's epilogue).  The ballot is ANDed with the ballot of (column < C), and after the 64 ballots lane l holds
+//       the two words of row wm0 + l: it stores those below ceil(C / 32) and adds their popcounts to the row's window size.
 //   No atomics, ws is never zeroed, the same bits on every run, and nothing but the stores of sim depends on whether sim exists.
 //
 // tag_label_map_topk:  one wave per row of sim: k rounds of a wave argmax over the window members that follow the last pick in
 //   the order (s descending, c ascending); the picks go to idx (N, k), -1 once the window is exhausted.  Round one is win_best.
-#include "tag_common.h"
-#include <limits.h>
+#include "march_f32.h"
 #include <math.h>
 
 namespace {
 
-constexpr int T = 128;            // rows of x per workgroup, labels per tile
-constexpr int KC = 32;            // K chunk per barrier
-constexpr int LD = KC + 4;        // LDS row stride (144-byte rows: conflict-free b128 reads, as gemm.hip)
-constexpr int SZ = T * LD;        // floats per stage buffer
-constexpr int NL = T * KC / 1024; // float4 per thread, operand and chunk
-constexpr int RQ = KC / 4;        // float4 per row of a chunk
-constexpr int RED_LD = 65;        // row stride of the end-of-march fold (64 candidates per row + 1 pad)
-constexpr size_t STAGE_BYTES = (size_t)4 * SZ * sizeof(float);
+using namespace march;
 constexpr size_t LDS_BYTES = STAGE_BYTES + T * sizeof(float);                 // + 1 / ||x|| of the workgroup's rows
 static_assert((size_t)2 * T * RED_LD * sizeof(float) + 2 * T * sizeof(int) <= STAGE_BYTES, "the fold reuses the stage buffers");
-
-// FAST: whole tiles, whole K chunks and 16-byte aligned rows (checked by the launcher, per operand): plain float4 loads
-template <bool FAST>
-__device__ __forceinline__ void load_rows(f32x4 (&reg)[NL], const float* __restrict__ base, int ld, int r0, int rmax, int k0, int D,
-                                          bool al) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        const int idx = threadIdx.x + 256 * i;
-        const int r = r0 + idx / RQ, k = k0 + (idx % RQ) * 4;
-        f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (FAST) {
-            v = *reinterpret_cast<const f32x4*>(base + (size_t)r * ld + k);
-        } else if (r < rmax) {
-            const float* p = base + (size_t)r * ld + k;
-            const int n = D - k;
-            if (n >= 4 && al) {
-                v = *reinterpret_cast<const f32x4*>(p);
-            } else {
-                if (n > 0) v.x = p[0];
-                if (n > 1) v.y = p[1];
-                if (n > 2) v.z = p[2];
-                if (n > 3) v.w = p[3];
-            }
-        }
-        reg[i] = v;
-    }
-}
-
-__device__ __forceinline__ void store_rows(float* s, const f32x4 (&reg)[NL]) {
-#pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        const int idx = threadIdx.x + 256 * i;
-        *reinterpret_cast<f32x4*>(s + (idx / RQ) * LD + (idx % RQ) * 4) = reg[i];
-    }
-}
 
 struct MapOut {
     int* best;
@@ -85,30 +39,17 @@ struct MapOut {
     int lds;
 };
 
-// the 64 lanes (2 waves x 32 columns) that share a row leave one candidate each; thread t < T then reads row t's 64
-__device__ __forceinline__ int fold_slot(int wm0, int i, int r, int kl, int wid, int ml) {
-    return (wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kl) * RED_LD + (wid & 1) * 32 + ml;
-}
-
 template <bool FX, bool FE, bool SIM>
 __global__ __launch_bounds__(256) void label_map_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ e, int lde,
                                                         const float* __restrict__ inv_x, const float* __restrict__ inv_e, float th0,
                                                         float th1, MapOut out, int N, int C, int D, int W, bool x_al, bool e_al) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;             // [2][SZ]
-    float* Bs = smem + 2 * SZ;    // [2][SZ]
     float* rxs = smem + 4 * SZ;   // [T]
     const int m0 = blockIdx.x * T;
-    const int n_tiles = (C + T - 1) / T;
-    const int kiters = (D + KC - 1) / KC;
-    const int total = n_tiles * kiters;
-
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wm0 = (wid >> 1) * 64, wn0 = (wid & 1) * 64;
-    const int kl = lane >> 5, ml = lane & 31;
+    const Lanes l = lanes();
+    const int wid = l.wid, wm0 = l.wm0, lane = l.lane;
     const int brow = m0 + wm0 + lane;     // the row whose window words this lane collects
 
-    f32x16 acc[2][2];
     float best[2][16], wval[2][16], minv[2][16];
     int bidx[2][16], widx[2][16];
     int cnt = 0;
@@ -121,112 +62,53 @@ __global__ __launch_bounds__(256) void label_map_kernel(const float* __restrict_
             wval[i][r] = -INFINITY;
             widx[i][r] = -1;
             minv[i][r] = INFINITY;
-            acc[i][0][r] = 0.0f;
-            acc[i][1][r] = 0.0f;
         }
 
     if (threadIdx.x < T) rxs[threadIdx.x] = m0 + (int)threadIdx.x < N ? inv_x[m0 + threadIdx.x] : 1.0f;
 
-    f32x4 ra[NL], rb[NL];
-    int ld_tile = 0, ld_k = 0;            // the chunk the next load requests
-    auto load_next = [&]() {
-        load_rows<FX>(ra, x, ldx, m0, N, ld_k * KC, D, x_al);
-        load_rows<FE>(rb, e, lde, ld_tile * T, C, ld_k * KC, D, e_al);
-        if (++ld_k == kiters) { ld_k = 0; ++ld_tile; }
-    };
-    load_next();
-    store_rows(As, ra);
-    store_rows(Bs, rb);
-    __syncthreads();
-
-    int tile = 0, kc = 0;
-    for (int it = 0; it < total; ++it) {
-        const int buf = it & 1;
-        if (it + 1 < total) load_next();
-        __builtin_amdgcn_sched_barrier(0);
-        const float* a = As + buf * SZ + (wm0 + ml) * LD + kl * 4;
-        const float* b = Bs + buf * SZ + (wn0 + ml) * LD + kl * 4;
-        f32x4 af[2][2], bf[2][2];
+    // This lane meets its columns in ascending order (tile, then j) and replaces on > only.  A column past C (its label rows were
+    // zero-filled: s = 0) takes part in nothing.
+    march_tiles<FX, FE>(smem, Rows{x, ldx, N, x_al}, Rows{e, lde, C, e_al}, m0, 0, (C + T - 1) / T, D,
+                        [&](int tile, const f32x16 (&acc)[2][2]) {
+        int w[2] = {0, 0};
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            af[0][i] = *reinterpret_cast<const f32x4*>(a + i * 32 * LD);
-            bf[0][i] = *reinterpret_cast<const f32x4*>(b + i * 32 * LD);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+        for (int j = 0; j < 2; ++j) {
+            const int n = tile * T + l.wn0 + j * 32 + l.ml;
+            const bool real = n < C;
+            const unsigned long long realb = __ballot(real);
+            const float re = real ? inv_e[n] : 1.0f;
 #pragma unroll
-        for (int g = 0; g < KC / 8; ++g) {
-            if (g + 1 < KC / 8) {
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    af[(g + 1) & 1][i] = *reinterpret_cast<const f32x4*>(a + i * 32 * LD + 8 * (g + 1));
-                    bf[(g + 1) & 1][i] = *reinterpret_cast<const f32x4*>(b + i * 32 * LD + 8 * (g + 1));
+                for (int r = 0; r < 16; ++r) {
+                    const int rl = acc_row(i, r);             // row wm0 + rl + 4 kl
+                    const float s = (acc[i][j][r] * rxs[wm0 + rl + 4 * l.kl]) * re;
+                    const bool inw = real && s >= th0 && s <= th1 && s != 0.0f;
+                    if constexpr (SIM) {
+                        const int row = m0 + wm0 + rl + 4 * l.kl;
+                        if (real && row < N) out.sim[(size_t)row * out.lds + n] = s;
+                    }
+                    if (real && s > best[i][r]) {
+                        best[i][r] = s;
+                        bidx[i][r] = n;
+                    }
+                    if (real && s < minv[i][r]) minv[i][r] = s;
+                    if (inw && (widx[i][r] < 0 || s > wval[i][r])) {
+                        wval[i][r] = s;
+                        widx[i][r] = n;
+                    }
+                    ballot_to_words(w[j], __ballot(inw) & realb, rl);
                 }
-            }
-#pragma unroll
-            for (int ee = 0; ee < 4; ++ee)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g & 1][i][ee], bf[g & 1][j][ee], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
         }
-        if (it + 1 < total) {
-            store_rows(As + (buf ^ 1) * SZ, ra);
-            store_rows(Bs + (buf ^ 1) * SZ, rb);
-        }
-        if (++kc == kiters) {
-            // the tile's products are complete: register r of acc[i][j] is row wm0 + 32 i + (r & 3) + 8 (r >> 2) + 4 kl, column
-            // wn0 + 32 j + ml.  This lane meets its columns in ascending order (tile, then j) and replaces on > only.  A column
-            // past C (its label rows were zero-filled: s = 0) takes part in nothing.
-            int w[2] = {0, 0};
+        if (brow < N) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const int n = tile * T + wn0 + j * 32 + ml;
-                const bool real = n < C;
-                const unsigned long long realb = __ballot(real);
-                const float re = real ? inv_e[n] : 1.0f;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rl = 32 * i + (r & 3) + 8 * (r >> 2);          // row wm0 + rl + 4 kl
-                        const float s = (acc[i][j][r] * rxs[wm0 + rl + 4 * kl]) * re;
-                        const bool inw = real && s >= th0 && s <= th1 && s != 0.0f;
-                        if constexpr (SIM) {
-                            const int row = m0 + wm0 + rl + 4 * kl;
-                            if (real && row < N) out.sim[(size_t)row * out.lds + n] = s;
-                        }
-                        if (real && s > best[i][r]) {
-                            best[i][r] = s;
-                            bidx[i][r] = n;
-                        }
-                        if (real && s < minv[i][r]) minv[i][r] = s;
-                        if (inw && (widx[i][r] < 0 || s > wval[i][r])) {
-                            wval[i][r] = s;
-                            widx[i][r] = n;
-                        }
-                        // lane rl takes the low half (the row of the lower 32 lanes), lane rl + 4 the high half
-                        const unsigned long long hit = __ballot(inw) & realb;
-                        // (v_writelane_b32 as in dbscan.hip: this compiler has no builtin for it)
-                        asm("v_writelane_b32 %0, %1, %2" : "+v"(w[j]) : "s"((int)(unsigned)hit), "n"(rl));
-                        asm("v_writelane_b32 %0, %1, %2" : "+v"(w[j]) : "s"((int)(unsigned)(hit >> 32)), "n"(rl + 4));
-                        acc[i][j][r] = 0.0f;
-                    }
+                const int word = tile * 4 + (wid & 1) * 2 + j;
+                if (word < W) out.win_bits[(size_t)brow * W + word] = (unsigned)w[j];
             }
-            if (brow < N) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int word = tile * 4 + (wid & 1) * 2 + j;
-                    if (word < W) out.win_bits[(size_t)brow * W + word] = (unsigned)w[j];
-                }
-            }
-            cnt += __popc((unsigned)w[0]) + __popc((unsigned)w[1]);
-            kc = 0;
-            ++tile;
         }
-        __syncthreads();
-    }
+        cnt += __popc((unsigned)w[0]) + __popc((unsigned)w[1]);
+    });
 
     // fold the 64 lanes that share a row, one quantity after the other; the stage buffers are free after the last barrier
     float* rs = smem;
@@ -240,7 +122,7 @@ __global__ __launch_bounds__(256) void label_map_kernel(const float* __restrict_
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = fold_slot(wm0, i, r, kl, wid, ml);
+            const int o = fold_slot(l, i, r);
             rs[o] = best[i][r];
             ri[o] = bidx[i][r];
         }
@@ -265,7 +147,7 @@ __global__ __launch_bounds__(256) void label_map_kernel(const float* __restrict_
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = fold_slot(wm0, i, r, kl, wid, ml);
+            const int o = fold_slot(l, i, r);
             rs[o] = wval[i][r];
             ri[o] = widx[i][r];
         }
@@ -287,7 +169,7 @@ __global__ __launch_bounds__(256) void label_map_kernel(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) rs[fold_slot(wm0, i, r, kl, wid, ml)] = minv[i][r];
+        for (int r = 0; r < 16; ++r) rs[fold_slot(l, i, r)] = minv[i][r];
     __syncthreads();
     if (owner) {
         float bs = rs[t * RED_LD];
@@ -353,8 +235,6 @@ __global__ __launch_bounds__(256) void label_map_topk_kernel(const float* __rest
     }
 }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 // row and tile origins (N + 127, C + 127, D + 31) are ints; the grids are one-dimensional (N / 128 and (N + C) / 4 workgroups)
 bool shape_ok(int N, int C, int D) { return N >= 1 && C >= 1 && D >= 1 && N <= INT_MAX - T && C <= INT_MAX - T && D <= INT_MAX - KC; }
 
@@ -363,18 +243,9 @@ int check_shape(const char* fn, int N, int C, int D) {
         tag_set_error("%s: N, C, D must be >= 1 (got %d, %d, %d)", fn, N, C, D);
         return TAG_EINVAL;
     }
-    if (N > INT_MAX - T) {
-        tag_set_error("%s: N = %d exceeds %d (row index limit)", fn, N, INT_MAX - T);
-        return TAG_EINVAL;
-    }
-    if (C > INT_MAX - T) {
-        tag_set_error("%s: C = %d exceeds %d (column index limit)", fn, C, INT_MAX - T);
-        return TAG_EINVAL;
-    }
-    if (D > INT_MAX - KC) {
-        tag_set_error("%s: D = %d exceeds %d (chunk index limit)", fn, D, INT_MAX - KC);
-        return TAG_EINVAL;
-    }
+    if (int rc = check_index_limit(fn, "N", N, T, "row")) return rc;
+    if (int rc = check_index_limit(fn, "C", C, T, "column")) return rc;
+    if (int rc = check_index_limit(fn, "D", D, KC, "chunk")) return rc;
     return 0;
 }
 

@@ -69,22 +69,6 @@ __global__ __launch_bounds__(64) void segments_double_kernel(const float* __rest
     counts[id] = n_out;
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return v;
-}
-
 // floor(t / r) and ceil(t / r) as segment indices in [0, MAX_SEGMENTS + 1]: negative, NaN -> 0; anything above the limit -> limit + 1
 __device__ __forceinline__ int seg_floor(double t, double r) {
     const double q = floor(t / r);

@@ -31,8 +31,6 @@ constexpr int T = 128;                  // tile edge of a workgroup (4 waves, 64
 constexpr int UN = 4;                   // row pairs per group of loads: 16 loads in flight per lane
 static_assert(L % (2 * UN) == 0 && UN % 2 == 0, "a slice is whole groups, a group feeds both accumulator sets alike");
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 // ------------------------------------------------------------------------------------------------------------------------
 // gram
 // ------------------------------------------------------------------------------------------------------------------------

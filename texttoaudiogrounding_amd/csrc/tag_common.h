@@ -37,6 +37,9 @@ static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// a pointer that float4 / 16-byte vector accesses may use
+static inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
 // ---- counter-based keep-mask for dropout: splitmix64 of (seed, index) -> uniform in [0,1) ----
 __host__ __device__ __forceinline__ uint64_t tag_mix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
@@ -73,6 +76,21 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_min_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
+    return v;
+}
+__device__ __forceinline__ int wave_max_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
     return v;
 }
 

@@ -222,8 +222,6 @@ int ta_waves(size_t lds_per_wave) {
     return fit >= 4 ? 4 : (fit >= 1 ? (int)fit : 1);
 }
 
-bool ta_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int ta_elementwise_blocks(long total) {
     const long b = (total + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
@@ -242,7 +240,7 @@ extern "C" int tag_text_selfattn_forward(const float* qkv, const int64_t* klen, 
     const dim3 grid((unsigned)((pairs + waves - 1) / waves)), block(64 * waves);
     const float scale = 1.0f / sqrtf((float)(E / H));
     // head slices start at multiples of 16 channels and rows are 3E floats apart: 16-byte reads need only an aligned base
-    if (ta_aligned16(qkv))
+    if (aligned16(qkv))
         hipLaunchKernelGGL(text_selfattn_fwd_kernel<true>, grid, block, lds_wave * waves, as_stream(stream), qkv, klen, ctx, attn, R, S,
                            E, H, scale, drop_p, seed);
     else
@@ -262,7 +260,7 @@ extern "C" int tag_text_selfattn_backward(const float* qkv, const float* attn, c
     const long pairs = (long)R * H;
     const dim3 grid((unsigned)((pairs + waves - 1) / waves)), block(64 * waves);
     const float scale = 1.0f / sqrtf((float)(E / H));
-    if (ta_aligned16(qkv) && ta_aligned16(dctx))
+    if (aligned16(qkv) && aligned16(dctx))
         hipLaunchKernelGGL(text_selfattn_bwd_kernel<true>, grid, block, lds_wave * waves, as_stream(stream), qkv, attn, dctx, klen,
                            dqkv, R, S, E, H, scale, drop_p, seed);
     else

@@ -260,8 +260,6 @@ __global__ __launch_bounds__(256) void tc_map_kernel(const float* __restrict__ a
     for (long i = done + tid; i < n; i += nt) out[i] = tc_map<OP>(a[i], OP == 0 ? 0.0f : b[i]);
 }
 
-bool tc_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int tc_part_blocks(long rows) {
     const long b = (rows + 3) / 4;
     return (int)(b > TC_MAX_PART_BLOCKS ? TC_MAX_PART_BLOCKS : b);
@@ -271,7 +269,7 @@ size_t tc_part_floats(long rows, int D) { return (size_t)tc_part_blocks(rows) * 
 
 template <int OP>
 int tc_launch_map(const float* a, const float* b, float* out, long n, void* stream) {
-    const int vec = tc_aligned16(a) && tc_aligned16(out) && (OP == 0 || tc_aligned16(b));
+    const int vec = aligned16(a) && aligned16(out) && (OP == 0 || aligned16(b));
     const long work = vec ? (n + 3) / 4 : n;
     long nb = (work + 255) / 256;
     if (nb > 8192) nb = 8192;
@@ -295,8 +293,8 @@ int tc_launch_map(const float* a, const float* b, float* out, long n, void* stre
 
 int tc_launch_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, float* ds, float* part, long rows,
                      int D, void* stream) {
-    const bool vec = D % 4 == 0 && tc_aligned16(dy) && tc_aligned16(xhat) && tc_aligned16(gamma) && tc_aligned16(ds) &&
-                     tc_aligned16(part);
+    const bool vec = D % 4 == 0 && aligned16(dy) && aligned16(xhat) && aligned16(gamma) && aligned16(ds) &&
+                     aligned16(part);
     const int nblk = tc_part_blocks(rows);
 #define CALL(NQ, V)                                                                                                        \
     hipLaunchKernelGGL((tc_ln_bwd_kernel<NQ, V>), dim3(nblk), dim3(256), 0, as_stream(stream), dy, xhat, rstd, gamma, ds, \
@@ -329,8 +327,8 @@ extern "C" int tag_text_clap_resln_forward(const float* x, const float* res, con
     TAG_CHECK_ARG(x && gamma && beta && y);
     TAG_CHECK_ARG((xhat == nullptr) == (rstd == nullptr));
     TAG_CHECK_ARG(rows >= 1 && rows <= (1L << 31) && D >= 1 && D <= TC_MAX_D && eps >= 0.0f);
-    const bool vec = D % 4 == 0 && tc_aligned16(x) && tc_aligned16(res) && tc_aligned16(gamma) && tc_aligned16(beta) &&
-                     tc_aligned16(y) && tc_aligned16(xhat);
+    const bool vec = D % 4 == 0 && aligned16(x) && aligned16(res) && aligned16(gamma) && aligned16(beta) &&
+                     aligned16(y) && aligned16(xhat);
 #define CALL(NQ, V)                                                                                                           \
     hipLaunchKernelGGL((tc_resln_fwd_kernel<NQ, V>), dim3(cdiv(rows, 4)), dim3(256), 0, as_stream(stream), x, res, gamma, beta, \
                        eps, y, xhat, rstd, rows, D);
@@ -366,8 +364,8 @@ extern "C" int tag_text_clap_embed_forward(const int64_t* ids, const float* word
     TAG_CHECK_ARG(B >= 1 && L >= 1 && D >= 1 && D <= TC_MAX_D && V >= 1 && eps >= 0.0f);
     TAG_CHECK_ARG(pad_id >= 0 && (long)L + pad_id < (long)P);          // the largest position id is L + pad_id
     const long rows = (long)B * L;
-    const bool vec = D % 4 == 0 && tc_aligned16(word) && tc_aligned16(type0) && tc_aligned16(pos) && tc_aligned16(gamma) &&
-                     tc_aligned16(beta) && tc_aligned16(h) && tc_aligned16(xhat);
+    const bool vec = D % 4 == 0 && aligned16(word) && aligned16(type0) && aligned16(pos) && aligned16(gamma) &&
+                     aligned16(beta) && aligned16(h) && aligned16(xhat);
 #define CALL(NQ, VV)                                                                                                         \
     hipLaunchKernelGGL((tc_embed_fwd_kernel<NQ, VV>), dim3(cdiv(rows, 4)), dim3(256), 0, as_stream(stream), ids, word, type0, \
                        pos, gamma, beta, eps, h, pos_ids, xhat, rstd, B, L, D, V, pad_id);
