@@ -1316,6 +1316,33 @@ int tag_label_map(const float* x, int ldx, const float* e, int lde, float th0, f
                   void* ws, void* stream);
 int tag_label_map_topk(const float* sim, int lds, float th0, float th1, int* idx, int N, int C, int k, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * BERTScore phrase-to-label map (bertscore.hip; utils/data/create_phrase_event_mapping/prepare_phrase_bertscore.py in the
+ * reference scores every (phrase, label) pair with bert_score.score and keeps the arg-max F1).  Greedy matching of token vectors,
+ * all pairs, without a token x token score matrix:
+ *   a  phrase tokens, N items of slot_a consecutive rows each: (N * slot_a, D) fp32, row stride lda >= D (in floats);
+ *   b  label tokens, C items of slot_b rows each: (C * slot_b, D) fp32, row stride ldb >= D;
+ *   a_len (N), b_len (C) int32: the valid rows of an item are its first len; a value outside 1 .. slot is taken as the nearest
+ *      end of that range (nothing is ever read out of bounds on account of a length);
+ *   a_w (N, slot_a), b_w (C, slot_b) fp32, dense: token weights; entries at and past the length are not read as weights.
+ * The ACCEPTED SLOTS are 8, 16 and 32 (slot_a and slot_b independently): a slot is a power of two that divides the 128-row
+ * tile, so no item straddles one.  The rows are used as they are (the caller normalises: bert_score normalises, then multiplies).
+ * With s_ij = a[n,i] . b[c,j] on the exact-fp32 MFMA (operands not rounded), i < a_len[n], j < b_len[c]:
+ *   P = sum_i a_w[n,i] max_j s_ij / sum_i a_w[n,i],  R = sum_j b_w[c,j] max_i s_ij / sum_j b_w[c,j],  F = 2 P R / (P + R);
+ *   a zero weight sum gives P = 0 (R = 0), P + R == 0 gives F = 0.  A row or column past the length enters NO maximum and no sum
+ *   (masked by the length; the contents of such rows do not matter as long as they are finite).
+ * Written for every phrase n: best[n] (int32) = argmax_c F, ties to the lowest c; best_f, best_p, best_r (fp32) = F, P, R there.
+ * scores: (3, N, C) fp32 dense = P, R, F of every pair, or NULL: the other outputs have the same bits either way.
+ * ws (tag_bertscore_map_ws_bytes, a function of the shape and the slots alone, 0 for a call that would be refused) is never
+ * zeroed; no atomics: the same bits on every run, and identical label items score identically bit for bit wherever they stand.
+ * TAG_EINVAL before any launch, the numbers named in tag_last_error: N, C or D < 1, a slot other than 8, 16, 32, a row stride
+ * below D, a null pointer (scores excepted), N * slot_a or C * slot_b above 2^31 - 129.
+ */
+size_t tag_bertscore_map_ws_bytes(int N, int C, int D, int slot_a, int slot_b);
+int tag_bertscore_map(const float* a, int lda, const int32_t* a_len, const float* a_w, const float* b, int ldb,
+                      const int32_t* b_len, const float* b_w, int slot_a, int slot_b, int N, int C, int D, int* best, float* best_f,
+                      float* best_p, float* best_r, float* scores, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

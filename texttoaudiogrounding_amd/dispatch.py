@@ -2783,3 +2783,117 @@ def label_map(x, e, th0, th1, topk=1, want_sim=False):
         idx = torch.empty(N, k, device=dev, dtype=torch.int32)
         call("tag_label_map_topk", ptr(sim), C, th0, th1, ptr(idx), N, C, k)
     return LabelMapResult(best, best_sim, min_sim, win_best, win_count, win_bits, sim if want_sim else None, idx)
+
+
+# ------------------------------------------------------------------------------------------------
+# BERTScore phrase-to-label map (bert_score.score on every (phrase, label) pair in the reference's prepare_phrase_bertscore.py),
+# bertscore.hip
+# ------------------------------------------------------------------------------------------------
+
+#: the item slots of tag_bertscore_map (include/tag_hip.h) and the longest item
+BERTSCORE_SLOTS = (8, 16, 32)
+BERTSCORE_MAX_LEN = 32
+
+BertScoreMapResult = collections.namedtuple("BertScoreMapResult", "best best_f best_p best_r scores")
+
+
+def bertscore_slot(L):
+    """The smallest accepted slot that holds items of L tokens."""
+    for s in BERTSCORE_SLOTS:
+        if L <= s:
+            return s
+    raise ValueError(f"bertscore_map: items of {L} tokens exceed the largest slot {BERTSCORE_MAX_LEN}")
+
+
+def bertscore_default_weights(lens, L):
+    """bert_score's weights with idf=False: 1 for every token below the length, 0 for the first and the last token of an item
+    (its [CLS] and [SEP]); (rows, L) fp32 on the device of lens.  An item of one or two tokens has no weight left."""
+    pos = torch.arange(L, device=lens.device)[None, :]
+    n = lens.to(torch.int64)[:, None]
+    return ((pos >= 1) & (pos < n - 1)).to(F32)
+
+
+def _bertscore_check(x, x_len, x_w, name):
+    """The checks of one operand that need no device -> (lengths tensor, the longest length)."""
+    if not torch.is_tensor(x) or x.dtype != F32 or x.dim() != 3 or min(x.shape) < 1:
+        raise RuntimeError(f"{name}: expected a float32 (items >= 1, L >= 1, D >= 1) tensor, got "
+                           f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    rows, L, D = x.shape
+    if x_len is None:
+        if L > BERTSCORE_MAX_LEN:
+            raise ValueError(f"{name}: L = {L} tokens per item exceed the limit {BERTSCORE_MAX_LEN}; pass {name}_len")
+        x_len = torch.full((rows,), L, device=x.device, dtype=torch.int32)
+    if not torch.is_tensor(x_len) or x_len.device != x.device or x_len.dtype not in (torch.int32, torch.int64) \
+            or tuple(x_len.shape) != (rows,):
+        raise RuntimeError(f"{name}_len: expected an int32 / int64 ({rows},) tensor on {x.device}, got "
+                           f"{getattr(x_len, 'dtype', type(x_len))} {tuple(getattr(x_len, 'shape', ()))} on "
+                           f"{getattr(x_len, 'device', 'the host')}")
+    if x_w is not None and (not torch.is_tensor(x_w) or x_w.device != x.device or x_w.dtype != F32
+                            or tuple(x_w.shape) != (rows, L)):
+        raise RuntimeError(f"{name}_w: expected a float32 ({rows}, {L}) tensor on {x.device}, got "
+                           f"{getattr(x_w, 'dtype', type(x_w))} {tuple(getattr(x_w, 'shape', ()))} on "
+                           f"{getattr(x_w, 'device', 'the host')}")
+    if x.device.type == "meta":
+        return x_len, min(L, BERTSCORE_MAX_LEN)
+    lo, hi = torch.stack([x_len.min(), x_len.max()]).tolist()          # (one read of the device per operand)
+    if lo < 1 or hi > min(L, BERTSCORE_MAX_LEN):
+        raise ValueError(f"{name}_len: lengths must lie in [1, {min(L, BERTSCORE_MAX_LEN)}] (L = {L}, the limit is "
+                         f"{BERTSCORE_MAX_LEN} tokens per item), got [{lo}, {hi}]")
+    return x_len, hi
+
+
+def _bertscore_operand(x, x_len, x_w, longest, normalize):
+    """-> (tokens (rows, slot, D) fp32 with unit column stride, lengths int32 (rows,), weights fp32 (rows, slot), slot)"""
+    rows, L, D = x.shape
+    slot = bertscore_slot(longest)
+    keep = min(L, slot)                                   # (columns past the longest item hold nothing that is used)
+    if x_w is None:
+        w = bertscore_default_weights(x_len, slot)
+    else:
+        w = torch.zeros(rows, slot, device=x.device, dtype=F32)
+        w[:, :keep] = x_w[:, :keep]
+    if L == slot and not normalize and x.stride(2) == 1 and x.stride(1) >= D and x.stride(0) == slot * x.stride(1):
+        tok = x                                           # slot-sized unit rows: passed as they are, any 4-byte aligned base
+    else:
+        tok = torch.zeros(rows, slot, D, device=x.device, dtype=F32)
+        tok[:, :keep] = x[:, :keep]
+        if normalize:
+            tok = _unit_rows(tok.view(rows * slot, D), rows * slot, D).view(rows, slot, D)
+    return tok, x_len.to(torch.int32).contiguous(), w.contiguous(), slot
+
+
+def bertscore_map(a, a_len, a_w, b, b_len, b_w, want_scores=False, normalize=True):
+    """BERTScore of every phrase against every label by greedy token matching, one march on the exact-fp32 MFMA (bertscore.hip):
+    a (N, La, D) phrase tokens with lengths a_len (N,) and weights a_w (N, La), b (C, Lb, D), b_len (C,), b_w (C, Lb) the labels;
+    any La, Lb, every length in 1 .. 32 (and <= La, Lb).  With s_ij = a[n,i] . b[c,j] over the tokens below the lengths:
+    P = sum_i a_w max_j s_ij / sum_i a_w, R = sum_j b_w max_i s_ij / sum_j b_w, F = 2 P R / (P + R); a zero weight sum gives 0, and
+    so does P + R == 0.  A padded position enters no maximum and no sum.  -> BertScoreMapResult of device tensors:
+
+    best (N,) int32 argmax_c F (ties to the lowest c), best_f, best_p, best_r (N,) fp32 the values there, scores (3, N, C) fp32
+    = P, R, F of every pair when want_scores, else None (no score array of any kind exists then).
+
+    a_len / b_len None: every item is full; a_w / b_w None: bert_score's idf=False weights (bertscore_default_weights: 0 for the
+    first and last token of an item, 1 between).  normalize: the token vectors through x / max(||x||, 1e-12) first (bert_score's
+    order: normalise, then multiply); with normalize=False a (items, slot, D) tensor or row-strided view whose L is an accepted
+    slot (8, 16, 32) is passed to the kernel as it is.  Items are padded to the smallest slot that holds the longest one.
+    The same bits on every run; there is no CPU fallback."""
+    a_len, a_hi = _bertscore_check(a, a_len, a_w, "a")
+    b_len, b_hi = _bertscore_check(b, b_len, b_w, "b")
+    if b.device != a.device or b.shape[2] != a.shape[2]:
+        raise RuntimeError(f"b {tuple(b.shape)} on {b.device}: expected a's device {a.device} and D = {a.shape[2]}")
+    if not a.is_cuda:
+        raise RuntimeError(f"a, b: expected tensors on the MI355X (cuda) device, got {a.device}; the HIP path has no CPU fallback")
+    at, al, aw, sa = _bertscore_operand(a, a_len, a_w, a_hi, normalize)
+    bt, bl, bw, sb = _bertscore_operand(b, b_len, b_w, b_hi, normalize)
+    N, C, D = at.shape[0], bt.shape[0], at.shape[2]
+    nws = query("tag_bertscore_map_ws_bytes", N, C, D, sa, sb)
+    if nws == 0:
+        raise RuntimeError(f"bertscore_map: N = {N} x slot {sa}, C = {C} x slot {sb}: expected at most {2**31 - 129} token rows")
+    dev = at.device
+    best = torch.empty(N, device=dev, dtype=torch.int32)
+    best_f, best_p, best_r = (torch.empty(N, device=dev, dtype=F32) for _ in range(3))
+    scores = torch.empty(3, N, C, device=dev, dtype=F32) if want_scores else None
+    ws = _ws(nws, at)
+    call("tag_bertscore_map", ptr(at), at.stride(1), ptr(al), ptr(aw), ptr(bt), bt.stride(1), ptr(bl), ptr(bw), sa, sb, N, C, D,
+         ptr(best), ptr(best_f), ptr(best_p), ptr(best_r), ptr(scores), ptr(ws))
+    return BertScoreMapResult(best, best_f, best_p, best_r, scores)

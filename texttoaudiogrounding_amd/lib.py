@@ -262,6 +262,8 @@ _SIGS = {
     "tag_label_map_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tag_label_map": (c_int, [P, c_int, P, c_int, c_float, c_float, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "tag_label_map_topk": (c_int, [P, c_int, c_float, c_float, P, c_int, c_int, c_int, P]),
+    "tag_bertscore_map_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "tag_bertscore_map": (c_int, [P, c_int, P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P]),
 }
 
 _lib = None
