@@ -598,6 +598,37 @@ int tag_text_clap_gelu_backward(const float* u, const float* df, float* du, long
 int tag_text_clap_tanh_backward(const float* y, const float* dy, float* dx, long n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * T7: BERT (models/text_encoder.py:271-308 Bert / SentenceBert over Hugging Face's BertModel): the encoder stack is the one of
+ * T6; text_bert.hip holds BertEmbeddings and the sentence poolings, each with its backward.  Same conventions as T6: fp32, one
+ * wave per row, 1 <= D <= 1024, no atomics, two runs bit-identical, TAG_EINVAL before any launch for anything else.
+ * embed_forward: h[b,l] = LayerNorm(word[ids[b,l]] + type[type_ids[b,l]] + pos[l]) gamma + beta; the position of a token is its
+ *   column l (pads included), L <= P.  T >= 1 (the backward serves T <= 16 only: a trainable model keeps to that).  type_ids
+ *   nullable (all zeros); a type id outside [0,T) is clamped, a token id outside
+ *   [0,V) reads nothing (tag_embed_check_ids raises the flag for either).  xhat (B*L,D), rstd (B*L): both or neither.
+ * embed_backward: dh (B*L,D) -> dword (V,D) ACCUMULATED into a caller-zeroed table by the first-occurrence gather of T6 (tokens
+ *   equal to pad_id skipped: row pad_id stays exactly zero; pad_id < 0: no padding index); dpos rows [0,L) WRITTEN with
+ *   sum_b ds[b,l], rows >= L not touched; dtype (T,D) WRITTEN with the sums of the rows of each type id (T <= 16); dgamma, dbeta.
+ *   Padded positions contribute to dpos and dtype.  Every output nullable (at least one asked for).
+ * pool_forward: h (R,L,D), klen (R) int64 (read by mode 1 only, clamped to [0,L]).  mode 0: x = h[r,0]; mode 1: x =
+ *   sum_{l<klen} h[r,l] / max(klen, 1e-9) (klen = 0: a zero row).  norm 0: out = x; 1: x / max(|x|, 1e-12); 2: x / (|x| + 1e-7)
+ *   clipped to +-1e3 (forward only).  raw (R,D) nullable receives x.
+ * pool_backward: dh (R,L,D) = dtok (nullable: zeros) + the pooling's gradient of dseq (nullable) on row 0 / the first klen rows,
+ *   through the F.normalize backward for norm 1 (raw = the forward's x).  norm in {0, 1}.  dh must not alias an input.
+ * ------------------------------------------------------------------------------------------- */
+int tag_text_bert_embed_forward(const int64_t* ids, const int64_t* type_ids /* nullable */, const float* word, const float* type,
+                                const float* pos, const float* gamma, const float* beta, float eps, float* h,
+                                float* xhat /* nullable */, float* rstd /* nullable */, int B, int L, int D, int V, int T, int P,
+                                void* stream);
+size_t tag_text_bert_embed_backward_ws_bytes(int B, int L, int D, int T);
+int tag_text_bert_embed_backward(const float* dh, const float* xhat, const float* rstd, const float* gamma, const int64_t* ids,
+                                 const int64_t* type_ids /* nullable */, float* dword, float* dtype, float* dpos, float* dgamma,
+                                 float* dbeta, int B, int L, int D, int V, int T, int P, int pad_id, void* ws, void* stream);
+int tag_text_bert_pool_forward(const float* h, const int64_t* klen, int mode, int norm, float* raw /* nullable */, float* out,
+                               long R, int L, int D, void* stream);
+int tag_text_bert_pool_backward(const float* dseq /* nullable */, const float* dtok /* nullable */, const float* raw,
+                                const int64_t* klen, int mode, int norm, float* dh, long R, int L, int D, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * T1 + T2: nn.Embedding gather + mean over valid tokens
  * models/text_encoder.py:39-43,79-88; models/utils.py:33-58.
  * text (B,L) int64, text_len (B) int64, table (V,D); token_emb (B,L,D) nullable; seq_emb (B,D).

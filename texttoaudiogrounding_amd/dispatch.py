@@ -1474,6 +1474,91 @@ def _clap_dropout(x2d, p, seed, backward=False):
     return text_gru_dropout(x2d, p, seed, backward) if p > 0.0 else x2d
 
 
+def _text_stack_forward(h, klen, params, layers, R, L, heads, eps, need_grad, p_hidden, p_attn, s_layers, last_out=None):
+    """The post-LayerNorm encoder layers shared by the CLAP and the BERT tower: per layer the packed q|k|v GEMM, the attention
+    core, the out-projection, residual LayerNorm, GELU feed-forward and the second residual LayerNorm.  h (R*L, D) behind the
+    embedding block; params[5 + 16 l ...] the layer's 16 parameters; last_out: a (R*L, D) destination of the last layer's rows.
+    -> the last hidden state (R*L, D), what the backward reads per layer ([] unless need_grad)."""
+    M, D = h.shape
+    saved = []
+    for l in range(layers):
+        b = 5 + 16 * l
+        qw, qb, kw, kb, vw, vb, aow, aob, g1, b1, iw, ib, ow, ob, g2, b2 = params[b:b + 16]
+        s_attn, s_ao, s_out = s_layers[l]
+        I = iw.shape[0]
+        wqkv, bqkv = torch.cat((qw, kw, vw), 0), torch.cat((qb, kb, vb), 0)
+        qkv = gemm(h, wqkv, M, 3 * D, D, transB=True, bias=bqkv)
+        ctx, attn = text_selfattn_core(qkv.view(R, L, 3 * D), klen, heads, need_grad, p_attn, s_attn)
+        ctx = ctx.view(M, D)
+        a = _clap_dropout(gemm(ctx, aow, M, D, D, transB=True, bias=aob), p_hidden, s_ao)
+        h1, xhat1, rstd1 = text_clap_resln_forward(a, h, g1, b1, eps, need_grad)
+        u = gemm(h1, iw, M, I, D, transB=True, bias=ib)      # no fused activation: the backward reads the pre-activation
+        f = text_clap_gelu_forward(u)
+        f2 = _clap_dropout(gemm(f, ow, M, D, I, transB=True, bias=ob), p_hidden, s_out)
+        hn, xhat2, rstd2 = text_clap_resln_forward(f2, h1, g2, b2, eps, need_grad, out=last_out if l == layers - 1 else None)
+        if need_grad:
+            saved.append(dict(x=h, qkv=qkv, attn=attn, ctx=ctx, xhat1=xhat1, rstd1=rstd1, h1=h1, u=u, f=f, xhat2=xhat2, rstd2=rstd2,
+                              wqkv=wqkv))
+        h = hn
+    return h, saved
+
+
+def _text_stack_backward(dh, saved_layers, klen, params, layers, R, L, heads, p_hidden, p_attn, s_layers, need, outs, g):
+    """Backward of _text_stack_forward: dh (R*L, D) on the last hidden state -> the gradient behind the embedding block, or None
+    when the walk stopped because nothing below needs a gradient.  Fills g[5 + 16 l ...] where need says so (outs: destinations)."""
+    M, D = dh.shape
+
+    def below(i):                                   # does anything at an index < i need a gradient?
+        return any(need[:i])
+
+    for l in range(layers - 1, -1, -1):
+        b = 5 + 16 * l
+        sv = saved_layers[l]
+        _, _, _, _, _, _, aow, _, g1, _, iw, _, ow, _, g2, _ = params[b:b + 16]
+        s_attn, s_ao, s_out = s_layers[l]
+        I = iw.shape[0]
+        ds2, g[b + 14], g[b + 15] = text_clap_resln_backward(dh, sv["xhat2"], sv["rstd2"], g2, need[b + 14], need[b + 15],
+                                                             outs[b + 14], outs[b + 15])
+        df2 = _clap_dropout(ds2, p_hidden, s_out, backward=True)
+        if need[b + 12]:
+            g[b + 12] = gemm(df2, sv["f"], D, I, M, transA=True, lda=D, out=outs[b + 12])
+        if need[b + 13]:
+            g[b + 13] = colsum(df2, M, D, out=outs[b + 13])
+        if not below(b + 12):
+            return None
+        du = text_clap_gelu_backward(sv["u"], gemm(df2, ow, M, I, D))
+        if need[b + 10]:
+            g[b + 10] = gemm(du, sv["h1"], I, D, M, transA=True, lda=I, out=outs[b + 10])
+        if need[b + 11]:
+            g[b + 11] = colsum(du, M, I, out=outs[b + 11])
+        if not below(b + 10):
+            return None
+        dh1 = gemm(du, iw, M, D, I, out=ds2, accumulate=True)                           # + the residual branch (df2 is spent)
+        ds1, g[b + 8], g[b + 9] = text_clap_resln_backward(dh1, sv["xhat1"], sv["rstd1"], g1, need[b + 8], need[b + 9],
+                                                           outs[b + 8], outs[b + 9])
+        if not below(b + 8):
+            return None
+        da = _clap_dropout(ds1, p_hidden, s_ao, backward=True)
+        if need[b + 6]:
+            g[b + 6] = gemm(da, sv["ctx"], D, D, M, transA=True, lda=D, out=outs[b + 6])
+        if need[b + 7]:
+            g[b + 7] = colsum(da, M, D, out=outs[b + 7])
+        if not below(b + 6):
+            return None
+        dctx = gemm(da, aow, M, D, D)
+        dqkv = text_selfattn_core_backward(sv["qkv"].view(R, L, 3 * D), sv["attn"], dctx.view(R, L, D), klen, heads,
+                                           p_attn, s_attn).view(M, 3 * D)
+        for j in range(3):
+            if need[b + 2 * j]:
+                g[b + 2 * j] = gemm(dqkv[:, j * D:], sv["x"], D, D, M, transA=True, lda=3 * D, out=outs[b + 2 * j])
+            if need[b + 2 * j + 1]:
+                g[b + 2 * j + 1] = colsum(dqkv[:, j * D:], M, D, ld=3 * D, out=outs[b + 2 * j + 1])
+        if not below(b):
+            return None
+        dh = gemm(dqkv, sv["wqkv"], M, D, 3 * D, out=ds1, accumulate=True)              # + the residual branch (da is spent)
+    return dh
+
+
 def text_clap_forward(ids, mask, params, heads, eps, pad_id, need_grad, p_hidden=0.0, p_attn=0.0, seed=0):
     """LaionClapEncoder.forward (models/text_encoder.py:320-327) over Hugging Face's ClapTextModel + ClapProjectionLayer:
     ids, mask (R, L) int64 on the device, mask a right-padded prefix (only its row sums are read: klen = mask.sum(-1), a row
@@ -1496,26 +1581,7 @@ def text_clap_forward(ids, mask, params, heads, eps, pad_id, need_grad, p_hidden
     h, pos_ids, xhat0, rstd0 = text_clap_embed_forward(ids, word, type0, pos, g0, b0, eps, pad_id, need_grad)
     h = _clap_dropout(h, p_hidden, s_emb)
     buf = h.new_empty(M + R, D)                       # the last layer's rows, then the pooled rows: ONE projection over both
-    saved = []
-    for l in range(layers):
-        b = 5 + 16 * l
-        qw, qb, kw, kb, vw, vb, aow, aob, g1, b1, iw, ib, ow, ob, g2, b2 = params[b:b + 16]
-        s_attn, s_ao, s_out = s_layers[l]
-        I = iw.shape[0]
-        wqkv, bqkv = torch.cat((qw, kw, vw), 0), torch.cat((qb, kb, vb), 0)
-        qkv = gemm(h, wqkv, M, 3 * D, D, transB=True, bias=bqkv)
-        ctx, attn = text_selfattn_core(qkv.view(R, L, 3 * D), klen, heads, need_grad, p_attn, s_attn)
-        ctx = ctx.view(M, D)
-        a = _clap_dropout(gemm(ctx, aow, M, D, D, transB=True, bias=aob), p_hidden, s_ao)
-        h1, xhat1, rstd1 = text_clap_resln_forward(a, h, g1, b1, eps, need_grad)
-        u = gemm(h1, iw, M, I, D, transB=True, bias=ib)      # no fused activation: the backward reads the pre-activation
-        f = text_clap_gelu_forward(u)
-        f2 = _clap_dropout(gemm(f, ow, M, D, I, transB=True, bias=ob), p_hidden, s_out)
-        hn, xhat2, rstd2 = text_clap_resln_forward(f2, h1, g2, b2, eps, need_grad, out=buf[:M] if l == layers - 1 else None)
-        if need_grad:
-            saved.append(dict(x=h, qkv=qkv, attn=attn, ctx=ctx, xhat1=xhat1, rstd1=rstd1, h1=h1, u=u, f=f, xhat2=xhat2, rstd2=rstd2,
-                              wqkv=wqkv))
-        h = hn
+    h, saved = _text_stack_forward(h, klen, params, layers, R, L, heads, eps, need_grad, p_hidden, p_attn, s_layers, buf[:M])
     pw, pb, w1, c1, w2, c2 = params[-6:]
     P = w1.shape[0]
     gemm(buf, pw, R, D, D, transB=True, lda=L * D, bias=pb, act=4, out=buf[M:])         # tanh(dense(h[:, 0]))
@@ -1581,54 +1647,211 @@ def text_clap_backward(dtok, dseq, ids, saved, params, heads, pad_id, p_hidden=0
         return g
     gemm(dpre, pw, R, D, D, out=dbuf, ldc=L * D, accumulate=True)                       # into the rows h[:, 0]
     dh = dbuf[:M]
-    for l in range(layers - 1, -1, -1):
-        b = 5 + 16 * l
-        sv = saved["layers"][l]
-        _, _, _, _, _, _, aow, _, g1, _, iw, _, ow, _, g2, _ = params[b:b + 16]
-        s_attn, s_ao, s_out = s_layers[l]
-        I = iw.shape[0]
-        ds2, g[b + 14], g[b + 15] = text_clap_resln_backward(dh, sv["xhat2"], sv["rstd2"], g2, need[b + 14], need[b + 15],
-                                                             outs[b + 14], outs[b + 15])
-        df2 = _clap_dropout(ds2, p_hidden, s_out, backward=True)
-        if need[b + 12]:
-            g[b + 12] = gemm(df2, sv["f"], D, I, M, transA=True, lda=D, out=outs[b + 12])
-        if need[b + 13]:
-            g[b + 13] = colsum(df2, M, D, out=outs[b + 13])
-        if not below(b + 12):
-            return g
-        du = text_clap_gelu_backward(sv["u"], gemm(df2, ow, M, I, D))
-        if need[b + 10]:
-            g[b + 10] = gemm(du, sv["h1"], I, D, M, transA=True, lda=I, out=outs[b + 10])
-        if need[b + 11]:
-            g[b + 11] = colsum(du, M, I, out=outs[b + 11])
-        if not below(b + 10):
-            return g
-        dh1 = gemm(du, iw, M, D, I, out=ds2, accumulate=True)                           # + the residual branch (df2 is spent)
-        ds1, g[b + 8], g[b + 9] = text_clap_resln_backward(dh1, sv["xhat1"], sv["rstd1"], g1, need[b + 8], need[b + 9],
-                                                           outs[b + 8], outs[b + 9])
-        if not below(b + 8):
-            return g
-        da = _clap_dropout(ds1, p_hidden, s_ao, backward=True)
-        if need[b + 6]:
-            g[b + 6] = gemm(da, sv["ctx"], D, D, M, transA=True, lda=D, out=outs[b + 6])
-        if need[b + 7]:
-            g[b + 7] = colsum(da, M, D, out=outs[b + 7])
-        if not below(b + 6):
-            return g
-        dctx = gemm(da, aow, M, D, D)
-        dqkv = text_selfattn_core_backward(sv["qkv"].view(R, L, 3 * D), sv["attn"], dctx.view(R, L, D), saved["klen"], heads,
-                                           p_attn, s_attn).view(M, 3 * D)
-        for j in range(3):
-            if need[b + 2 * j]:
-                g[b + 2 * j] = gemm(dqkv[:, j * D:], sv["x"], D, D, M, transA=True, lda=3 * D, out=outs[b + 2 * j])
-            if need[b + 2 * j + 1]:
-                g[b + 2 * j + 1] = colsum(dqkv[:, j * D:], M, D, ld=3 * D, out=outs[b + 2 * j + 1])
-        if not below(b):
-            return g
-        dh = gemm(dqkv, sv["wqkv"], M, D, 3 * D, out=ds1, accumulate=True)              # + the residual branch (da is spent)
+    dh = _text_stack_backward(dh, saved["layers"], saved["klen"], params, layers, R, L, heads, p_hidden, p_attn, s_layers, need, outs, g)
+    if dh is None:
+        return g
     dh0 = _clap_dropout(dh, p_hidden, s_emb, backward=True)
     g[:5] = text_clap_embed_backward(dh0, saved["xhat0"], saved["rstd0"], params[3], ids, saved["pos_ids"], params[0].shape[0],
                                      params[2].shape[0], pad_id, need[:5], outs[:5])
+    return g
+
+
+# ------------------------------------------------------------------------------------------------
+# BERT for training (row T7; models/text_encoder.py:271-308 Bert / SentenceBert over Hugging Face's BertModel): BertEmbeddings
+# (token types, absolute positions) and the sentence poolings of csrc/text_bert.hip around the encoder stack of the CLAP tower
+# ------------------------------------------------------------------------------------------------
+TEXT_BERT_POOLER = ("model.pooler.dense.weight", "model.pooler.dense.bias")
+TEXT_BERT_SAVED_HEAD = ("klen", "xhat0", "rstd0", "raw")
+TEXT_BERT_POOL_MODES = {"cls": 0, "mean": 1}
+TEXT_BERT_NORMS = {"none": 0, "normalize": 1, "retrieval": 2}
+TEXT_BERT_MAX_TYPES = 16
+
+
+def text_bert_param_names(layers, pooler=True):
+    """State-dict names of Bert's / SentenceBert's parameters in the order the operator takes them: 5 of the embedding block, 16
+    per layer, then (pooler) BertPooler's two -- held for checkpoint compatibility, they take no part in the arithmetic."""
+    return (["model." + n for n in TEXT_CLAP_HEAD]
+            + [f"model.encoder.layer.{l}.{n}" for l in range(layers) for n in TEXT_CLAP_LAYER]
+            + (list(TEXT_BERT_POOLER) if pooler else []))
+
+
+def text_bert_layers(n_params):
+    """-> (layers, pooler parameters present) from the number of parameters."""
+    rest = n_params - len(TEXT_CLAP_HEAD)
+    layers, tail = divmod(rest, len(TEXT_CLAP_LAYER))
+    if layers < 1 or tail not in (0, 2):
+        raise ValueError(f"text_bert: {n_params} parameters are not 5 + 16 per layer (>= 1 layer) (+ 2 of the pooler)")
+    return layers, tail == 2
+
+
+def text_bert_check(D, heads, L=None, P=None, T=None, pool_mode=None, norm=None, need_grad=False):
+    """The domain of the BERT path, raised before any launch with the limit named: the tower's limits (text_clap_check), L within
+    the position table, at most 16 token types, a known pooling / normalisation, and no backward through normalisation 2."""
+    try:
+        text_selfattn_check(D, heads)
+    except NotImplementedError as e:                # one exception type for every limit of this path
+        raise ValueError(str(e)) from None
+    if L is not None and not 2 <= L <= TEXT_CLAP_MAX_L:
+        raise ValueError(f"text_bert: {L} tokens per phrase; the attention kernel serves 2 ... {TEXT_CLAP_MAX_L} tokens and there is "
+                         "no eager fallback")
+    if L is not None and P is not None and L > P:
+        raise ValueError(f"text_bert: {L} tokens per phrase but max_position_embeddings is {P}")
+    if T is not None and not 1 <= T <= TEXT_BERT_MAX_TYPES:
+        raise ValueError(f"text_bert: type_vocab_size {T}; the token-type gradient serves 1 ... {TEXT_BERT_MAX_TYPES} types")
+    if pool_mode is not None and pool_mode not in (0, 1):
+        raise ValueError(f"text_bert: pooling mode {pool_mode!r}; 0 ([CLS]) and 1 (masked mean) exist")
+    if norm is not None and norm not in (0, 1, 2):
+        raise ValueError(f"text_bert: normalisation {norm!r}; 0 (none), 1 (F.normalize) and 2 (x / (|x| + 1e-7), clipped) exist")
+    if norm == 2 and need_grad:
+        raise ValueError("text_bert: normalisation 2 (the retrieval model's) is forward-only")
+
+
+def text_bert_embed_forward(ids, type_ids, word, type_tab, pos, gamma, beta, eps, need_state=True):
+    """BertEmbeddings: ids, type_ids (B, L) int64 (type_ids None = all zeros) -> h (B*L, D) = LayerNorm(word[ids] + type[type_ids]
+    + pos[column]), xhat (B*L, D), rstd (B*L) (None unless need_state)."""
+    ids = _clap_ids_chk(ids, "input_ids")
+    type_ids = _clap_ids_chk(type_ids, "token_type_ids") if type_ids is not None else None
+    B, L = ids.shape
+    word, type_tab, pos = _chk(word, "word_embeddings"), _chk(type_tab, "token_type_embeddings"), _chk(pos, "position_embeddings")
+    V, D = word.shape
+    T, P = type_tab.shape[0], pos.shape[0]
+    if L > P:
+        raise ValueError(f"text_bert: {L} tokens per phrase but the position table has {P} rows")
+    if type_ids is not None and tuple(type_ids.shape) != (B, L):
+        raise ValueError(f"text_bert: token_type_ids {tuple(type_ids.shape)} and input_ids {(B, L)} differ in shape")
+    M = B * L
+    h = _empty(M, D, like=word)
+    xhat = _empty(M, D, like=word) if need_state else None
+    rstd = _empty(M, like=word) if need_state else None
+    call("tag_embed_check_ids", ptr(ids), M, V, ptr(_embed_flag(word)))       # nn.Embedding raises; see check_async_errors
+    if type_ids is not None:
+        call("tag_embed_check_ids", ptr(type_ids), M, T, ptr(_embed_flag(word)))
+    call("tag_text_bert_embed_forward", ptr(ids), ptr(type_ids), ptr(word), ptr(type_tab), ptr(pos), ptr(_chk(gamma, "gamma")),
+         ptr(_chk(beta, "beta")), float(eps), ptr(h), ptr(xhat), ptr(rstd), B, L, D, V, T, P)
+    return h, xhat, rstd
+
+
+def text_bert_embed_backward(dh, xhat, rstd, gamma, ids, type_ids, V, T, P, pad_id, need=None, outs=None):
+    """dh (B*L, D) -> [dword (V, D), dtype (T, D), dpos (P, D), dgamma (D), dbeta (D)] (None where need[i] is False).  outs:
+    optional destination per gradient; the table destinations must be ZEROED (the flat-gradient rows after zero_grad): dword is
+    accumulated by the gather and only the first L rows of dpos are written.  Row pad_id of dword receives exactly zero (pad_id
+    None / negative: no padding index); padded positions DO contribute to dtype and dpos, as in Hugging Face."""
+    dh = _chk(dh, "grad")
+    ids = _clap_ids_chk(ids, "input_ids")
+    type_ids = _clap_ids_chk(type_ids, "token_type_ids") if type_ids is not None else None
+    B, L = ids.shape
+    D = dh.shape[-1]
+    need = list(need) if need is not None else [True] * 5
+    outs = list(outs) if outs is not None else [None] * 5
+    if not any(need):
+        return [None] * 5
+    shapes = ((V, D), (T, D), (P, D), (D,), (D,))
+    g = [None] * 5
+    for i in range(5):
+        if need[i]:
+            g[i] = outs[i] if outs[i] is not None else (torch.zeros if i in (0, 2) else torch.empty)(
+                shapes[i], device=dh.device, dtype=F32)
+    ws = _ws(query("tag_text_bert_embed_backward_ws_bytes", B, L, D, T), dh)
+    call("tag_text_bert_embed_backward", ptr(dh), ptr(_chk(xhat, "xhat")), ptr(_chk(rstd, "rstd")), ptr(_chk(gamma, "gamma")),
+         ptr(ids), ptr(type_ids), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), ptr(g[4]), B, L, D, V, T, P,
+         -1 if pad_id is None else int(pad_id), ptr(ws))
+    return g
+
+
+def text_bert_pool_forward(h, klen, mode, norm, need_raw=False):
+    """h (R, L, D), klen (R) int64 -> seq (R, D), raw (R, D) or None: the sentence pooling (0 [CLS], 1 masked mean over the first
+    klen rows) and normalisation (0 none, 1 F.normalize, 2 x / (|x| + 1e-7) clipped to +-1e3) in one pass."""
+    h = _chk(h, "h")
+    R, L, D = h.shape
+    if mode not in (0, 1) or norm not in (0, 1, 2):
+        raise ValueError(f"text_bert: pooling mode {mode!r} / normalisation {norm!r}")
+    if klen is None and mode == 1:
+        raise ValueError("text_bert: the masked mean needs klen")
+    klen = _klen_chk(klen, R) if klen is not None else None
+    out = _empty(R, D, like=h)
+    raw = _empty(R, D, like=h) if need_raw else None
+    call("tag_text_bert_pool_forward", ptr(h), ptr(klen), int(mode), int(norm), ptr(raw), ptr(out), R, L, D)
+    return out, raw
+
+
+def text_bert_pool_backward(dseq, dtok, raw, klen, mode, norm, shape):
+    """-> dh (R, L, D) = dtok (or zero) + the pooling's gradient of dseq (R, D) (or nothing) on row 0 / the first klen rows,
+    through the F.normalize backward when norm is 1 (raw: the forward's pooled rows)."""
+    R, L, D = shape
+    if norm not in (0, 1):
+        raise ValueError("text_bert: normalisation 2 (the retrieval model's) is forward-only")
+    if mode not in (0, 1):
+        raise ValueError(f"text_bert: pooling mode {mode!r}")
+    if dseq is None and dtok is None:
+        raise ValueError("text_bert_pool_backward: neither dseq nor dtok")
+    like = dseq if dseq is not None else dtok
+    dseq = _chk(dseq, "grad") if dseq is not None else None
+    dtok = _chk(dtok, "grad") if dtok is not None else None
+    if klen is None and mode == 1:
+        raise ValueError("text_bert: the masked mean needs klen")
+    klen = _klen_chk(klen, R) if klen is not None else None
+    dh = _empty(R, L, D, like=like)
+    call("tag_text_bert_pool_backward", ptr(dseq), ptr(dtok), ptr(_chk(raw, "raw")) if norm == 1 else None, ptr(klen), int(mode),
+         int(norm), ptr(dh), R, L, D)
+    return dh
+
+
+def text_bert_forward(ids, type_ids, mask, params, heads, eps, pad_id, pool_mode, norm, need_grad, p_hidden=0.0, p_attn=0.0,
+                      seed=0):
+    """Bert.forward / SentenceBert.forward (models/text_encoder.py:281-308) over Hugging Face's BertModel: ids, mask (R, L) int64 on
+    the device, type_ids the same or None (all zeros), mask a right-padded prefix (only its row sums are read, as in
+    text_clap_forward); params in the order of text_bert_param_names (with or without the pooler's two, which are not read).
+    pool_mode 0 [CLS] / 1 masked mean, norm 0 none / 1 F.normalize / 2 the retrieval model's (forward-only).  Dropout sites and
+    seeds are text_clap_dropout_seeds'.  -> token_emb (R, L, D) the last hidden state, seq_emb (R, D), saved state or None."""
+    ids, mask = _clap_ids_chk(ids, "input_ids"), _clap_ids_chk(mask, "attention_mask")
+    R, L = ids.shape
+    layers, _ = text_bert_layers(len(params))
+    params = [_chk(p, "parameter") for p in params]
+    word, type_tab, pos, g0, b0 = params[:5]
+    D = word.shape[1]
+    text_bert_check(D, heads, L, pos.shape[0], type_tab.shape[0], pool_mode, norm, need_grad)
+    klen = mask.sum(-1)
+    s_emb, s_layers = text_clap_dropout_seeds(seed, layers)
+    h, xhat0, rstd0 = text_bert_embed_forward(ids, type_ids, word, type_tab, pos, g0, b0, eps, need_grad)
+    h = _clap_dropout(h, p_hidden, s_emb)
+    h, saved = _text_stack_forward(h, klen, params, layers, R, L, heads, eps, need_grad, p_hidden, p_attn, s_layers)
+    tok = h.view(R, L, D)
+    seq, raw = text_bert_pool_forward(tok, klen, pool_mode, norm, need_grad and norm == 1)
+    state = None
+    if need_grad:
+        state = dict(klen=klen, xhat0=xhat0, rstd0=rstd0, raw=raw if raw is not None else seq, layers=saved)
+    return tok, seq, state
+
+
+def text_bert_backward(dtok, dseq, ids, type_ids, saved, params, heads, pad_id, pool_mode, norm, p_hidden=0.0, p_attn=0.0, seed=0,
+                       outs=None, need=None):
+    """-> one gradient per parameter (text_bert_param_names order; the pooler's stay None).  dtok (R, L, D) / dseq (R, D): either
+    may be None.  outs / need: as in text_clap_backward -- destinations written directly (the embedding tables' must be zeroed) and
+    per-parameter switches; the walk stops below the lowest parameter that needs a gradient."""
+    n = len(params)
+    layers, pooler = text_bert_layers(n)
+    params = [_chk(p, "parameter") for p in params]
+    outs = list(outs) if outs is not None else [None] * n
+    need = list(need) if need is not None else [True] * n
+    if pooler:
+        need[-2:] = [False, False]                  # BertPooler takes no part in the arithmetic
+    g = [None] * n
+    if not any(need) or (dtok is None and dseq is None):
+        return g
+    R, L = ids.shape
+    D = params[0].shape[1]
+    M = R * L
+    s_emb, s_layers = text_clap_dropout_seeds(seed, layers)
+    if dseq is None:
+        dh = _chk(dtok, "grad").view(M, D)
+    else:
+        dh = text_bert_pool_backward(dseq, dtok, saved["raw"], saved["klen"], pool_mode, norm, (R, L, D)).view(M, D)
+    dh = _text_stack_backward(dh, saved["layers"], saved["klen"], params, layers, R, L, heads, p_hidden, p_attn, s_layers, need, outs, g)
+    if dh is None:
+        return g
+    dh0 = _clap_dropout(dh, p_hidden, s_emb, backward=True)
+    g[:5] = text_bert_embed_backward(dh0, saved["xhat0"], saved["rstd0"], params[3], ids, type_ids, params[0].shape[0],
+                                     params[1].shape[0], params[2].shape[0], pad_id, need[:5], outs[:5])
     return g
 
 

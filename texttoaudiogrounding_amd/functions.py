@@ -35,6 +35,7 @@ from .dispatch import (bias_bnrelu_backward, bias_bnrelu_forward, bias_bnrelu_po
 from .dispatch import class_pool_forward, tagging_head_dlogit
 from .dispatch import text_gru_backward, text_gru_forward
 from .dispatch import text_selfattn_backward, text_selfattn_forward
+from .dispatch import text_bert_backward, text_bert_forward
 from .dispatch import text_clap_backward, text_clap_forward
 from .dispatch import text_intra_backward, text_intra_forward
 from . import engine
@@ -1005,6 +1006,46 @@ class TextClapFunction(TagFunction):
         grads = [None] * n
         for i in range(n):
             if need[i]:
+                _deliver(grads, sk, i, g[i] if sk[i] is not None else g[i].view(ctx.shapes[i]))
+        _ready(ctx.params)
+        return (*([None] * k), *grads)
+
+
+class TextBertFunction(TagFunction):
+    """torch.ops.tag.text_bert with direct gradients (StrongRunner / WeakPhraseRunner): Bert / SentenceBert
+    (models/text_encoder.py:271-308) whose parameter gradients go straight into their flat-gradient views -- the embedding tables'
+    rows into the zeroed flat buffer, like TextClapFunction's; a parameter with requires_grad = False costs no GEMM / column sum
+    and the walk stops below the lowest trainable parameter.  The pooler's two parameters (when passed) receive no gradient and
+    their flat-gradient rows are not touched.  Same kernels as the operator."""
+
+    N_ARGS = 11                                         # arguments in front of the parameters
+
+    @staticmethod
+    def forward(ctx, input_ids, token_type_ids, attention_mask, heads, eps, pad_id, pool_mode, norm, p_hidden, p_attn, seed, *params):
+        need = engine._RECORDING and any(ctx.needs_input_grad)
+        tok, seq, saved = text_bert_forward(input_ids, token_type_ids, attention_mask, [p.detach() for p in params], heads, eps,
+                                            pad_id, pool_mode, norm, need, p_hidden, p_attn, seed)
+        ctx.tb = (saved, input_ids, token_type_ids, heads, pad_id, pool_mode, norm, p_hidden, p_attn, seed)
+        ctx.weights = [p.detach() for p in params] if need else None
+        ctx.shapes = [tuple(p.shape) for p in params]
+        ctx.sinks = _sinks(list(params))
+        ctx.params = list(params) if cfg.DIRECT_GRADS else None
+        ctx.set_materialize_grads(False)
+        return tok, seq
+
+    @staticmethod
+    def backward(ctx, dtok, dseq):
+        saved, input_ids, type_ids, heads, pad_id, pool_mode, norm, p_hidden, p_attn, seed = ctx.tb
+        k = TextBertFunction.N_ARGS
+        sk, need = ctx.sinks, list(ctx.needs_input_grad[k:])
+        n = len(need)
+        if (dtok is None and dseq is None) or saved is None:
+            return (None,) * (k + n)
+        g = text_bert_backward(dtok, dseq, input_ids, type_ids, saved, ctx.weights, heads, pad_id, pool_mode, norm, p_hidden, p_attn,
+                               seed, outs=[sk[i] for i in range(n)], need=need)
+        grads = [None] * n
+        for i in range(n):
+            if need[i] and g[i] is not None:
                 _deliver(grads, sk, i, g[i] if sk[i] is not None else g[i].view(ctx.shapes[i]))
         _ready(ctx.params)
         return (*([None] * k), *grads)

@@ -147,6 +147,11 @@ _SIGS = {
     "tag_text_clap_gelu_forward": (c_int, [P, P, c_long, P]),
     "tag_text_clap_gelu_backward": (c_int, [P, P, P, c_long, P]),
     "tag_text_clap_tanh_backward": (c_int, [P, P, P, c_long, P]),
+    "tag_text_bert_embed_forward": (c_int, [P] * 7 + [c_float] + [P] * 3 + [c_int] * 6 + [P]),
+    "tag_text_bert_embed_backward_ws_bytes": (c_size_t, [c_int] * 4),
+    "tag_text_bert_embed_backward": (c_int, [P] * 11 + [c_int] * 7 + [P, P]),
+    "tag_text_bert_pool_forward": (c_int, [P, P, c_int, c_int, P, P, c_long, c_int, c_int, P]),
+    "tag_text_bert_pool_backward": (c_int, [P, P, P, P, c_int, c_int, P, c_long, c_int, c_int, P]),
     "tag_embed_mean_forward": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_mean_backward": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "tag_embed_check_ids": (c_int, [P, c_long, c_int, P, P]),

@@ -1,7 +1,11 @@
 """Learned text encoders: the word-embedding bag EmbeddingAgg, the recurrent RnnEncoder, the IntraAttention encoder with its
-ConvGRUCell, the SelfAttention encoder and the trainable LAION-CLAP tower LaionClapEncoder (mirror of
-models/text_encoder.py:14-43,61-268,311-327 in the reference)."""
+ConvGRUCell, the SelfAttention encoder, the BERT encoders Bert and SentenceBert and the trainable LAION-CLAP tower LaionClapEncoder (mirror
+of models/text_encoder.py:14-43,61-327 in the reference)."""
+import json
 import math
+import os
+import warnings
+from collections.abc import Mapping
 from typing import Dict
 
 import numpy as np
@@ -453,3 +457,262 @@ class LaionClapEncoder(nn.Module):
             tok, seq, _ = torch.ops.tag.text_clap(ids, mask, params, heads, eps, pad, p_h, p_a, seed, need)
         lead = shape[:-1]
         return {"seq_emb": seq.view(*lead, seq.shape[-1]), "token_emb": tok.view(*lead, L, tok.shape[-1])}
+
+
+#: BertConfig defaults of "bert-base-uncased"
+BERT_DEFAULTS = dict(vocab_size=30522, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
+                     max_position_embeddings=512, type_vocab_size=2, layer_norm_eps=1e-12, pad_token_id=0,
+                     hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1)
+#: the shape of sentence-transformers/all-MiniLM-L6-v2
+MINILM_DEFAULTS = dict(BERT_DEFAULTS, hidden_size=384, num_hidden_layers=6, intermediate_size=1536)
+_BERT_INDEX_BUFFERS = ("model.embeddings.position_ids", "model.embeddings.token_type_ids")
+
+
+def _bert_model(cfg):
+    """The parameter tree of Hugging Face's ``BertModel`` (names only; the arithmetic is torch.ops.tag.text_bert): the tree of the
+    CLAP text model with BERT's embedding tables -- ``type_vocab_size`` token types, positions WITHOUT a padding index -- and
+    without the two index buffers, which BertModel keeps out of its state dict."""
+    from .hf_modeling_grounding import _text_model
+    m = _text_model(cfg)
+    D = cfg["hidden_size"]
+    emb = m.embeddings
+    emb.token_type_embeddings = nn.Embedding(cfg["type_vocab_size"], D)
+    emb.position_embeddings = nn.Embedding(cfg["max_position_embeddings"], D)
+    del emb._buffers["position_ids"], emb._buffers["token_type_ids"]
+    return m
+
+
+def _local_bert(path):
+    """(configuration entries, state dict under ``model.``) of a ``BertModel`` that resolves locally, else None.  Never touches
+    the network."""
+    if not path:
+        return None
+    try:
+        from transformers import BertModel
+        bert = BertModel.from_pretrained(path, local_files_only=True)
+    except Exception as e:                                  # noqa: BLE001 - not cached / no such directory / no transformers
+        warnings.warn(f"{path!r} did not resolve to a local BertModel ({type(e).__name__}); the model is built from its "
+                      "configuration and RANDOMLY initialised", stacklevel=3)
+        return None
+    hc = bert.config
+    if getattr(hc, "hidden_act", "gelu") != "gelu" or getattr(hc, "position_embedding_type", "absolute") != "absolute":
+        raise ValueError(f"{path}: hidden_act {hc.hidden_act!r} / position_embedding_type "
+                         f"{getattr(hc, 'position_embedding_type', None)!r}; the HIP path serves erf-GELU and absolute positions")
+    cfg = {k: getattr(hc, k) for k in BERT_DEFAULTS}
+    if cfg["pad_token_id"] is None:
+        cfg["pad_token_id"] = 0
+    return cfg, {"model." + k: v for k, v in bert.state_dict().items()}
+
+
+class _BertBase(nn.Module):
+    """What Bert and SentenceBert share: the parameter tree under Hugging Face's ``BertModel`` names as ``self.model``,
+    ``dummy_param`` (models/text_encoder.py:275,300), the input checks and the call of torch.ops.tag.text_bert."""
+
+    MAX_TOKENS = ops.TEXT_CLAP_MAX_L
+
+    def _build(self, defaults, pretrained, config):
+        cfg = dict(defaults)
+        cfg.update(pretrained[0] if pretrained is not None else (config or {}))
+        if cfg["num_hidden_layers"] < 1:
+            raise ValueError(f"{type(self).__name__}: num_hidden_layers must be >= 1")
+        ops.text_bert_check(cfg["hidden_size"], cfg["num_attention_heads"], T=cfg["type_vocab_size"])
+        self.config = cfg
+        self.model = _bert_model(cfg)
+        self.dummy_param = nn.Parameter(torch.zeros(1))
+        self.embed_dim = cfg["hidden_size"]
+        self._names = ops.text_bert_param_names(cfg["num_hidden_layers"], pooler=False)
+        self._register_load_state_dict_pre_hook(self._drop_index_buffers)
+        if pretrained is not None:
+            st = dict(pretrained[1])
+            st["dummy_param"] = self.dummy_param.detach()
+            self.load_state_dict(st, strict=True)
+        else:
+            self._init_weights(self.model)
+
+    @staticmethod
+    def _drop_index_buffers(state_dict, prefix, *_):
+        """Load pre-hook: the ``position_ids`` / ``token_type_ids`` index buffers are optional in checkpoints.  It runs under
+        whatever prefix this module has, so a checkpoint of a whole model loads strictly through the parent as well."""
+        for name in _BERT_INDEX_BUFFERS:
+            state_dict.pop(prefix + name, None)
+
+    @staticmethod
+    def _init_weights(model, std=0.02):
+        """BertPreTrainedModel._init_weights: N(0, 0.02^2) matrices and tables, zero biases, LayerNorm at 1 / 0, a zero pad row."""
+        for m in model.modules():
+            if isinstance(m, (nn.Linear, nn.Embedding)):
+                nn.init.normal_(m.weight, mean=0.0, std=std)
+                if isinstance(m, nn.Linear):
+                    nn.init.zeros_(m.bias)
+                elif m.padding_idx is not None:
+                    with torch.no_grad():
+                        m.weight[m.padding_idx].zero_()
+            elif isinstance(m, nn.LayerNorm):
+                nn.init.ones_(m.weight)
+                nn.init.zeros_(m.bias)
+
+    def _params(self):
+        own = dict(self.named_parameters())
+        return [own[n] for n in self._names]
+
+    def _encode(self, ids, type_ids, mask, pool_mode, norm):
+        """ids / type_ids (or None) / mask of one shape (..., L), any dtype, host or device -> token_emb (..., L, D),
+        seq_emb (..., D), the int64 device mask (..., L)."""
+        name = type(self).__name__
+        shape = tuple(np.shape(ids))
+        L = shape[-1]
+        cfg = self.config
+        if not 2 <= L <= self.MAX_TOKENS:                   # before any launch
+            raise ValueError(f"{name}: {L} tokens per phrase; the attention kernel serves 2 ... {self.MAX_TOKENS} tokens and there "
+                             "is no eager fallback")
+        if L > cfg["max_position_embeddings"]:
+            raise ValueError(f"{name}: {L} tokens per phrase but max_position_embeddings is {cfg['max_position_embeddings']}")
+        for what, t in (("attention_mask", mask), ("token_type_ids", type_ids)):
+            if t is not None and tuple(np.shape(t)) != shape:
+                raise ValueError(f"{name}: input_ids {shape} and {what} {tuple(np.shape(t))} differ in shape")
+        mask = torch.as_tensor(mask)
+        if not mask.is_cuda:
+            m = mask.reshape(-1, L) != 0
+            if bool((m[:, 1:] & ~m[:, :-1]).any()):
+                raise ValueError(f"{name}: attention_mask must be a right-padded prefix (ones, then zeros); the attention kernel "
+                                 "reads only the number of valid keys per row")
+        table = self.model.embeddings.word_embeddings.weight
+        if type_ids is not None:
+            type_ids = torch.as_tensor(type_ids)
+            if not type_ids.is_cuda and type_ids.numel():
+                lo, hi = int(type_ids.min()), int(type_ids.max())
+                if lo < 0 or hi >= cfg["type_vocab_size"]:
+                    raise ValueError(f"{name}: token_type_ids span [{lo}, {hi}], type_vocab_size is {cfg['type_vocab_size']}")
+            type_ids = type_ids.long().to(table.device).reshape(-1, L).contiguous()
+        ids = _ids_to_device(ids, table).reshape(-1, L)
+        mask = mask.long().to(table.device).reshape(-1, L).contiguous()
+        params = self._params()
+        p_h = float(cfg["hidden_dropout_prob"]) if self.training else 0.0
+        p_a = float(cfg["attention_probs_dropout_prob"]) if self.training else 0.0
+        seed = ops.new_seed() if (p_h > 0.0 or p_a > 0.0) else 0
+        heads, eps, pad = int(cfg["num_attention_heads"]), float(cfg["layer_norm_eps"]), int(cfg["pad_token_id"])
+        if ops.DIRECT_GRADS:
+            tok, seq = ops.TextBertFunction.apply(ids, type_ids, mask, heads, eps, pad, pool_mode, norm, p_h, p_a, seed, *params)
+        else:
+            need = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+            tok, seq, _ = torch.ops.tag.text_bert(ids, type_ids, mask, params, heads, eps, pad, pool_mode, norm, p_h, p_a, seed, need)
+        lead = shape[:-1]
+        return tok.view(*lead, L, tok.shape[-1]), seq.view(*lead, seq.shape[-1]), mask.view(shape)
+
+
+class Bert(_BertBase):
+    """models/text_encoder.py:271-293: Hugging Face ``BertModel`` with ``[CLS]`` pooling, TRAINABLE on the HIP text tower.
+    ``forward(input_dict)`` reads ``input_ids``, ``token_type_ids`` and ``attention_mask`` -- any leading shape (flattened like the
+    other text encoders), any dtype (the reference's runner stages them as float, hence its ``.long()``) -- and returns ``seq_emb``
+    = ``last_hidden_state[:, 0]`` (..., D), ``token_emb`` = ``last_hidden_state`` (..., L, D) and ``attention_mask``.
+
+    ``self.model`` only HOLDS the parameters, under ``BertModel``'s names (``model.embeddings.*``, ``model.encoder.layer.N.*``,
+    ``model.pooler.dense.*``), next to ``dummy_param``: a reference checkpoint loads with ``load_state_dict(strict=True)``; the
+    ``position_ids`` / ``token_type_ids`` index buffers are optional there.  The arithmetic runs in ``torch.ops.tag.text_bert``:
+    BertEmbeddings and the pooling in csrc/text_bert.hip, the encoder stack shared with LaionClapEncoder.  The pooler and
+    ``dummy_param`` take no part in it and receive no gradient.
+
+    ``model_name``: a directory or a name that resolves WITHOUT the network (``local_files_only=True``) -- its weights and
+    configuration are copied; otherwise (with a warning when a name was given) the model is built from ``BERT_DEFAULTS`` (BERT-base)
+    updated by ``config`` and initialised as ``BertPreTrainedModel`` does (N(0, 0.02^2), LayerNorm 1 / 0).  ``embed_dim`` = ``hidden_size``.
+
+    Limits (ValueError before any launch, there is no eager fallback): 2 <= L <= 64 tokens and L <= max_position_embeddings;
+    head_dim 16, 32 or a multiple of 64; hidden_size <= 1024; at most 16 token types; erf-GELU and absolute positions;
+    ``attention_mask`` a right-padded PREFIX (a host-resident mask is checked, a device-resident one is trusted); host-resident
+    ``token_type_ids`` outside the table raise ValueError, device-resident ones are clamped and raise the sticky flag of
+    ``ops.check_async_errors``.  Dropout (train mode): Hugging Face's four sites with the project's counter-based keep masks, as in
+    LaionClapEncoder."""
+
+    def __init__(self, model_name: str = None, config: dict = None):
+        super().__init__()
+        self.model_name = model_name
+        self._build(BERT_DEFAULTS, _local_bert(model_name), config)
+
+    def load_pretrained(self, pretrained, output_fn):       # models/text_encoder.py:278-279
+        pass
+
+    def forward(self, input_dict: Dict):
+        tok, seq, mask = self._encode(input_dict["input_ids"], input_dict["token_type_ids"], input_dict["attention_mask"],
+                                      ops.TEXT_BERT_POOL_MODES["cls"], ops.TEXT_BERT_NORMS["none"])
+        return {"seq_emb": seq, "token_emb": tok, "attention_mask": mask}
+
+
+class SentenceBert(_BertBase):
+    """models/text_encoder.py:296-308: a sentence-transformers BERT model -- transformer, ``Pooling`` (mean or cls), optional
+    ``Normalize`` -- TRAINABLE on the HIP text tower, WITHOUT the ``sentence_transformers`` package.
+
+    ``model_type``: a LOCAL sentence-transformers directory: the transformer at its root or under ``0_Transformer/``, the pooling
+    choice from ``1_Pooling/config.json`` (any mode but mean / cls raises ValueError), a ``Normalize`` entry from ``modules.json``,
+    ``max_seq_length`` from ``sentence_bert_config.json``.  Without a directory the model is built from ``MINILM_DEFAULTS``
+    (all-MiniLM-L6-v2's shape) updated by ``config``, with ``pooling`` / ``normalize`` as given, initialised as in ``Bert`` (with a
+    warning when a name was given).
+
+    ``forward(text)``: a list of strings is tokenised with the directory's tokenizer (``self.tokenizer``, which can be injected),
+    padded to the batch's longest phrase and truncated at ``min(max_seq_length, 64)``; a dict with ``input_ids`` /
+    ``attention_mask`` (and ``token_type_ids`` if present) is accepted as well, so that the class also works inside ``BiEncoder``.
+    -> ``seq_emb`` pooled and normalised as configured, ``token_emb`` the last hidden state.  Limits and dropout as in ``Bert``.
+    Parity with the ``sentence_transformers`` package itself is NOT pinned by a test (the package is not a dependency)."""
+
+    def __init__(self, model_type: str = None, config: dict = None, pooling: str = "mean", normalize: bool = True):
+        super().__init__()
+        self.model_type = model_type
+        self.max_seq_length = self.MAX_TOKENS
+        self.tokenizer = None
+        self._tokenizer_dir = None
+        pretrained = None
+        if model_type and os.path.isdir(model_type):
+            pooling, normalize, self.max_seq_length, root = self._read_directory(model_type)
+            pretrained = _local_bert(root)
+            if pretrained is None:
+                raise ValueError(f"SentenceBert: no BERT transformer could be read from {root}")
+            self._tokenizer_dir = root
+        elif model_type:
+            warnings.warn(f"{model_type!r} is not a local sentence-transformers directory; the model is built from its "
+                          "configuration and RANDOMLY initialised", stacklevel=2)
+        if pooling not in ops.TEXT_BERT_POOL_MODES:
+            raise ValueError(f"SentenceBert: pooling {pooling!r}; 'mean' and 'cls' exist")
+        self.pooling, self.normalize = pooling, bool(normalize)
+        self._build(MINILM_DEFAULTS, pretrained, config)
+
+    @staticmethod
+    def _read_directory(path):
+        """-> (pooling, normalize, max_seq_length, the transformer's directory) of a sentence-transformers directory."""
+        def read(*parts):
+            f = os.path.join(path, *parts)
+            if not os.path.isfile(f):
+                return None
+            with open(f) as fh:
+                return json.load(fh)
+        modules = read("modules.json") or []
+        kinds = {str(m.get("type", "")).rsplit(".", 1)[-1]: m.get("path", "") for m in modules}
+        root = os.path.join(path, kinds.get("Transformer", "")) if kinds.get("Transformer") else path
+        if not os.path.isfile(os.path.join(root, "config.json")) and os.path.isfile(os.path.join(path, "0_Transformer", "config.json")):
+            root = os.path.join(path, "0_Transformer")
+        pool = read(kinds.get("Pooling") or "1_Pooling", "config.json") or {"pooling_mode_mean_tokens": True}
+        on = sorted(k[len("pooling_mode_"):] for k, v in pool.items() if k.startswith("pooling_mode_") and v is True)
+        if on == ["mean_tokens"]:
+            pooling = "mean"
+        elif on == ["cls_token"]:
+            pooling = "cls"
+        else:
+            raise ValueError(f"SentenceBert: pooling modes {on} of {path}; exactly one of mean_tokens / cls_token is served")
+        sb = {}
+        for d in (root, path):
+            sb = sb or read(os.path.relpath(d, path), "sentence_bert_config.json") or {}
+        return pooling, "Normalize" in kinds, int(sb.get("max_seq_length") or SentenceBert.MAX_TOKENS), root
+
+    def _tokenize(self, text):
+        if self.tokenizer is None:
+            if self._tokenizer_dir is None:
+                raise RuntimeError("SentenceBert: strings need a tokenizer; none came with the model (set .tokenizer)")
+            from transformers import AutoTokenizer
+            self.tokenizer = AutoTokenizer.from_pretrained(self._tokenizer_dir, local_files_only=True)
+        return self.tokenizer(list(text), padding=True, truncation=True, max_length=min(self.max_seq_length, self.MAX_TOKENS),
+                              return_tensors="pt")
+
+    def forward(self, text):
+        tokens = text if isinstance(text, Mapping) else self._tokenize(text)
+        norm = ops.TEXT_BERT_NORMS["normalize" if self.normalize else "none"]
+        tok, seq, _ = self._encode(tokens["input_ids"], tokens.get("token_type_ids"), tokens["attention_mask"],
+                                   ops.TEXT_BERT_POOL_MODES[self.pooling], norm)
+        return {"seq_emb": seq, "token_emb": tok}

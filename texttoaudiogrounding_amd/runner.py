@@ -22,7 +22,7 @@ from .utils.train_util import init_obj_from_str
 
 #: batch entries that hold token ids or masks (DictTokenizer's ``text``, HuggingFaceTokenizer's ``input_ids`` / ``attention_mask``):
 #: staged as int64; every other tensor is cast to fp32
-_INT64_KEYS = ("text", "input_ids", "attention_mask")
+_INT64_KEYS = ("text", "input_ids", "token_type_ids", "attention_mask")
 
 
 def build_model(model_cfg: Dict):

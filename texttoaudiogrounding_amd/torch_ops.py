@@ -556,6 +556,105 @@ def _tcl_backward(ctx, dtok, dseq, _dsaved):
 register_autograd("tag::text_clap", _tcl_backward, setup_context=_tcl_setup)
 
 
+# ------------------------------------------------------------------------------------------------ T7 BERT / SentenceBert
+_TBT_HEAD = _dispatch.TEXT_BERT_SAVED_HEAD
+
+
+def _tbt_saved(saved, params, layers):
+    """The state ops.text_bert_backward expects, from what the operator returned: four tensors of the embedding block and the
+    pooling, then eleven per layer; the packed q|k|v weights are formed again from the three parameters."""
+    nh, nl = len(_TBT_HEAD), len(_TCL_LAYER)
+    st = dict(zip(_TBT_HEAD, saved[:nh]))
+    st["layers"] = []
+    for l in range(layers):
+        sv = dict(zip(_TCL_LAYER, saved[nh + nl * l: nh + nl * (l + 1)]))
+        b = 5 + 16 * l
+        sv["wqkv"] = torch.cat((params[b], params[b + 2], params[b + 4]), 0)
+        st["layers"].append(sv)
+    return st
+
+
+@custom_op("tag::text_bert", mutates_args=())
+def text_bert(input_ids: Tensor, token_type_ids: Optional[Tensor], attention_mask: Tensor, params: List[Tensor], heads: int,
+              eps: float, pad_id: int, pool_mode: int, norm: int, p_hidden: float, p_attn: float, seed: int,
+              need_grad: bool) -> Tuple[Tensor, Tensor, List[Tensor]]:
+    """Bert.forward / SentenceBert.forward (models/text_encoder.py:281-308): input_ids, attention_mask (R, L) int64,
+    token_type_ids the same or None, params in the order of ops.text_bert_param_names -> token_emb (R, L, D) the last hidden state,
+    seq_emb (R, D) pooled (0 [CLS], 1 masked mean) and normalised (0 none, 1 F.normalize, 2 the retrieval model's, forward-only),
+    and the saved state (ops.TEXT_BERT_SAVED_HEAD, then ops.TEXT_CLAP_SAVED_LAYER per layer; empty when need_grad is False)."""
+    tok, seq, st = ops.text_bert_forward(input_ids, token_type_ids, attention_mask, list(params), heads, eps, pad_id, pool_mode, norm,
+                                         need_grad, p_hidden, p_attn, seed)
+    if st is None:
+        return tok, seq, []
+    if st["raw"] is seq:
+        st = dict(st, raw=seq.clone())                            # an operator may not return one tensor twice
+    return tok, seq, [st[k] for k in _TBT_HEAD] + [sv[k] for sv in st["layers"] for k in _TCL_LAYER]
+
+
+@text_bert.register_fake
+def _(input_ids, token_type_ids, attention_mask, params, heads, eps, pad_id, pool_mode, norm, p_hidden, p_attn, seed, need_grad):
+    R, L = input_ids.shape
+    D, I = params[0].shape[1], params[5 + 10].shape[0]
+    M = R * L
+    x = params[0]
+    out = (x.new_empty(R, L, D), x.new_empty(R, D))
+    if not need_grad:
+        return (*out, [])
+    head = [input_ids.new_empty(R), x.new_empty(M, D), x.new_empty(M), x.new_empty(R, D)]
+    per = [x.new_empty(M, D), x.new_empty(M, 3 * D), x.new_empty(R, heads, L, L), x.new_empty(M, D), x.new_empty(M, D), x.new_empty(M),
+           x.new_empty(M, D), x.new_empty(M, I), x.new_empty(M, I), x.new_empty(M, D), x.new_empty(M)]
+    layers, _ = _dispatch.text_bert_layers(len(params))
+    return (*out, head + [torch.empty_like(t) for _ in range(layers) for t in per])
+
+
+@custom_op("tag::text_bert_backward", mutates_args=())
+def text_bert_backward(dtok: Optional[Tensor], dseq: Optional[Tensor], input_ids: Tensor, token_type_ids: Optional[Tensor],
+                       saved: List[Tensor], params: List[Tensor], heads: int, pad_id: int, pool_mode: int, norm: int,
+                       p_hidden: float, p_attn: float, seed: int, need: List[bool]) -> List[Tensor]:
+    """-> one gradient per parameter; an entry that is not needed (need[i] False, the pooler's always) is an empty tensor."""
+    st = _tbt_saved(list(saved), list(params), _dispatch.text_bert_layers(len(params))[0])
+    g = ops.text_bert_backward(dtok, dseq, input_ids, token_type_ids, st, list(params), heads, pad_id, pool_mode, norm, p_hidden,
+                               p_attn, seed, need=list(need))
+    return [t.view(p.shape) if t is not None else p.new_empty(0) for t, p in zip(g, params)]
+
+
+@text_bert_backward.register_fake
+def _(dtok, dseq, input_ids, token_type_ids, saved, params, heads, pad_id, pool_mode, norm, p_hidden, p_attn, seed, need):
+    return [torch.empty_like(p) if n else p.new_empty(0) for p, n in zip(params, need)]
+
+
+def _tbt_setup(ctx, inputs, output):
+    input_ids, type_ids, _, params, heads, _, pad_id, pool_mode, norm, p_hidden, p_attn, seed, _ = inputs
+    _, _, saved = output
+    ctx.has_types = type_ids is not None
+    ctx.save_for_backward(input_ids, *([type_ids] if ctx.has_types else []), *saved, *params)
+    ctx.meta = (heads, pad_id, pool_mode, norm, p_hidden, p_attn, seed, len(saved))
+    pooler = _dispatch.text_bert_layers(len(params))[1]
+    ctx.need = [bool(p.requires_grad) and not (pooler and i >= len(params) - 2) for i, p in enumerate(params)]
+
+
+def _tbt_backward(ctx, dtok, dseq, _dsaved):
+    heads, pad_id, pool_mode, norm, p_hidden, p_attn, seed, ns = ctx.meta
+    t = list(ctx.saved_tensors)
+    input_ids = t.pop(0)
+    type_ids = t.pop(0) if ctx.has_types else None
+    saved, params = t[:ns], t[ns:]
+    if (dtok is None and dseq is None) or not any(ctx.need):
+        return (None,) * 13
+    if ns == 0:
+        raise RuntimeError("tag::text_bert ran with need_grad = False: nothing was saved for a backward pass")
+    if dtok is not None:
+        dtok = dtok.contiguous()
+    if dseq is not None:
+        dseq = dseq.contiguous()
+    g = torch.ops.tag.text_bert_backward(dtok, dseq, input_ids, type_ids, saved, params, heads, pad_id, pool_mode, norm, p_hidden,
+                                         p_attn, seed, ctx.need)
+    return (None, None, None, [t if n else None for t, n in zip(g, ctx.need)], *([None] * 9))
+
+
+register_autograd("tag::text_bert", _tbt_backward, setup_context=_tbt_setup)
+
+
 # ------------------------------------------------------------------------------------------------ M1/M2 frame x phrase heads
 @custom_op("tag::frame_match", mutates_args=())
 def frame_match(audio: Tensor, text: Tensor, kind: int, l2norm: bool, scale: bool) -> Tensor:
@@ -1169,4 +1268,4 @@ OP_NAMES = ["logmel", "conv3x3", "conv3x3_dgrad", "conv3x3_wgrad", "conv3x3_bn_r
             "cross_cnn8rnn", "cross_cdur", "tagging_head", "tagging_head_backward", "masked_frame_bce",
             "masked_frame_bce_backward", "text_gru", "text_gru_backward", "text_selfattn", "text_selfattn_backward", "infonce",
             "infonce_backward", "triplet", "triplet_backward", "milnce", "milnce_backward", "text_intra", "text_intra_backward",
-            "clip_bce", "clip_bce_backward", "text_clap", "text_clap_backward"]
+            "clip_bce", "clip_bce_backward", "text_clap", "text_clap_backward", "text_bert", "text_bert_backward"]
