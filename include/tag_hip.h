@@ -1318,6 +1318,33 @@ int tag_sed_counts(const int64_t* regions, const int32_t* counts, int max_region
                    double segment_resolution, int32_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Score-based PSDS: the PSDS counts of EVERY decision threshold a pair's frame scores define (psds_scores.hip;
+ * utils/eval_util.py:226-292 compute_psds_sed_scores of the reference hands the raw scores to sed_scores_eval's
+ * intersection_based.psd_roc, where every distinct score is a threshold; utils/psds_scores.py restates that on the host over
+ * utils/grounding_eval.py psds_operating_point and is the yardstick).  One launch, one workgroup per pair.
+ * sim (B rows of T fp32 frame scores, row stride ld >= T in floats); gt (B,max_gt,2) double [onset, offset] in seconds and
+ * gt_count (B) int32 rows in use per pair, as for tag_grounding_counts.  With v_1 < ... < v_m the distinct non-NaN scores of a
+ * row (-0.0 and +0.0 are one value, written as +0.0; a NaN score is never active and is no value), v_0 = -inf, and
+ * c_k = {psds_tp, psds_fp} of the detections of regime k -- the maximal runs [on, off) of frames with score > v_k, as seconds
+ * ((double)frame * time_resolution), no median filter and no connect step -- against the pair's ground truths taken as one
+ * file, EXACTLY psds_operating_point's integers (fp64, IEEE division, numpy's order of additions; c_m = {0, 0}):
+ *   values   (B,T)   fp32   v_1 .. v_m ascending, then +inf
+ *   deltas   (B,T,2) int32  deltas[b][j] = c_{j+1} - c_j for j < m, then 0
+ *   base     (B,2)   int32  c_0
+ *   n_values (B)     int32  m; it is authoritative: a genuine +inf score is a value like any other (its regime counts {0, 0})
+ * so the counts of the pair at a threshold theta are base + the deltas of every value <= theta.  EVERY entry of the four outputs
+ * is written.  A pair without a ground truth: psds_tp = 0 and every detection is a false positive.  No atomics, no host read, no
+ * floating-point value crosses lanes: the same bits on every run.  gt_count[b] > max_gt (or negative) is clamped, never read
+ * out of bounds.
+ * TAG_EINVAL before any launch, the numbers named in tag_last_error: a null pointer (gt may be null when max_gt == 0), B < 1,
+ * T outside 1 .. TAG_PSDS_SCORES_MAX_T, ld < T, max_gt outside 0 .. 128, time_resolution <= 0, dtc or gtc outside [0, 1].
+ * ------------------------------------------------------------------------------------------- */
+#define TAG_PSDS_SCORES_MAX_T 1024
+int tag_psds_score_deltas(const float* sim, int ld, int B, int T, const double* gt, const int32_t* gt_count, int max_gt,
+                          double time_resolution, double dtc, double gtc, float* values, int32_t* deltas, int32_t* base,
+                          int32_t* n_values, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Phrase-to-label cosine map (label_map.hip; ASMapping*Dataset of datasets/class_mapping_dataset.py in the reference call
  * sklearn's cosine_similarity(phrase, label_embs) on the host per item).  x (N, D) phrases with row stride ldx, e (C, D) labels
  * with row stride lde (both >= D, in floats), all fp32.  ws (tag_label_map_ws_bytes = 4 (N + C), a function of the shape alone,

@@ -6,7 +6,7 @@
 // (-fno-fast-math -ffp-contract=off, csrc/Makefile) AND numpy's order of additions:
 //
 //   * a sum over the ground truths of one detection (det_prec.sum(1) and its masked variant) is numpy's contiguous fp64
-//     reduction, np_sum below: fewer than 8 terms left to right; up to 128 terms eight running lanes r[j] += a[i + j], combined as
+//     reduction, np_sum of grounding_pairs.h: fewer than 8 terms left to right; up to 128 terms eight running lanes r[j] += a[i + j], combined as
 //     ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the remainder added in order; above 128 terms the halves (the first rounded down to a
 //     multiple of 8) summed on their own and added.
 //   * a sum over the detections of one ground truth (gt_cov.sum(0) and its masked variants) is left to right in d when the file
@@ -23,92 +23,13 @@
 // The ratios are recomputed where they are needed (the same operations give the same bits); the ground truths of the clip are
 // staged in LDS, the detections are read from global memory at a wave-uniform address.  The integer counts are folded with a
 // butterfly, which is exact.  No atomics; every entry of out is written.
-#include "tag_common.h"
+#include "grounding_pairs.h"      // np_sum, pair_ratios, Sum3: shared with psds_scores.hip
 #include <limits.h>
 
 namespace {
 
 constexpr int MAX_GT = 128;          // ground-truth rows per clip (LDS staging; numpy's pairwise block size, so row sums never recurse)
 constexpr int MAX_REGIONS = 32768;   // detection flags: one byte each in dynamic LDS
-constexpr int PW_BLOCK = 128;        // numpy's PW_BLOCKSIZE
-constexpr int PW_DEPTH = 12;         // halving MAX_REGIONS down to PW_BLOCK takes 8 levels
-
-struct Sum3 {                        // three sums carried through the same order of additions
-    double a, b, c;
-};
-__device__ __forceinline__ Sum3 operator+(Sum3 x, Sum3 y) { return Sum3{x.a + y.a, x.b + y.b, x.c + y.c}; }
-
-// numpy's pairwise_sum for n <= 128 terms term(lo) .. term(lo + n - 1)
-template <class V, class F>
-__device__ __forceinline__ V np_block(int lo, int n, F term) {
-    if (n < 8) {
-        V s{};
-        for (int i = 0; i < n; ++i) s = s + term(lo + i);
-        return s;
-    }
-    V r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = term(lo + j);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = r[j] + term(lo + i + j);
-    }
-    V s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) s = s + term(lo + i);
-    return s;
-}
-
-// numpy's pairwise_sum for any n <= MAX_REGIONS: the recursion pw(lo, n) = pw(lo, n2) + pw(lo + n2, n - n2), n2 = n / 2 rounded
-// down to a multiple of 8, on an explicit stack
-template <class V, class F>
-__device__ __forceinline__ V np_sum(int n, F term) {
-    if (n <= PW_BLOCK) return np_block<V>(0, n, term);
-    int lo[PW_DEPTH], len[PW_DEPTH], state[PW_DEPTH];
-    V left[PW_DEPTH];
-    V ret{};
-    int sp = 0;
-    lo[0] = 0, len[0] = n, state[0] = 0;
-    while (sp >= 0) {
-        if (len[sp] <= PW_BLOCK) {
-            ret = np_block<V>(lo[sp], len[sp], term);
-            --sp;
-            continue;
-        }
-        int n2 = len[sp] / 2;
-        n2 -= n2 % 8;
-        if (state[sp] == 0) {
-            state[sp] = 1;
-            lo[sp + 1] = lo[sp], len[sp + 1] = n2, state[sp + 1] = 0;
-            ++sp;
-        } else if (state[sp] == 1) {
-            left[sp] = ret;
-            state[sp] = 2;
-            lo[sp + 1] = lo[sp] + n2, len[sp + 1] = len[sp] - n2, state[sp + 1] = 0;
-            ++sp;
-        } else {
-            ret = left[sp] + ret;
-            --sp;
-        }
-    }
-    return ret;
-}
-
-// one (detection, ground truth) pair as utils/grounding_eval.py _pair_ratios computes it (np.minimum / np.maximum spelled out)
-struct Pair {
-    bool cross;
-    double det_prec, gt_cov;
-};
-__device__ __forceinline__ Pair pair_ratios(double on_d, double off_d, double on_g, double off_g) {
-    Pair p;
-    p.cross = (on_d <= off_g) && (on_g <= off_d);
-    const double lo = (on_d >= on_g || on_d != on_d) ? on_d : on_g;
-    const double hi = (off_d <= off_g || off_d != off_d) ? off_d : off_g;
-    const double inter = hi - lo;
-    p.det_prec = p.cross ? inter / (off_d - on_d) : 0.0;
-    p.gt_cov = p.cross ? inter / (off_g - on_g) : 0.0;
-    return p;
-}
 
 constexpr unsigned char F_DTC = 1, F_RELEVANT = 2;
 

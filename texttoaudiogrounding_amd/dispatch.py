@@ -2960,6 +2960,53 @@ def sed_counts(regions, counts, gt, gt_count, time_resolution, t_collar=0.2, per
 
 
 # ------------------------------------------------------------------------------------------------
+# score-based PSDS: the counts of every threshold the scores define (utils/psds_scores.py on the host), psds_scores.hip
+# ------------------------------------------------------------------------------------------------
+
+#: the most frames per pair tag_psds_score_deltas takes (= TAG_PSDS_SCORES_MAX_T of include/tag_hip.h)
+PSDS_SCORES_MAX_T = 1024
+
+
+def psds_score_deltas(frame_sim, gt, gt_count, time_resolution, dtc=0.5, gtc=0.5, check=True):
+    """Frame scores + the pairs' ground truths -> ``(values (B,T) fp32, deltas (B,T,2) int32, base (B,2) int32, n_values (B,)
+    int32)``: per pair the ascending distinct non-NaN scores v_1 .. v_m (then +inf; -0.0 is +0.0), the differences
+    c_{j+1} - c_j of the PSDS counts c_k = (psds_tp, psds_fp) of the regimes ``score > v_k`` (then 0), c_0 (v_0 = -inf) and m --
+    the integers utils.psds_scores.pair_regimes gives, exactly (psds_scores.hip).  ``n_values`` is authoritative: a genuine +inf
+    score is a value.  frame_sim (B, T) float32 on the device, T <= PSDS_SCORES_MAX_T; a view with unit inner stride and a row
+    stride >= T is taken as it is.  gt (B,Gmax,2) float64 seconds and gt_count (B,) int32, on the device or on the host
+    (utils.device_eval.ground_truth_arrays), Gmax <= 128.  Every entry of the four outputs is written; one launch.
+    check: refuse gt_count outside [0, Gmax] (ONE host read for a device tensor); the kernel clamps it either way."""
+    if not frame_sim.is_cuda:
+        _chk(frame_sim, "frame_sim")
+    if frame_sim.dtype != F32 or frame_sim.dim() != 2 or frame_sim.shape[0] < 1 or frame_sim.shape[1] < 1:
+        raise RuntimeError(f"frame_sim: expected a float32 (B >= 1, T >= 1) matrix, got {frame_sim.dtype} {tuple(frame_sim.shape)}")
+    B, T = frame_sim.shape
+    if frame_sim.stride(1) != 1 or (B > 1 and frame_sim.stride(0) < T):
+        frame_sim = frame_sim.contiguous()
+    ld = frame_sim.stride(0) if B > 1 else T
+    gt = torch.as_tensor(gt)
+    if gt.dim() != 3 or gt.shape[2] != 2:
+        raise RuntimeError(f"gt: expected float64 ({B},Gmax,2), got {gt.dtype} {tuple(gt.shape)}")
+    max_gt = gt.shape[1]
+    gt_count = torch.as_tensor(gt_count)
+    if gt_count.dtype != torch.int32 or tuple(gt_count.shape) != (B,):
+        raise RuntimeError(f"gt_count: expected {torch.int32} ({B},), got {gt_count.dtype} {tuple(gt_count.shape)}")
+    if check:
+        lo_g, hi_g = torch.stack([gt_count.min(), gt_count.max()]).tolist()
+        if lo_g < 0 or hi_g > max_gt:
+            raise RuntimeError(f"psds_score_deltas: gt_count must lie in [0, {max_gt}], got [{lo_g}, {hi_g}]")
+    gt = _grounding_tensor(gt, "gt", torch.float64, (B, max_gt, 2), frame_sim, "")
+    gt_count = gt_count.to(frame_sim.device).contiguous()
+    values = torch.empty(B, T, device=frame_sim.device, dtype=F32)
+    deltas = torch.empty(B, T, 2, device=frame_sim.device, dtype=torch.int32)
+    base = torch.empty(B, 2, device=frame_sim.device, dtype=torch.int32)
+    n_values = torch.empty(B, device=frame_sim.device, dtype=torch.int32)
+    call("tag_psds_score_deltas", ptr(frame_sim), ld, B, T, ptr(gt) if max_gt else None, ptr(gt_count), max_gt,
+         float(time_resolution), float(dtc), float(gtc), ptr(values), ptr(deltas), ptr(base), ptr(n_values))
+    return values, deltas, base, n_values
+
+
+# ------------------------------------------------------------------------------------------------
 # phrase-to-label cosine map of the ASMapping datasets (sklearn's cosine_similarity per item on the host in the reference),
 # label_map.hip
 # ------------------------------------------------------------------------------------------------

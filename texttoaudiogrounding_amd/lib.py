@@ -264,6 +264,7 @@ _SIGS = {
     "tag_grounding_counts": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, c_double, P, P]),
     "tag_segments_double": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, c_int, P]),
     "tag_sed_counts": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, c_double, c_double, P, P]),
+    "tag_psds_score_deltas": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_double, c_double, c_double, P, P, P, P, P]),
     "tag_label_map_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tag_label_map": (c_int, [P, c_int, P, c_int, c_float, c_float, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "tag_label_map_topk": (c_int, [P, c_int, c_float, c_float, P, c_int, c_int, c_int, P]),

@@ -396,6 +396,22 @@ class StrongRunner:
         ops.check_async_errors()
         return result
 
+    def evaluate_psds_scores(self, batches, ground_truth: Dict, durations: Dict, eval_config: Dict) -> Dict:
+        """The reference's headline PSDS (eval_util.compute_psds_sed_scores, printed by ``evaluate`` of run_strong.py:867-888
+        and called after every validation epoch): intersection-based PSDS with every distinct frame score as a threshold, no
+        median filter and no connect step, on the device (device_eval.ScorePsdsEvaluator; utils/psds_scores.py defines it).
+        ``batches``, ``ground_truth`` and ``durations`` as for ``evaluate``, the same key rule, and a pair without a
+        ground-truth row is left out.  eval_config: ``time_resolution``, optionally ``dtc_threshold`` (0.5), ``gtc_threshold``
+        (0.5) and ``max_efprs`` (a sequence -> ``psds`` is {max_efpr: value}) or ``max_efpr`` (None: the largest eFPR).
+        Returns ScorePsdsEvaluator.compute's dict; the pairs of this rank's batches only."""
+        ev = device_eval.ScorePsdsEvaluator(float(eval_config["time_resolution"]), dtc=eval_config.get("dtc_threshold", 0.5),
+                                            gtc=eval_config.get("gtc_threshold", 0.5), device=self.device)
+        self._update_over_batches(ev, batches, ground_truth)
+        max_efpr = eval_config["max_efprs"] if "max_efprs" in eval_config else eval_config.get("max_efpr")
+        result = ev.compute(float(sum(durations[k] for k in ground_truth)), max_efpr=max_efpr)
+        ops.check_async_errors()
+        return result
+
 
 class ClassMappingRunner(StrongRunner):
     """Training-step driver of the class-mapping baseline (Runner.forward of python_scripts/training/mapping_to_class/

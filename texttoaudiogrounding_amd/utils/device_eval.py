@@ -111,6 +111,92 @@ class GroundingEvaluator:
                 "recall": np.array([r["recall"] for r in ev.operating_points]), "thresholds": self.thresholds.copy()}
 
 
+def best_tp_per_fp(counts: torch.Tensor) -> torch.Tensor:
+    """Operating-point counts (P, 2) int64 [psds_tp, psds_fp] on the device -> (U, 2) [the largest psds_tp, psds_fp] per
+    distinct psds_fp, ascending.  ``psd_roc`` keeps the best TP ratio at equal eFPR anyway, so its staircase is the same."""
+    fp, inverse = torch.unique(counts[:, 1], return_inverse=True)
+    best_tp = torch.full_like(fp, -1).scatter_reduce_(0, inverse, counts[:, 0], "amax")
+    return torch.stack([best_tp, fp], 1)
+
+
+class ScorePsdsEvaluator:
+    """Score-based PSDS (the reference's ``compute_psds_sed_scores``; utils/psds_scores.py is the definition and the yardstick)
+    over batches on the device: every distinct frame score of the evaluation is a decision threshold, no median filter and no
+    connect step.
+
+    ``update`` runs ``ops.psds_score_deltas`` (csrc/psds_scores.hip), which leaves per pair the sorted distinct scores and the
+    change of (psds_tp, psds_fp) at each of them, and keeps the batch's tensors on the device: 12 bytes per evaluated frame
+    (4 for the value, 8 for the two int32 deltas) plus 4 per pair, until ``reset``.  ``compute`` merges them there --
+    ``psds_scores.points_from_deltas``: sort by value, prefix sum, the last entry of each run of equal values -- and keeps the
+    best TP count per distinct FP count, which is all ``psd_roc`` looks at.  The host functions stay the yardstick: the score
+    equals ``psds_scores.psds_from_scores`` over a table that holds every pair once, as a float.
+
+    A data-parallel caller gathers ``state()`` of every rank before ``compute`` (not done here).
+    """
+
+    def __init__(self, time_resolution: float, dtc: float = 0.5, gtc: float = 0.5, device="cuda"):
+        if not 0.0 <= dtc <= 1.0 or not 0.0 <= gtc <= 1.0:
+            raise ValueError("ScorePsdsEvaluator: dtc and gtc must be between 0 and 1")
+        if time_resolution is None or not time_resolution > 0:
+            raise ValueError("ScorePsdsEvaluator: time_resolution must be positive")
+        self.time_resolution, self.dtc, self.gtc = float(time_resolution), float(dtc), float(gtc)
+        self.device = torch.device(device)
+        self.reset()
+
+    def reset(self):
+        self._values, self._deltas, self._n_values = [], [], []
+        self.base = torch.zeros(2, device=self.device, dtype=torch.int64)       # sum of the pairs' c_0
+        self.n_refs = torch.zeros((), device=self.device, dtype=torch.int64)
+        self.bytes_read = 0                                                      # size of the tensor the last compute read
+
+    def update(self, frame_sim: torch.Tensor, gt, gt_count):
+        """frame_sim (B, T) float32 on the device (B and T may differ between batches); gt, gt_count as
+        ``ground_truth_arrays`` returns them (host arrays are checked here and copied over; device tensors are taken as they
+        are).  One kernel launch, no host read."""
+        gt, gt_count = torch.as_tensor(gt), torch.as_tensor(gt_count)
+        if not gt_count.is_cuda and gt_count.numel() and (int(gt_count.min()) < 0 or int(gt_count.max()) > gt.shape[1]):
+            raise ValueError(f"gt_count must lie in [0, {gt.shape[1]}]")
+        gt_count = gt_count.to(self.device)
+        values, deltas, base, n_values = ops.psds_score_deltas(frame_sim, gt, gt_count, self.time_resolution, self.dtc, self.gtc,
+                                                               check=False)
+        self._values.append(values)
+        self._deltas.append(deltas)
+        self._n_values.append(n_values)
+        self.base += base.sum(0)
+        self.n_refs += gt_count.sum()
+
+    def state(self) -> dict:
+        """The held tensors: per batch ``values`` (B,T) fp32, ``deltas`` (B,T,2) int32 and ``n_values`` (B,) int32 (the entries
+        j < n_values[b] of a row count), and the running sums ``base`` (2,) and ``n_refs`` () int64."""
+        return {"values": list(self._values), "deltas": list(self._deltas), "n_values": list(self._n_values),
+                "base": self.base, "n_refs": self.n_refs}
+
+    def compute(self, total_duration_s: float, max_efpr=None) -> dict:
+        """{"psds": float, or {max_efpr: float} for a sequence, "efpr", "etpr" (the PSD-ROC staircase), "n_refs",
+        "n_operating_points" (1 + the distinct scores)}.  max_efpr per hour; None: the largest eFPR; <= 0: the largest eTPR.
+        total_duration_s: seconds of audio of the evaluated files (the PSDS metadata).
+
+        The merge runs on the device.  Host reads: the sizes of three data-dependent selections (the entries in use, the
+        operating points, the distinct FP counts) and ONE (U + 1, 2) int64 tensor, U = the distinct FP counts among the
+        operating points -- 16 (U + 1) bytes; nothing proportional to the number of frames."""
+        from . import psds_scores
+        if self._values:
+            used = torch.cat([(torch.arange(v.shape[1], device=v.device) < n[:, None]).reshape(-1)
+                              for v, n in zip(self._values, self._n_values)])
+            values = torch.cat([v.reshape(-1) for v in self._values])[used]
+            deltas = torch.cat([d.reshape(-1, 2) for d in self._deltas])[used]
+        else:
+            values = torch.zeros(0, device=self.device, dtype=torch.float32)
+            deltas = torch.zeros(0, 2, device=self.device, dtype=torch.int32)
+        thresholds, counts = psds_scores.points_from_deltas(values, deltas, self.base)
+        head = torch.stack([self.n_refs, torch.full_like(self.n_refs, thresholds.numel())])
+        table = torch.cat([head[None, :], best_tp_per_fp(counts)]).cpu().numpy()
+        self.bytes_read = int(table.nbytes)
+        n_refs, n_points = int(table[0, 0]), int(table[0, 1])
+        psds, efpr, etpr = psds_scores.psds_from_counts(table[1:], n_refs, float(total_duration_s), max_efpr)
+        return {"psds": psds, "efpr": efpr, "etpr": etpr, "n_refs": n_refs, "n_operating_points": n_points}
+
+
 class SedEvaluator:
     """Accumulates the sed_eval protocol (event-based and segment-based F-score / error rate, utils/sed_metrics.py) over
     batches on the device, for a row of operating points.
